@@ -6,11 +6,18 @@ A "step" is one reverse-diffusion step of the device-resident sampler over the w
 L-layer EGNN forward eps_theta(x_t, h_t, t) plus the fused eps -> mu -> noise -> state update kernel
 (parts/train_per_iretation.py:335-373).  Inputs (state, conditioning, weights, schedule table) are
 resident in HBM before the timed region.  With --gpus N every rank samples its own batch of graphs
-(independent replicas: no data-path collective, weak scaling); only the timing uses a collective.  The
-same JSON line carries a `ddp_train` sub-record (BASELINE configs[3] per-rank shape: forward + backward +
+(independent replicas: no data-path collective, weak scaling); only the timing uses a collective.  With
+--full the same JSON line carries a `ddp_train` sub-record (BASELINE configs[3] per-rank shape: forward + backward +
 per-layer RCCL gradient all-reduce + Adam), which is where the data-path collective of the N > 1 curve is.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up with W steps, times exactly K steps once and prints the headline line.  `--full` adds
+everything else the benchmark measures: the median of `--reps` (default 5) repetitions, the hipGraph replay time,
+the `ddp_train`, `slab_4096`, `tolerance_grade`, `fp16`, `c3`, `ddp_train_tolerance_grade`, `latency` and
+`cpu_baseline` sub-records.  `--dump-outputs DIR` writes what the timed path computed in its last step (the
+sampler state, or the loss and parameters with --mode train) as DIR/<name>.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 `--gpus N` from a plain shell starts the N ranks itself (a torch.distributed.run child process, before
 anything has touched the GPU); under torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE.
@@ -33,6 +40,30 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 H, M, W, A, T = 36, 256, 1024, 2, 1000
+# longest reverse chain from x_T the sampler legs run: the untrained weights overflow the state to inf / NaN after about 100
+# steps (the fp32 oracle at the headline shape), and a non-finite state runs faster and invalidates the line
+CHAIN_STEPS = 50
+DUMP_LIMIT_BYTES = 60 * 10 ** 6      # under 64 MB with the .npy headers
+
+
+def write_outputs(out_dir, arrays):
+    """`--dump-outputs`: every array as out_dir/<name>.npy, float64 kept, everything else as float32.  If all of them together
+    exceed DUMP_LIMIT_BYTES, an array over its even share of the limit is replaced by a fixed sample of its flattened
+    elements (seed 0, sorted indices, the same for every run of the same shape)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        arrs[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    if sum(a.nbytes for a in arrs.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(arrs)
+        for name, a in arrs.items():
+            if a.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                arrs[name] = a.reshape(-1)[idx]
+    for name, a in arrs.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 # algorithmic work of the fused edge kernel (SURVEY.md 8(d)): per edge per layer
@@ -204,7 +235,7 @@ class Ranks:
             dist.destroy_process_group()
 
 
-def train_leg(args, rk, steps, warmup, batch):
+def train_leg(args, rk, steps, warmup, batch, dump_dir=None):
     """BASELINE configs[3] per-rank shape: 64-atom SiO2 training, `batch` graphs per rank (256 -> global 2048 on 8 GPUs);
     one step = diffuse_as_batch + EGNN forward + backward (HIP) + per-layer gradient all-reduce (RCCL, issued from inside
     the backward) + Adam.  Timed twice on N > 1: with the all-reduce and without it (what the same rank does alone)."""
@@ -327,6 +358,8 @@ def train_leg(args, rk, steps, warmup, batch):
     final = torch.stack(losses[-steps:]).float()
     out["final_loss"] = float(final[-1])
     out["finite"] = bool(torch.isfinite(final).all())
+    if dump_dir and rank == 0:    # what the last timed step left: the losses of the timed steps and the updated parameters
+        write_outputs(dump_dir, {"loss": final, **{f"param.{k}": p for k, p in net.named_parameters()}})
     return out
 
 
@@ -350,8 +383,33 @@ def golden_error_from_log(precision):
     return best
 
 
-def sample_leg(args, rk, precision=None, batch=None, atoms=None, steps=None, warmup=None, reps=None):
-    """the sampler leg at the headline shape (defaults from the command line) or at a sub-record's shape / precision"""
+def run_chains(smp, rk, warmup, steps):
+    """init + `warmup` untimed steps, then `steps` timed ones (each timed piece bracketed by rk.timed).  A chain that has
+    run CHAIN_STEPS steps from x_T starts again from the same seeded x_T (same noise), outside the timed pieces; with
+    warmup + steps <= CHAIN_STEPS this is one chain and one timed piece.  -> (seconds, worst non-finite graph count,
+    (pos, h, flags) after the last step)"""
+    chain, bad_max, el = 0, 0, 0.0
+    smp.init()
+    for n_left, timed in ((warmup, False), (steps, True)):
+        while n_left > 0:
+            if chain == CHAIN_STEPS:
+                bad_max = max(bad_max, int(smp.state()[2].sum()))
+                smp.init()
+                chain = 0
+            n = min(n_left, CHAIN_STEPS - chain)
+            if timed:
+                el += rk.timed(lambda: smp.run(nsteps=n, use_graph=False, sync=True))
+            else:
+                smp.run(nsteps=n, use_graph=False)
+            chain += n
+            n_left -= n
+    pos, h, flags = smp.state()
+    return el, max(bad_max, int(flags.sum())), (pos, h, flags)
+
+
+def sample_leg(args, rk, precision=None, batch=None, atoms=None, steps=None, warmup=None, reps=None, dump_dir=None):
+    """the sampler leg at the headline shape (defaults from the command line) or at a sub-record's shape / precision;
+    the hipGraph replay extra only with --full"""
     import ctypes as C
     import diffusion_model_amd as dma
     from diffusion_model_amd import _lib
@@ -368,36 +426,39 @@ def sample_leg(args, rk, precision=None, batch=None, atoms=None, steps=None, war
     smp = dma.DeviceSampler(net, proc, [n] * B, cond, atom_type_size=A, seed=rank, norm_scope="graph", device=dev)
     lib = _lib.lib()
     reps = max(1, reps or args.reps)
-    if K + Wm > T:
-        raise SystemExit(f"--steps + --warmup must be <= T = {T}")
 
-    # warm-up
-    smp.init()
-    smp.run(nsteps=Wm, use_graph=False)
-    # ---- timed region: `reps` repetitions of EXACTLY K steps from the same initial state (seeded x_T, h_T after the
-    # warm-up steps), each bracketed by barrier + synchronize, MAX over ranks; HIP events around every fused
-    # edge-kernel launch.  The median repetition is reported.
+    if reps > 1:
+        # warm-up before the first of several repetitions (a single repetition is warmed up by its own Wm steps)
+        run_chains(smp, rk, Wm, 0)
+    # ---- timed region: `reps` repetitions (1 unless --full) of EXACTLY K steps from the same initial state (seeded x_T,
+    # h_T after the warm-up steps; restarted from x_T every CHAIN_STEPS steps, run_chains), each bracketed by barrier +
+    # synchronize, MAX over ranks; HIP events around every fused edge-kernel launch.  The median repetition is reported.
     _lib.check(lib.egnn_profile_enable(smp.ctx.handle, 1))
     rep_s = []
     bad_total = 0
     for _ in range(reps):
-        smp.init()
-        smp.run(nsteps=Wm, use_graph=False)
-        rep_s.append(rk.timed(lambda: smp.run(nsteps=K, use_graph=False, sync=True)))
-        bad_total = max(bad_total, int(smp.state()[2].sum()))
+        el, bad, last = run_chains(smp, rk, Wm, K)
+        rep_s.append(el)
+        bad_total = max(bad_total, bad)
+    if dump_dir and rank == 0:
+        # the state the last timed step left: positions x_t, atom-type features h_t, per-graph non-finite flags
+        write_outputs(dump_dir, dict(zip(("pos", "h", "nonfinite"), last)))
     edge_ms, edge_n, node_ms = C.c_float(0), C.c_int(0), C.c_float(0)
     _lib.check(lib.egnn_profile_read(smp.ctx.handle, C.byref(edge_ms), C.byref(edge_n), C.byref(node_ms)))
     _lib.check(lib.egnn_profile_enable(smp.ctx.handle, 0))
     elapsed = statistics.median(rep_s)
     # ---- extra: the same K steps replayed from the captured hipGraph (no events) ----
     graph_ms = None
-    if smp.t >= K + 2:
+    if args.full:
+        # (from a fresh chain: 2 replays to capture, then up to K steps within CHAIN_STEPS)
+        Kg = min(K, CHAIN_STEPS - 2)
+        smp.init()
         smp.run(nsteps=2, use_graph=True)
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
-        smp.run(nsteps=K, use_graph=True, sync=True)
+        smp.run(nsteps=Kg, use_graph=True, sync=True)
         torch.cuda.synchronize(dev)
-        graph_ms = (time.perf_counter() - t1) * 1e3 / K
+        graph_ms = (time.perf_counter() - t1) * 1e3 / Kg
         bad_total = max(bad_total, int(smp.state()[2].sum()))
 
     E = B * n * (n - 1)
@@ -432,7 +493,7 @@ def sample_leg(args, rk, precision=None, batch=None, atoms=None, steps=None, war
                                f"T=1000 reverse steps, fully connected (E={E}/GPU)",
                    "global_batch": world * B, "parallelism": f"replicas x{world} (no data-path collective)"},
         "timed_region": {"repetitions": reps, "steps_each": K, "ms_per_step_each": [s * 1e3 / K for s in rep_s],
-                         "reported": "median repetition"},
+                         "reported": "median repetition", "chain_restart_every": CHAIN_STEPS},
         "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
                      "frac": achieved / peak, "traffic": traffic,
                      "traffic_source": (f"profiles/traffic.json (rocprofv3 --pmc, separate passes of this command at git head "
@@ -457,10 +518,11 @@ def sample_leg(args, rk, precision=None, batch=None, atoms=None, steps=None, war
                      # the first Linear layers are evaluated per node (factorised), so the matrix cores execute
                      # only the second-layer products of the count above
                      "mfma_executed_flop_per_launch": 2.0 * (W * M + W * W) * E},
-        "graph_replay_ms_per_step": graph_ms,
         "node_kernels_ms_per_layer": node_ms.value * 2,
         "nonfinite_graphs": bad_total,
     }
+    if args.full:
+        out["graph_replay_ms_per_step"] = graph_ms
     del smp
     return out, sd
 
@@ -518,7 +580,7 @@ def precision_legs(args, rk):
     return out
 
 
-def slab_leg(args, rk, steps, warmup):
+def slab_leg(args, rk, steps, warmup, dump_dir=None):
     """BASELINE configs[4]: one 4096-atom slab (16x16x16 jittered grid, spacing 1.6 A), fixed radius graph with ~10
     neighbours per atom (~40 k directed edges; the reference only has fully connected graphs), T = 1000 sampling.
     N = 1: the device-resident sampler on the one graph (hipGraph replay).  N > 1: the graph's receiving nodes are
@@ -544,7 +606,7 @@ def slab_leg(args, rk, steps, warmup):
            "atoms": n, "directed_edges": int(ei.shape[1]), "radius": radius, "steps": steps, "warmup": warmup,
            "scaling": "strong" if world > 1 else None}
 
-    def time_single():
+    def time_single(dump_dir=None):
         smp = dma.DeviceSampler(net, proc, [n], cond, atom_type_size=A, seed=0, norm_scope="graph", device=dev, edge_index=ei)
         smp.init()
         smp.run(nsteps=warmup, use_graph=True)
@@ -553,12 +615,15 @@ def slab_leg(args, rk, steps, warmup):
         smp.run(nsteps=steps, use_graph=True, sync=True)
         torch.cuda.synchronize(dev)
         el = time.perf_counter() - t0
-        bad = int(smp.state()[2].sum())
+        pos_out, h_out, flags = smp.state()
+        bad = int(flags.sum())
+        if dump_dir:
+            write_outputs(dump_dir, {"pos": pos_out, "h": h_out, "nonfinite": flags})
         del smp
         return el, bad
 
     if world == 1:
-        el, bad = time_single()
+        el, bad = time_single(dump_dir)
         out.update({"value": n * steps / el, "ms_per_step": el * 1e3 / steps, "nonfinite_graphs": bad,
                     "implementation": "DeviceSampler on one GPU, hipGraph replay"})
         return out
@@ -647,13 +712,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the K timed steps; the median is reported")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the K timed steps; the median is reported (default 1, with --full 5)")
     ap.add_argument("--batch", type=int, default=256, help="graphs per GPU")
     ap.add_argument("--atoms", type=int, default=64)
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "bf16x3", "f16c8", "fp32"])
     ap.add_argument("--mode", default="sample", choices=["sample", "train", "slab"],
-                    help="sample = headline metric (default, with the ddp_train sub-record); train = BASELINE configs[3] "
+                    help="sample = headline metric (default; with --full also the ddp_train and the other sub-records); train = BASELINE configs[3] "
                          "shape only (fwd+bwd+all-reduce+Adam) as the headline of the line; slab = BASELINE configs[4] only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train-leg", action="store_true")
@@ -662,7 +728,14 @@ def main():
     ap.add_argument("--no-precision-legs", action="store_true", help="skip the tolerance_grade / fp16 / c3 sub-records")
     ap.add_argument("--train-steps", type=int, default=8)
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the median of --reps repetitions, hipGraph replay, "
+                         "and the ddp_train / slab / precision / latency / CPU-baseline sub-records (the --no-* options select)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -671,7 +744,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={rk.world}")
     valid = True
     if args.mode == "train":
-        tr = train_leg(args, rk, args.steps, args.warmup, args.batch)
+        tr = train_leg(args, rk, args.steps, args.warmup, args.batch, dump_dir=args.dump_outputs)
         out = dict(tr)
         out.update({"n_gpus": rk.world, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                     "dtype": args.precision, "data": "synthetic",
@@ -680,15 +753,16 @@ def main():
                                "parallelism": f"dp{rk.world}"}})
         valid = tr["finite"]
     elif args.mode == "slab":
-        out = slab_leg(args, rk, args.steps, args.warmup)
+        out = slab_leg(args, rk, args.steps, args.warmup, dump_dir=args.dump_outputs)
         out.update({"n_gpus": rk.world, "higher_is_better": True, "vs_baseline": None, "dtype": args.precision,
                     "data": "synthetic", "config": {"workload": "4096-atom slab, radius graph ~40k directed edges, "
                                                                 f"{args.layers}-layer EGNN, T=1000 reverse steps",
                                                     "parallelism": f"node-partitioned x{rk.world}"}})
         valid = out["nonfinite_graphs"] == 0
     else:
-        out, sd = sample_leg(args, rk)
+        out, sd = sample_leg(args, rk, dump_dir=args.dump_outputs)
         valid = out["nonfinite_graphs"] == 0
+    if args.mode == "sample" and args.full:
         if not args.no_train_leg:
             if args.atoms == 64:
                 tr = train_leg(args, rk, args.train_steps, 2, 256)

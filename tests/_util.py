@@ -1,4 +1,5 @@
 """Shared helpers for the test-suite (test infrastructure, not product)."""
+import glob
 import hashlib
 import os
 
@@ -8,8 +9,25 @@ import torch
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+class _Golden(dict):
+    """the arrays of a golden split over several files, with NpzFile's `files`"""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    """tests/golden/<name>, merged with its parts <name>-part<N>.npz where make_golden.py split it (every file < 1 MiB)"""
+    path = os.path.join(GOLDEN, name)
+    parts = sorted(glob.glob(path[:-len(".npz")] + "-part*.npz"))
+    if not parts:
+        return np.load(path, allow_pickle=False)
+    merged = _Golden()
+    for p in [path] + parts:
+        with np.load(p, allow_pickle=False) as z:
+            merged.update({k: z[k] for k in z.files})
+    return merged
 
 
 def dims_for(h, m_size, wm, wx, wh):

@@ -1,7 +1,11 @@
 import os
 import sys
 
-import pytest
+# The CPU oracle is compared with tests/golden bit for bit or at 1e-6.  MKL picks its kernels by CPU vendor, instruction set
+# and thread count unless a reproducibility mode is set, so the suite pins the one the goldens were made in (make_golden.py)
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE,STRICT")
+
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

@@ -28,7 +28,8 @@ import os
 import sys
 import types
 
-import numpy as np
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE,STRICT")    # the suite's MKL mode (tests/conftest.py): CPU-independent results
+import numpy as np  # noqa: E402
 import torch
 
 REF = "/root/reference"
@@ -366,6 +367,28 @@ def run_stats_cases(ER, EA):
     return out
 
 
+PART_BYTES = 960 << 10     # no committed file over 1 MiB: a larger golden goes to <name>.npz + <name>-part<N>.npz
+
+
+def save_golden(name, arrays):
+    """np.savez_compressed, split over files of at most about PART_BYTES each (tests/_util.load_golden merges them again)"""
+    import glob
+    import zlib
+    stem = os.path.join(OUT, name[:-len(".npz")])
+    for stale in glob.glob(stem + "-part*.npz"):
+        os.remove(stale)
+    parts, size = [{}], 0
+    for k, v in arrays.items():
+        n = len(zlib.compress(np.ascontiguousarray(v).tobytes())) + 256
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += n
+    for i, part in enumerate(parts):
+        np.savez_compressed(stem + (f"-part{i}" if i else "") + ".npz", **part)
+
+
 def main():
     assert os.path.isdir(REF), "reference not present: goldens can only be regenerated in the build container"
     _install_stub()
@@ -377,7 +400,7 @@ def main():
     import SNR
     import diffusion_x_h as dxh
 
-    np.savez_compressed(os.path.join(OUT, "egnn_golden.npz"), **run_egnn_cases(EG.EquivariantGNN))
+    save_golden("egnn_golden.npz", run_egnn_cases(EG.EquivariantGNN))
     np.savez_compressed(os.path.join(OUT, "diffusion_golden.npz"), **run_diffusion_cases(dxh, dnew, dold))
     np.savez_compressed(os.path.join(OUT, "aux_golden.npz"), **run_aux_cases(SNR, DP))
     np.savez_compressed(os.path.join(OUT, "learned_legacy_golden.npz"), **run_learned_and_legacy_cases(dxh, dnew, dold))

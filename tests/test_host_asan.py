@@ -36,7 +36,9 @@ def _run(body):
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
         OK, EINVAL, ESTATE = 0, -22, -1
     """ % ASAN_LIB) + textwrap.dedent(body) + "\nprint('CHILD-OK')\n"
-    env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0",
+    # libasan must come first; whatever the environment already preloads stays loaded behind it
+    preload = " ".join(p for p in (asan, os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     r = subprocess.run([sys.executable, "-c", prog], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "CHILD-OK" in r.stdout, f"rc={r.returncode}\nstdout:\n{r.stdout}\nstderr:\n{r.stderr[-4000:]}"

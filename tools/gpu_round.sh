@@ -5,6 +5,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 tag=${1:-r04z}
 mkdir -p gpurun_out/$tag
+o=${BENCH_RECORDS:-bench_records}/$tag; mkdir -p "$o"   # the bench lines' JSON records (--full: with every sub-record)
 python -m pytest tests -m gpu -x -q > gpurun_out/$tag/gpu_tests.log 2>&1; echo "pytest rc=$?" | tee -a gpurun_out/$tag/gpu_tests.log
 tail -3 gpurun_out/$tag/gpu_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/$tag/smoke.log 2>&1; echo "smoke rc=$?" | tee -a gpurun_out/$tag/smoke.log
@@ -16,11 +17,11 @@ if [ "$2" = "profile" ]; then
 fi
 # measured errors of every precision on the goldens + C2 batch, with this tree's forward-source fingerprint: the bench lines below quote it
 python tools/prec_errors.py --out gpurun_out/$tag/prec_errors.log > gpurun_out/$tag/prec.out 2>&1; cp gpurun_out/$tag/prec_errors.log profiles/${tag}_prec_errors.log; grep golden_max gpurun_out/$tag/prec.out
-python bench.py > gpurun_out/$tag/bench_c2.json 2> gpurun_out/$tag/bench_c2.err; echo "c2 rc=$?"
-python bench.py --atoms 512 --batch 32 --steps 5 --warmup 2 --reps 3 --no-cpu-baseline > gpurun_out/$tag/bench_c3.json 2> gpurun_out/$tag/bench_c3.err; echo "c3 rc=$?"
+python bench.py --full > "$o/bench_c2.json" 2> "$o/bench_c2.err"; echo "c2 rc=$?"
+python bench.py --full --atoms 512 --batch 32 --steps 5 --warmup 2 --reps 3 --no-cpu-baseline > "$o/bench_c3.json" 2> "$o/bench_c3.err"; echo "c3 rc=$?"
 python bench.py --mode train --steps 10 --warmup 3 > gpurun_out/$tag/bench_train.json 2> gpurun_out/$tag/bench_train.err; echo "train rc=$?"
-BENCH_DEVICE=0 BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 5 --warmup 2 --reps 2 --train-steps 3 > gpurun_out/$tag/bench_2rank_gloo.json 2> gpurun_out/$tag/bench_2rank_gloo.err; echo "2rank rc=$?"
-tail -c 600 gpurun_out/$tag/bench_c2.json; echo
-tail -c 400 gpurun_out/$tag/bench_c3.json; echo
+BENCH_DEVICE=0 BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 5 --warmup 2 --reps 2 --train-steps 3 > "$o/bench_2rank_gloo.json" 2> "$o/bench_2rank_gloo.err"; echo "2rank rc=$?"
+tail -c 600 "$o/bench_c2.json"; echo
+tail -c 400 "$o/bench_c3.json"; echo
 tail -c 400 gpurun_out/$tag/bench_train.json; echo
-tail -c 400 gpurun_out/$tag/bench_2rank_gloo.json; tail -5 gpurun_out/$tag/bench_2rank_gloo.err
+tail -c 400 "$o/bench_2rank_gloo.json"; tail -5 "$o/bench_2rank_gloo.err"

@@ -8,7 +8,7 @@ tail -3 $o/tests.log
 for r in 1 2; do
 for cfg in "0 0" "2048 0" "2048 6144" "2048 24000"; do
   set -- $cfg
-  EGNN_SMALL_EDGES=$1 EGNN_SMALL64_EDGES=$2 python bench.py --steps 5 --warmup 2 --reps 1 --no-cpu-baseline --no-train-leg --no-slab-leg --no-precision-legs 2>/dev/null | python -c "
+  EGNN_SMALL_EDGES=$1 EGNN_SMALL64_EDGES=$2 python bench.py --full --steps 5 --warmup 2 --reps 1 --no-cpu-baseline --no-train-leg --no-slab-leg --no-precision-legs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('small32<=$1 small64<=$2', [(round(r['eager_ms_per_step'],4), round(r['graph_replay_ms_per_step'],4)) for r in d['latency']['rows']], [r['nonfinite_graphs'] for r in d['latency']['rows']])" | tee -a $o/lat_ab.log
 done

@@ -62,18 +62,24 @@ struct LayerPack {
   void* w2x_f16s16 = nullptr;  // mlp_x.2 scaled, v_mfma_f32_16x16x32_f16 B fragments
   void* w2m_f16s = nullptr;    // mlp_m.2 scaled, v_mfma_f32_32x32x16_f16 B fragments
   void* w2m_f16s16 = nullptr;  // mlp_m.2 scaled, v_mfma_f32_16x16x32_f16 B fragments (edge_small.hip)
-  void* w1h_f16 = nullptr;     // mlp_h.0
   void* w2h_f16p = nullptr;    // mlp_h.2, k in accumulator-row order
   // split-operand node MLP (node_post_bf16_kernel<., f16x8, true>): mlp_h.0 head / remainder with K padded to its ring's two
   // turns, mlp_h.2 remainder (its head is w2h_f16p); null when the shape is outside that kernel
   void *w1h_f16k = nullptr, *w1h_f16k_lo = nullptr, *w2h_f16p_lo = nullptr;
-  // precision f16c8 (edge_f16c8.hip): e4m3 fragments [N/16][K/64][2][64][16 B] of the heads and remainders of the fp16 streams
-  // above (hi | lo K blocks interleaved), and the e8m0 bytes of their block scales {x: hi, lo, m: hi, lo}
-  void *w2x_c8 = nullptr, *w2m_c8 = nullptr;
-  int* c8_exp = nullptr;
-  // the same on 32x32 matrix tiles (edge_f16c8w.hip): mlp_x.2 as v_mfma_f32_32x32x16_f16 B fragments (mlp_m.2: w2m_f16s above) and
-  // e4m3 fragments [N/32][K/32][2][64][16 B]
+  // precision f16c8 (edge_f16c8w.hip): mlp_x.2 as v_mfma_f32_32x32x16_f16 B fragments (mlp_m.2: w2m_f16s above), e4m3 fragments
+  // [N/32][K/32][2][64][16 B] of the heads and remainders of the fp16 streams, and the e8m0 bytes of their block scales
+  // {x: hi, lo, m: hi, lo} (+ [4..5]: the packs' max |w| scratch words)
   void *w2x_f16s = nullptr, *w2x_c8w = nullptr, *w2m_c8w = nullptr;
+  int* c8_exp = nullptr;
+};
+
+// edge path of a layer's forward pass, chosen by launch_layer_begin (egnn_forward.hip: plan_edge) and read by launch_layer_end
+enum class EdgePath {
+  kGeneric,   // the 64-edge-tile kernel edge_kernel<PREC> (fp32, and every shape / switch the tiled kernels do not take)
+  kBf16,      // precision bf16: edge_x_m16.hip or edge_bf16_v3.hip + edge_bf16_v4.hip (fp16 table), or edge_small.hip
+  kBf16x3,    // precision bf16x3: edge_bf16x3.hip
+  kF16,       // precision fp16: the bf16 path's kernels on fp16 operands
+  kF16c8,     // precision f16c8: edge_f16c8w.hip
 };
 
 constexpr int kGraphSteps = 8;   // reverse steps captured per hipGraph
@@ -118,7 +124,8 @@ struct egnn_ctx {
   float* part_x = nullptr;   // [tiles][2][4]
   float* node_d2 = nullptr;  // [N]
   float* gscale = nullptr;   // [B] sum of d^2 per graph (G^2); node_post applies 1/(G+1)
-  int last_R = 64, last_nsplit_x = 1, last_path = 1;   // edge path chosen by the last launch_layer_begin
+  int last_R = 64, last_nsplit_x = 1;
+  egnn::EdgePath last_path = egnn::EdgePath::kGeneric;   // edge path chosen by the last launch_layer_begin
   bool sq_from_agg = false;             // node_post takes the d^2 sums from the coordinate sums' component 3
   bool small_ok = false;                // the partial slots were sized for 32-edge tiles (E <= 65536): edge_small.hip may run
   // A layer's hidden-split node_post leaves its 8 partial h' in h_partial; inside a multi-layer call the NEXT layer's node_pre

@@ -97,7 +97,7 @@ EGNN_DIAG_FLAG(kNpNoMlp, true);
 #else
 EGNN_DIAG_FLAG(kNpNoMlp, false);
 #endif
-// f16c8 edge kernels (edge_f16c8.hip, tools/c8_ab.sh): without the correction MFMAs (and their operand reads), without the fp16
+// f16c8 edge kernels (edge_f16c8w.hip, tools/c8w_decomp.sh): without the correction MFMAs (and their operand reads), without the fp16
 // MFMAs, without the activation build's arithmetic (the LDS images keep their first contents), without the e4m3 conversions and
 // their LDS stores, without the epilogue
 #ifdef EGNN_EXP_C8_NOCORR

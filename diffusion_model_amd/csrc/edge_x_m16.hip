@@ -237,7 +237,7 @@ __global__ __launch_bounds__(kT, 2) void edge_x_m16_kernel(const EdgeParams p) {
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
           acc[rb][cb] = mfma16(a[u % 3], bq[s][cb], acc[rb][cb]);
-#ifdef XM16_PIN   // (A/B, tools/c8_ab2.sh: a scheduling barrier behind every group of MFMAs, as edge_f16c8.hip needs)
+#ifdef XM16_PIN   // (A/B, tools/c8_ab2.sh: a scheduling barrier behind every group of MFMAs, as edge_f16c8w.hip has)
         __builtin_amdgcn_sched_barrier(0);
 #endif
         // refill in place for use u + 3 (the MFMAs above have read the registers at issue): row block (u + 3) & 7 of k-step (u + 3) >> 3

@@ -1027,7 +1027,6 @@ int init_kernel_attributes() {
   if ((rc = init_edge_dgrad_graph_attributes())) return rc;
   if ((rc = init_edge_x_m16_attributes())) return rc;
   if ((rc = init_edge_bf16x3_attributes())) return rc;
-  if ((rc = init_edge_f16c8_attributes())) return rc;
   if ((rc = init_edge_f16c8w_attributes())) return rc;
   done = true;
   return EGNN_OK;
@@ -1089,7 +1088,7 @@ static void use_scaled_pack(egnn_ctx* c, int layer, EdgeParams& p, const float*&
   p.w2x = lp.w2x_bf16s; p.w2m = lp.w2m_bf16s;
   p.w2x16 = lp.w2x_bf16s16; p.w2m16 = lp.w2m_bf16s16;
   p.w2x_lo = lp.w2x_bf16s_lo; p.w2m_lo = lp.w2m_bf16s_lo;
-  p.w2x_c8 = lp.w2x_c8; p.w2m_c8 = lp.w2m_c8; p.c8_exp = lp.c8_exp;
+  p.w2x_c8 = lp.w2x_c8w; p.w2m_c8 = lp.w2m_c8w; p.c8_exp = lp.c8_exp;
 }
 // first-layer table of the v3 / v4 kernels (fp16, pre-scaled) for node features h
 static int launch_node_pre_f16(egnn_ctx* c, hipStream_t st, int layer, const float* h, const float* w1catT,
@@ -1201,6 +1200,74 @@ int backward_dgrad_graph(egnn_ctx* c, hipStream_t st, int layer, const float* x,
                                  gd2_part + (size_t)(c->WxP / 256) * n_edges, st);
 }
 
+// Edge path of a layer and its EdgeParams.  The 128-edge-tile kernels take the pre-scaled parameters (use_scaled_pack: w1catT /
+// b1cat then point at the scaled first layers), the generic kernel the plain ones:
+//   bf16    edge_x_m16.hip (hidden width 512 / 1024) or edge_bf16_v3.hip (256) + edge_bf16_v4.hip, fp16 table
+//   bf16x3  edge_bf16x3.hip (head / remainder operands, fp32 table)
+//   fp16    the bf16 path's kernels on fp16 operands (hidden width 512 / 1024)
+//   f16c8   edge_f16c8w.hip (fp16 heads + e4m3 corrections, fp32 table)
+// A precision whose tiled kernels do not take the shape runs the generic kernel: bf16 as bf16, the others as the exact fp32 path
+// (prec is set to EGNN_PREC_F32; their EdgeParams are the fp32 ones already).  EGNN_EDGE=1 forces the generic kernel (the one
+// switch kept: the fallback kernels' own parity test runs the reference widths on them).
+static EdgePath plan_edge(egnn_ctx* c, int layer, int& prec, const float* x, EdgeParams& p, const float*& w1catT,
+                          const float*& b1cat) {
+  static const int edge_sel = getenv("EGNN_EDGE") ? atoi(getenv("EGNN_EDGE")) : 4;
+  const LayerPack& lp = c->layers[layer];
+  fill_edge_params(c, layer, prec, x, p);
+  w1catT = lp.w1catT; b1cat = lp.b1cat;
+  EdgePath path = EdgePath::kGeneric;
+  if (edge_sel >= 4) {
+    EdgeParams q = p;
+    const float *w1c, *b1c;
+    use_scaled_pack(c, layer, q, w1c, b1c);
+    if (prec == EGNN_PREC_BF16) {
+      if (edge_bf16_v4_supported(p) && edge_bf16_v3_supported(p)) path = EdgePath::kBf16;
+    } else if (prec == EGNN_PREC_BF16X3) {
+      if (edge_bf16x3_supported(q)) path = EdgePath::kBf16x3;
+    } else if (prec == EGNN_PREC_F16C8) {
+      q.w2x = lp.w2x_f16s; q.w2m = lp.w2m_f16s;
+      if (!c->save_s1x && edge_f16c8w_supported(q)) path = EdgePath::kF16c8;
+    } else if (prec == EGNN_PREC_F16) {
+      if (!c->save_s1x && edge_bf16_v4_supported(q) && edge_x_m16_supported(q)) path = EdgePath::kF16;
+    }
+  }
+  if (path == EdgePath::kGeneric && prec != EGNN_PREC_BF16) prec = EGNN_PREC_F32;
+  if (path != EdgePath::kGeneric) use_scaled_pack(c, layer, p, w1catT, b1cat);
+  return path;
+}
+
+// fp32 first-layer table (exact: the generic path, and the fp32 table of bf16x3 / f16c8)
+static void launch_node_pre_f32(egnn_ctx* c, hipStream_t st, const float* h, const float* w1catT, const float* b1cat) {
+  const int N = c->N;
+  if (c->H <= 64) {
+    dim3 grid((N + kPre2Nodes - 1) / kPre2Nodes, (c->TC + kPre2Cols - 1) / kPre2Cols);
+    const size_t sm = (size_t)((c->H + 1) & ~1) * 33 * sizeof(float);
+    hipLaunchKernelGGL(node_pre_mfma_kernel<float>, grid, dim3(kThreads), sm, st, h, N, c->H, w1catT, b1cat, c->TC, c->table);
+  } else {
+    dim3 grid((N + kPreNodes - 1) / kPreNodes, (c->TC + kThreads - 1) / kThreads);
+    const size_t sm = (size_t)kPreNodes * c->H * sizeof(float);
+    hipLaunchKernelGGL(node_pre_kernel<float>, grid, dim3(kThreads), sm, st, h, N, c->H, w1catT, b1cat, c->TC, c->table);
+  }
+}
+
+// A layer's coordinate and message kernel: with `fork`, the message kernel goes to the caller's side stream between two events
+// (fork / join; under capture they become graph edges) and runs in the shadow of the coordinate kernel's last, partly filled
+// round (see fork_streams); else both in order on st
+template <class LaunchX, class LaunchM>
+static int launch_edge_pair(egnn_ctx* c, hipStream_t st, bool fork, LaunchX launch_x, LaunchM launch_m) {
+  if (!fork) {
+    const int rc = launch_x(st);
+    return rc ? rc : launch_m(st);
+  }
+  EGNN_HIP(hipEventRecord(c->ev_fork, st));
+  EGNN_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+  int rc = launch_x(st);
+  if (!rc) rc = launch_m(c->side);
+  EGNN_HIP(hipEventRecord(c->ev_join, c->side));
+  EGNN_HIP(hipStreamWaitEvent(st, c->ev_join, 0));
+  return rc;
+}
+
 // Stage 1 of a layer: node_pre, squared-distance sums and the fused edge pass.  gsum (c->gscale) then holds the
 // sum of d^2 over the edges THIS context received, per graph (or per call).
 int launch_layer_begin(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_scope, const float* h,
@@ -1208,191 +1275,95 @@ int launch_layer_begin(egnn_ctx* c, hipStream_t st, int layer, int prec, int nor
   const LayerPack& lp = c->layers[layer];
   if (!lp.packed) { set_error("layer %d has no packed parameters", layer); return EGNN_ESTATE; }
   const int N = c->N, E = c->E;
-  int R = edge_rows_per_tile(prec), nsplit_x = 1;
   const int per_graph = norm_scope == EGNN_NORM_GRAPH;
-
-  // choose the edge path first: the 128-edge-tile bf16 kernels consume the pre-scaled first-layer table
-  //   path 5  precision bf16x3: edge_bf16x3.hip (head / remainder operands, fp32 table)
-  //   path 4  precision bf16  : coordinate kernel edge_x_m16.hip (hidden width 512 / 1024) or edge_bf16_v3.hip (256) +
-  //                             message kernel edge_bf16_v4.hip (fp16 table)
-  //   path 1  every other shape, and fp32: the generic 64-edge-tile kernel edge_kernel<PREC> of this file
-  // EGNN_EDGE=1 forces path 1 (the one switch kept: the fallback kernels' own parity test runs the reference widths on them)
   EdgeParams p;
-  fill_edge_params(c, layer, prec, x, p);
-  static const int edge_sel = getenv("EGNN_EDGE") ? atoi(getenv("EGNN_EDGE")) : 4;
-  int path = 1;
-  if (prec == EGNN_PREC_BF16X3) {   // split-operand kernels where the 128-edge tiling applies, else the exact fp32 path
-    EdgeParams q = p;
-    const float *w1c, *b1c;
-    use_scaled_pack(c, layer, q, w1c, b1c);
-    if (edge_sel >= 4 && edge_bf16x3_supported(q)) path = 5;
-    else prec = EGNN_PREC_F32;
-    fill_edge_params(c, layer, prec, x, p);
-  }
-  if (prec == EGNN_PREC_F16C8) {   // fp16 heads + e4m3 corrections where the 128-edge tiling applies, else the exact fp32 path
-    EdgeParams q = p;
-    const float *w1c, *b1c;
-    use_scaled_pack(c, layer, q, w1c, b1c);
-    q.w2x16 = lp.w2x_f16s16; q.w2m16 = lp.w2m_f16s16;
-    if (edge_sel >= 4 && edge_f16c8_supported(q) && !c->save_s1x) path = 7;
-    else prec = EGNN_PREC_F32;
-    fill_edge_params(c, layer, prec, x, p);
-  }
-  if (prec == EGNN_PREC_F16) {   // fp16 operands on the bf16 path's kernels (hidden width 512 / 1024), else the exact fp32 path
-    EdgeParams q = p;
-    const float *w1c, *b1c;
-    use_scaled_pack(c, layer, q, w1c, b1c);
-    if (edge_sel >= 4 && edge_bf16_v4_supported(q) && edge_x_m16_supported(q) && !c->save_s1x) path = 6;
-    else { prec = EGNN_PREC_F32; fill_edge_params(c, layer, prec, x, p); }
-  }
-  if (prec == EGNN_PREC_BF16 && edge_sel >= 4 && edge_bf16_v4_supported(p) && edge_bf16_v3_supported(p)) path = 4;
-  if (c->save_s1x && path != 4) { set_error("egcl_forward_save needs the 128-edge-tile bf16 kernels"); return EGNN_EINVAL; }
-  const float* w1catT = lp.w1catT;
-  const float* b1cat = lp.b1cat;
-  if (path >= 4) use_scaled_pack(c, layer, p, w1catT, b1cat);
+  const float *w1catT, *b1cat;
+  const EdgePath path = plan_edge(c, layer, prec, x, p, w1catT, b1cat);
+  if (c->save_s1x && path != EdgePath::kBf16) { set_error("egcl_forward_save needs the 128-edge-tile bf16 kernels"); return EGNN_EINVAL; }
+  const bool tiled = path != EdgePath::kGeneric;            // the 128-edge-tile kernels sum d^2 per receiving node themselves
+  const bool half_table = path == EdgePath::kBf16 || path == EdgePath::kF16;   // fp16 table (launch_node_pre_f16)
 
   // a pending hidden-split finish (previous layer of a multi-layer call) is fused into the half-precision node_pre for H <= 48;
   // every other case runs the finish launch now
-  if (c->pend.active && !((path == 4 || path == 6) && c->H <= 48 && c->pend.h_out == h)) {
+  if (c->pend.active && !(half_table && c->H <= 48 && c->pend.h_out == h)) {
     int rc = launch_node_post_finish(N, c->H, c->pend.hs, c->h_partial, c->pend.b2h, c->pend.h_out, st);
     c->pend.active = false;
     if (rc) return rc;
   }
   prof_begin(c, st, 1);
-  {
-    if (path == 5 || path == 7) {   // bf16x3 / f16c8: exact fp32 table of the scaled first layers
-      dim3 grid((N + kPre2Nodes - 1) / kPre2Nodes, (c->TC + kPre2Cols - 1) / kPre2Cols);
-      const size_t sm = (size_t)((c->H + 1) & ~1) * 33 * sizeof(float);
-      if (c->H <= 64)
-        hipLaunchKernelGGL(node_pre_mfma_kernel<float>, grid, dim3(kThreads), sm, st, h, N, c->H, w1catT, b1cat, c->TC, c->table);
-      else
-        hipLaunchKernelGGL(node_pre_kernel<float>, dim3((N + kPreNodes - 1) / kPreNodes, (c->TC + kThreads - 1) / kThreads),
-                           dim3(kThreads), (size_t)kPreNodes * c->H * sizeof(float), st, h, N, c->H, w1catT, b1cat, c->TC, c->table);
-    } else if (path == 4 || path == 6) {   // half-precision table
-      int rc = launch_node_pre_f16(c, st, layer, h, w1catT, b1cat);
-      if (rc) return rc;
-    } else if (c->H <= 64) {
-      dim3 grid((N + kPre2Nodes - 1) / kPre2Nodes, (c->TC + kPre2Cols - 1) / kPre2Cols);
-      const size_t sm = (size_t)((c->H + 1) & ~1) * 33 * sizeof(float);
-      hipLaunchKernelGGL(node_pre_mfma_kernel<float>, grid, dim3(kThreads), sm, st, h, N, c->H, w1catT, b1cat, c->TC,
-                         c->table);
-    } else {
-      dim3 grid((N + kPreNodes - 1) / kPreNodes, (c->TC + kThreads - 1) / kThreads);
-      const size_t sm = (size_t)kPreNodes * c->H * sizeof(float);
-      hipLaunchKernelGGL(node_pre_kernel<float>, grid, dim3(kThreads), sm, st, h, N, c->H, w1catT, b1cat, c->TC,
-                         c->table);
-    }
-    if (path < 4) {   // the 128-edge-tile kernels sum d^2 per receiving node themselves
-      hipLaunchKernelGGL(node_d2_kernel, dim3((N + 255) / 256), dim3(256), 0, st, x, c->row_ptr, c->edge_src, N,
-                         c->node_d2);
-      hipLaunchKernelGGL(graph_sum_kernel, dim3(per_graph ? c->B : 1), dim3(kThreads), 0, st, c->node_d2,
-                         c->graph_ptr, N, per_graph, c->gscale);
-    }
+  if (half_table) {
+    int rc = launch_node_pre_f16(c, st, layer, h, w1catT, b1cat);
+    if (rc) return rc;
+  } else {
+    launch_node_pre_f32(c, st, h, w1catT, b1cat);
+  }
+  if (!tiled) {
+    hipLaunchKernelGGL(node_d2_kernel, dim3((N + 255) / 256), dim3(256), 0, st, x, c->row_ptr, c->edge_src, N, c->node_d2);
+    hipLaunchKernelGGL(graph_sum_kernel, dim3(per_graph ? c->B : 1), dim3(kThreads), 0, st, c->node_d2, c->graph_ptr, N, per_graph,
+                       c->gscale);
   }
   prof_end(c, st);
   EGNN_HIP(hipGetLastError());
 
+  int R = edge_rows_per_tile(prec), nsplit_x = 1;
   if (E > 0) {
-    const int tiles = (E + R - 1) / R;
-    const size_t smem = edge_smem_bytes(R, c->MP);
     prof_begin(c, st, 0);
+    // fork_candidate(): whether the message kernel fits the shadow of the coordinate kernel's last round (small-tile kernels:
+    // always fork when the caller gave a side stream)
+    const bool can_fork = !c->prof && st != nullptr && c->side != nullptr && c->ev_fork != nullptr;
+    const bool fork = can_fork && fork_candidate(E, p.WxP);
+    const int small = half_table && !c->save_s1x ? small_tiles(c, p) : 0;
     int rc;
-    if (path == 5) {
+    if (path == EdgePath::kBf16x3) {
       R = 128;
       nsplit_x = p.WxP / 256;
       rc = launch_edge_bf16x3(p, st);
-    } else if (path == 7) {   // precision f16c8 (edge_f16c8.hip): fp16 16-column streams + e4m3 correction streams
+    } else if (path == EdgePath::kF16c8) {   // fp16 32-column streams + e4m3 correction streams
       R = 128;
+      nsplit_x = p.WxP / 512;
       p.w2x16 = lp.w2x_f16s16; p.w2m16 = lp.w2m_f16s16;
-      // matrix tile shape: 32x32 (edge_f16c8w.hip) / 16x16 (edge_f16c8.hip); EGNN_C8_TILE = A/B switch
-      static const int c8_tile = getenv("EGNN_C8_TILE") ? atoi(getenv("EGNN_C8_TILE")) : 32;
-      bool wide = false;
-      if (c8_tile == 32) {
-        EdgeParams q = p;
-        q.w2x = lp.w2x_f16s; q.w2m = lp.w2m_f16s; q.w2x_c8 = lp.w2x_c8w; q.w2m_c8 = lp.w2m_c8w;
-        if (edge_f16c8w_supported(q)) { p = q; wide = true; }
-      }
-      nsplit_x = wide ? p.WxP / 512 : edge_f16c8_x_split(p.WxP);
-      const bool fork = !c->prof && st != nullptr && c->side != nullptr && c->ev_fork != nullptr && fork_candidate(E, p.WxP);
-      if (fork) {
-        EGNN_HIP(hipEventRecord(c->ev_fork, st));
-        EGNN_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        rc = wide ? launch_edge_f16c8w_x(p, st) : launch_edge_f16c8_x(p, st);
-        if (!rc) rc = wide ? launch_edge_f16c8w_m(p, c->side) : launch_edge_f16c8_m(p, c->side);
-        EGNN_HIP(hipEventRecord(c->ev_join, c->side));
-        EGNN_HIP(hipStreamWaitEvent(st, c->ev_join, 0));
-      } else {
-        rc = wide ? launch_edge_f16c8w_x(p, st) : launch_edge_f16c8_x(p, st);
-        if (!rc) rc = wide ? launch_edge_f16c8w_m(p, st) : launch_edge_f16c8_m(p, st);
-      }
-    } else if ((path == 6 || path == 4) && !c->save_s1x && small_tiles(c, p) != 0) {
-      // small graphs (the reference's per-call workload): 32-edge tiles, weight-stream-bound workgroups (edge_small.hip);
-      // coordinate and message kernel side by side when the caller gave a side stream
-      const bool f16 = path == 6;
-      R = small_tiles(c, p);
+      p.w2x = lp.w2x_f16s; p.w2m = lp.w2m_f16s;
+      rc = launch_edge_pair(c, st, fork, [&](hipStream_t s) { return launch_edge_f16c8w_x(p, s); },
+                            [&](hipStream_t s) { return launch_edge_f16c8w_m(p, s); });
+    } else if (small != 0) {
+      // small graphs (the reference's per-call workload): 32-edge tiles, weight-stream-bound workgroups (edge_small.hip)
+      const bool f16 = path == EdgePath::kF16;
+      R = small;
       nsplit_x = p.WxP / 512;
       if (f16) { p.w2x16 = lp.w2x_f16s16; p.w2m16 = lp.w2m_f16s16; }
-      const bool fork = !c->prof && st != nullptr && c->side != nullptr && c->ev_fork != nullptr;
-      if (fork) {
-        EGNN_HIP(hipEventRecord(c->ev_fork, st));
-        EGNN_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        rc = launch_edge_small_x(p, st, f16, R);
-        if (!rc) rc = launch_edge_small_m(p, c->side, f16, R);
-        EGNN_HIP(hipEventRecord(c->ev_join, c->side));
-        EGNN_HIP(hipStreamWaitEvent(st, c->ev_join, 0));
-      } else {
-        rc = launch_edge_small_x(p, st, f16, R);
-        if (!rc) rc = launch_edge_small_m(p, st, f16, R);
-      }
-    } else if (path == 6) {   // precision fp16: the path-4 kernels on fp16 operands (same tiles, same launch structure)
+      rc = launch_edge_pair(c, st, can_fork, [&](hipStream_t s) { return launch_edge_small_x(p, s, f16, R); },
+                            [&](hipStream_t s) { return launch_edge_small_m(p, s, f16, R); });
+    } else if (path == EdgePath::kF16) {   // the bf16 path's kernels on fp16 operands (same tiles, same launch structure)
       R = edge_v4_rows();
       nsplit_x = p.WxP / 512;
       p.w2x16 = lp.w2x_f16s16; p.w2m = lp.w2m_f16s;
-      const bool fork = !c->prof && st != nullptr && c->side != nullptr && c->ev_fork != nullptr && fork_candidate(E, p.WxP);
-      if (fork) {
-        EGNN_HIP(hipEventRecord(c->ev_fork, st));
-        EGNN_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        rc = launch_edge_x_m16_f16(p, st);
-        if (!rc) rc = launch_edge_f16_v4_m(p, c->side);
-        EGNN_HIP(hipEventRecord(c->ev_join, c->side));
-        EGNN_HIP(hipStreamWaitEvent(st, c->ev_join, 0));
-      } else {
-        rc = launch_edge_x_m16_f16(p, st);
-        if (!rc) rc = launch_edge_f16_v4_m(p, st);
-      }
-    } else if (path == 4) {
+      rc = launch_edge_pair(c, st, fork, [&](hipStream_t s) { return launch_edge_x_m16_f16(p, s); },
+                            [&](hipStream_t s) { return launch_edge_f16_v4_m(p, s); });
+    } else if (path == EdgePath::kBf16) {
       R = edge_v4_rows();
       const bool xm16 = edge_x_m16_supported(p);   // hidden width 512 / 1024: v_mfma_f32_16x16x32_bf16 (512 columns per workgroup)
       nsplit_x = xm16 ? p.WxP / 512 : 1;
-      // fork_candidate(): the message kernel goes to the caller's side stream between two events (fork / join; under capture
-      // they become graph edges) and runs in the shadow of the coordinate kernel's last, partly filled round
-      const bool fork = !c->prof && st != nullptr && c->side != nullptr && c->ev_fork != nullptr && fork_candidate(E, p.WxP);
-      auto launch_x = [&](hipStream_t s) { return xm16 ? launch_edge_x_m16(p, s) : launch_edge_bf16_v3_x(p, s); };
       if (c->save_s1x) {   // training forward (egcl_forward_save): the same kernels, which also store what the backward needs
         p.s1_out = c->save_s1x; p.g_a2_out = c->save_t2x; p.s_half_out = c->save_s;
         rc = xm16 ? launch_edge_x_m16_save(p, st) : launch_edge_bf16_v3_x_save(p, st);
         p.s1_out = c->save_s1m; p.g_a2_out = c->save_t2m; p.s_half_out = nullptr;
         if (!rc) rc = launch_edge_bf16_v4_m_save(p, st);
-      } else if (fork) {
-        EGNN_HIP(hipEventRecord(c->ev_fork, st));
-        EGNN_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        rc = launch_x(st);
-        if (!rc) rc = launch_edge_bf16_v4_m(p, c->side);
-        EGNN_HIP(hipEventRecord(c->ev_join, c->side));
-        EGNN_HIP(hipStreamWaitEvent(st, c->ev_join, 0));
       } else {
-        rc = launch_x(st);
-        if (!rc) rc = launch_edge_bf16_v4_m(p, st);
+        rc = launch_edge_pair(c, st, fork, [&](hipStream_t s) { return xm16 ? launch_edge_x_m16(p, s) : launch_edge_bf16_v3_x(p, s); },
+                              [&](hipStream_t s) { return launch_edge_bf16_v4_m(p, s); });
       }
-    } else if (prec == EGNN_PREC_BF16) rc = launch_edge<EGNN_PREC_BF16, 2>(p, tiles, smem, st);
-    else rc = launch_edge<EGNN_PREC_F32, 2>(p, tiles, smem, st);
+    } else {
+      const int tiles = (E + R - 1) / R;
+      const size_t smem = edge_smem_bytes(R, c->MP);
+      rc = prec == EGNN_PREC_BF16 ? launch_edge<EGNN_PREC_BF16, 2>(p, tiles, smem, st) : launch_edge<EGNN_PREC_F32, 2>(p, tiles, smem, st);
+    }
     prof_end(c, st);
     if (rc) return rc;
   }
 
   c->last_R = R; c->last_nsplit_x = nsplit_x; c->last_path = path;
   c->sq_from_agg = false;
-  if (path >= 4) {
+  if (tiled) {
     if (E == 0) {
       EGNN_HIP(hipMemsetAsync(c->gscale, 0, sizeof(float) * (per_graph ? c->B : 1), st));
     } else if (!per_graph || need_gscale) {
@@ -1427,24 +1398,17 @@ int launch_layer_end(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_
     q.w1h_bf16 = lp.w1h_bf16; q.w2h_bf16p = lp.w2h_bf16p; q.K1Q = c->K1Q;
     q.h_partial = c->h_partial;
     prof_begin(c, st, 1);
-    // node MLP of precision fp16 (and of bf16x3 on the 128-edge-tile path): split-operand fp16 products (22 significant bits,
-    // node_bf16.hip) where the shape allows, else the exact fp32 kernel.  EGNN_F16_NODE (error-budget experiments only):
-    // 0 = exact fp32 node MLP, 1 = plain fp16 operands.
-    static const int f16_node = getenv("EGNN_F16_NODE") ? atoi(getenv("EGNN_F16_NODE")) : 2;
+    // node MLP of precisions fp16, bf16x3 and f16c8 on their 128-edge-tile paths: split-operand fp16 products (22 significant
+    // bits, node_bf16.hip) where the shape allows, else the exact fp32 kernel
     PostParams qs = q;
     qs.w1h_bf16 = lp.w1h_f16k; qs.w2h_bf16p = lp.w2h_f16p; qs.w1h_lo = lp.w1h_f16k_lo; qs.w2h_lo = lp.w2h_f16p_lo;
-    const bool half_path = (prec == EGNN_PREC_F16 && c->last_path == 6) || (prec == EGNN_PREC_BF16X3 && c->last_path == 5) ||
-                           (prec == EGNN_PREC_F16C8 && c->last_path == 7);
+    const bool split_path = c->last_path == EdgePath::kF16 || c->last_path == EdgePath::kBf16x3 || c->last_path == EdgePath::kF16c8;
     int hs_used = 1;
-    if (half_path && f16_node == 2 && node_post_split_supported(qs)) {
-      int rc = launch_node_post_bf16(qs, st, true, true, defer_finish, &hs_used);
-      if (rc) return rc;
-    } else if (prec == EGNN_PREC_F16 && c->last_path == 6 && f16_node == 1 && node_post_bf16_supported(q)) {
-      q.w1h_bf16 = lp.w1h_f16; q.w2h_bf16p = lp.w2h_f16p;
-      int rc = launch_node_post_bf16(q, st, true);
+    if (split_path && node_post_split_supported(qs)) {
+      int rc = launch_node_post_bf16(qs, st, true, defer_finish, &hs_used);
       if (rc) return rc;
     } else if (prec == EGNN_PREC_BF16 && node_post_bf16_supported(q)) {
-      int rc = launch_node_post_bf16(q, st, false, false, defer_finish, &hs_used);
+      int rc = launch_node_post_bf16(q, st, false, defer_finish, &hs_used);
       if (rc) return rc;
     } else {
       if (q.sq_from_agg) {   // the fp32 node kernel reads gscale
@@ -1468,8 +1432,6 @@ int launch_layer_end(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_
 int launch_layer(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_scope, const float* h,
                  const float* x, float* h_out, float* x_out, bool need_gscale, bool defer_finish) {
   if (layer == 0) c->pend.active = false;   // (a call that failed half-way leaves nothing behind)
-  static const bool defer_ok = !(getenv("EGNN_DEFER_FINISH") && atoi(getenv("EGNN_DEFER_FINISH")) == 0);   // A/B switch
-  defer_finish = defer_finish && defer_ok;
   int rc = launch_layer_begin(c, st, layer, prec, norm_scope, h, x, need_gscale);
   if (rc) return rc;
   return launch_layer_end(c, st, layer, prec, norm_scope, h, x, h_out, x_out, defer_finish);
@@ -1506,8 +1468,8 @@ static void free_layer(LayerPack& lp) {
   void* ptrs[] = {lp.w1catT, lp.b1cat, lp.wdx, lp.wdm, lp.w2x_f32, lp.w2x_bf16, lp.b2x, lp.w3x, lp.w2m_f32,
                   lp.w2m_bf16, lp.b2m, lp.wa, lp.scal, lp.w1h_f32, lp.b1h, lp.w2h_f32, lp.b2h, lp.sc, lp.w2x_bf16s, lp.w2m_bf16s, lp.w1h_bf16, lp.w2h_bf16p,
                   lp.w2xT_bf16, lp.w2mT_bf16, lp.w1hl_bf16, lp.w2x_bf16s16, lp.w2x_bf16s_lo, lp.w2m_bf16s_lo,
-                  lp.w2x_f16s16, lp.w2m_f16s, lp.w1h_f16, lp.w2h_f16p, lp.w1h_f16k, lp.w1h_f16k_lo, lp.w2h_f16p_lo,
-                  lp.w2m_bf16s16, lp.w2m_f16s16, lp.w2x_c8, lp.w2m_c8, lp.c8_exp, lp.w2x_f16s, lp.w2x_c8w, lp.w2m_c8w};
+                  lp.w2x_f16s16, lp.w2m_f16s, lp.w2h_f16p, lp.w1h_f16k, lp.w1h_f16k_lo, lp.w2h_f16p_lo,
+                  lp.w2m_bf16s16, lp.w2m_f16s16, lp.c8_exp, lp.w2x_f16s, lp.w2x_c8w, lp.w2m_c8w};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   lp = LayerPack();
@@ -1619,8 +1581,6 @@ int egnn_pack_layer(egnn_ctx* c, void* stream, int l, const float* m0_w, const f
     lp.w2x_f16s16 = tmp; tmp = nullptr;
     if ((rc = dev_alloc(&tmp, (size_t)MP * WmP))) return rc;
     lp.w2m_f16s = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)WhP * c->K1Q))) return rc;
-    lp.w1h_f16 = tmp; tmp = nullptr;
     if ((rc = dev_alloc(&tmp, (size_t)HP * WhP))) return rc;
     lp.w2h_f16p = tmp; tmp = nullptr;
     if (HP <= 64 && H + MP > node_post_split_k() / 2 && H + MP <= node_post_split_k()) {   // shapes of the split-operand node MLP
@@ -1631,12 +1591,9 @@ int egnn_pack_layer(egnn_ctx* c, void* stream, int l, const float* m0_w, const f
       if ((rc = dev_alloc(&tmp, (size_t)HP * WhP))) return rc;
       lp.w2h_f16p_lo = tmp;
     }
-    // precision f16c8: e4m3 fragments of heads + remainders (2 bytes per weight) and the block-scale exponents
+    // precision f16c8: mlp_x.2 as 32-column fp16 fragments, e4m3 fragments of heads + remainders (2 bytes per weight) and the
+    // block-scale exponents
     tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)WxP * WxP))) return rc;
-    lp.w2x_c8 = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)MP * WmP))) return rc;
-    lp.w2m_c8 = tmp; tmp = nullptr;
     if ((rc = dev_alloc(&tmp, (size_t)WxP * WxP))) return rc;
     lp.w2x_f16s = tmp; tmp = nullptr;
     if ((rc = dev_alloc(&tmp, (size_t)WxP * WxP))) return rc;
@@ -1683,7 +1640,6 @@ int egnn_pack_layer(egnn_ctx* c, void* stream, int l, const float* m0_w, const f
     // precision fp16: the same streams as fp16 fragments, times 2^8 (kernels.h "MFMA operand type")
     hipLaunchKernelGGL(pack_frags_bf16_n16<_Float16>, g, b, 0, st, x2_w, Wx, Wx, Wx, WxP, WxP, reinterpret_cast<_Float16*>(lp.w2x_f16s16), s2 * kF16WScale);
     hipLaunchKernelGGL(pack_frags_bf16<_Float16>, g, b, 0, st, m2_w, M, Wm, Wm, MP, WmP, reinterpret_cast<_Float16*>(lp.w2m_f16s), s2 * kF16WScale);
-    hipLaunchKernelGGL(pack_frags_bf16<_Float16>, g, b, 0, st, h0_w, Wh, H + M, H + M, WhP, c->K1Q, reinterpret_cast<_Float16*>(lp.w1h_f16), kF16WScale);
     hipLaunchKernelGGL(pack_frags_bf16_accperm<_Float16>, g, b, 0, st, h2_w, H, Wh, Wh, HP, WhP, reinterpret_cast<_Float16*>(lp.w2h_f16p), kF16WScale);
     if (lp.w1h_f16k) {   // split-operand node MLP: heads + remainders, mlp_h.0 with K padded to the ring's two turns
       const int KS = node_post_split_k();
@@ -1691,13 +1647,11 @@ int egnn_pack_layer(egnn_ctx* c, void* stream, int l, const float* m0_w, const f
       hipLaunchKernelGGL((pack_frags_bf16<_Float16, true>), g, b, 0, st, h0_w, Wh, H + M, H + M, WhP, KS, reinterpret_cast<_Float16*>(lp.w1h_f16k_lo), kF16WScale);
       hipLaunchKernelGGL((pack_frags_bf16_accperm<_Float16, true>), g, b, 0, st, h2_w, H, Wh, Wh, HP, WhP, reinterpret_cast<_Float16*>(lp.w2h_f16p_lo), kF16WScale);
     }
-    // precision f16c8: the same scaled weights as e4m3 head / remainder fragments for the block-scaled correction product
-    if ((rc = pack_c8_stream(x2_w, Wx, Wx, Wx, WxP, WxP, lp.w2x_c8, s2 * kF16WScale, lp.c8_exp, reinterpret_cast<unsigned*>(lp.c8_exp + 4), st))) return rc;
-    if ((rc = pack_c8_stream(m2_w, M, Wm, Wm, MP, WmP, lp.w2m_c8, s2 * kF16WScale, lp.c8_exp + 2, reinterpret_cast<unsigned*>(lp.c8_exp + 5), st))) return rc;
-    // ... and for the 32x32 tiles of edge_f16c8w.hip (same scale exponents)
+    // precision f16c8 (edge_f16c8w.hip): the same scaled weights as 32-column fp16 fragments (mlp_m.2: w2m_f16s) and as e4m3
+    // head / remainder fragments for the block-scaled correction product
     hipLaunchKernelGGL(pack_frags_bf16<_Float16>, g, b, 0, st, x2_w, Wx, Wx, Wx, WxP, WxP, reinterpret_cast<_Float16*>(lp.w2x_f16s), s2 * kF16WScale);
-    if ((rc = pack_c8w_stream(x2_w, Wx, Wx, Wx, WxP, WxP, lp.w2x_c8w, s2 * kF16WScale, lp.c8_exp, st))) return rc;
-    if ((rc = pack_c8w_stream(m2_w, M, Wm, Wm, MP, WmP, lp.w2m_c8w, s2 * kF16WScale, lp.c8_exp + 2, st))) return rc;
+    if ((rc = pack_c8w_stream(x2_w, Wx, Wx, Wx, WxP, WxP, lp.w2x_c8w, s2 * kF16WScale, lp.c8_exp, reinterpret_cast<unsigned*>(lp.c8_exp + 4), st))) return rc;
+    if ((rc = pack_c8w_stream(m2_w, M, Wm, Wm, MP, WmP, lp.w2m_c8w, s2 * kF16WScale, lp.c8_exp + 2, reinterpret_cast<unsigned*>(lp.c8_exp + 5), st))) return rc;
     hipLaunchKernelGGL(pack_frags_bf16_lo, g, b, 0, st, x2_w, Wx, Wx, Wx, WxP, WxP, reinterpret_cast<__bf16*>(lp.w2x_bf16s_lo), s2);
     hipLaunchKernelGGL(pack_frags_bf16_lo, g, b, 0, st, m2_w, M, Wm, Wm, MP, WmP, reinterpret_cast<__bf16*>(lp.w2m_bf16s_lo), s2);
     hipLaunchKernelGGL(pack_frags_bf16<__bf16>, g, b, 0, st, h0_w, Wh, H + M, H + M, WhP, c->K1Q, reinterpret_cast<__bf16*>(lp.w1h_bf16), 1.0f);

@@ -43,7 +43,7 @@ struct EdgeParams {
   const void *w2x_lo, *w2m_lo;   // bf16 remainders W - bf16(W) of the scaled second-layer weights, same fragment layout (bf16x3)
   const void* w2x16;   // mlp_x.2 as 16x16x32 B fragments (edge_x_m16.hip), scaled; null when not packed
   const void* w2m16;   // mlp_m.2 as 16x16x32 B fragments (edge_small.hip), scaled; null when not packed
-  const void *w2x_c8, *w2m_c8;   // precision f16c8: e4m3 fragments of the correction product (edge_f16c8.hip: pack_frags_c8)
+  const void *w2x_c8, *w2m_c8;   // precision f16c8: e4m3 fragments of the correction product (edge_f16c8w.hip: pack_frags_c8w)
   const int* c8_exp;             // device int[4]: e8m0 bytes of the weight block scales {x: hi, lo, m: hi, lo}
   float *agg_m, *agg_x, *part_m, *part_x;
   size_t agg_x_stride, part_x_stride;  // elements between the column-split copies of agg_x / part_x
@@ -310,8 +310,7 @@ struct PostParams {
   float* h_partial;   // [8][N][H] scratch of the hidden-split form (small N), or null
 };
 // hs_out: the hidden split that was launched (1 = none); defer_finish: leave the partial h' of a split launch to the caller
-int launch_node_post_bf16(const PostParams& q, hipStream_t st, bool f16 = false, bool split = false, bool defer_finish = false,
-                          int* hs_out = nullptr);
+int launch_node_post_bf16(const PostParams& q, hipStream_t st, bool split = false, bool defer_finish = false, int* hs_out = nullptr);
 int launch_node_post_finish(int N, int H, int hs, const float* partial, const float* b2h, float* h_out, hipStream_t st);
 bool node_post_split_supported(const PostParams& q);   // head + remainder fp16 operands, three MFMAs per product (node_bf16.hip)
 int node_post_split_k();
@@ -343,20 +342,14 @@ bool edge_small_supported(const EdgeParams& p);
 int launch_edge_bf16x3(const EdgeParams& p, hipStream_t st);    // precision 'bf16x3': head / remainder split operands
 bool edge_bf16x3_supported(const EdgeParams& p);
 int init_edge_bf16x3_attributes();
-// precision 'f16c8': fp16 main product + block-scaled e4m3 correction (edge_f16c8.hip); p.w2x16 / p.w2m16 = the fp16 16-column streams
-int launch_edge_f16c8_x(const EdgeParams& p, hipStream_t st);
-int launch_edge_f16c8_m(const EdgeParams& p, hipStream_t st);
-bool edge_f16c8_supported(const EdgeParams& p);
-int edge_f16c8_x_split(int WxP);
-int init_edge_f16c8_attributes();
-// the same precision on 32x32 matrix tiles (edge_f16c8w.hip); p.w2x / p.w2m = the fp16 32-column streams, p.w2x_c8 / p.w2m_c8 =
-// the e4m3 streams of pack_c8w_stream (scale exponents: those pack_c8_stream wrote)
+// precision 'f16c8': fp16 main product + block-scaled e4m3 correction on 32x32 matrix tiles (edge_f16c8w.hip); p.w2x / p.w2m = the
+// fp16 32-column streams, p.w2x_c8 / p.w2m_c8 = the e4m3 streams of pack_c8w_stream
 int launch_edge_f16c8w_x(const EdgeParams& p, hipStream_t st);
 int launch_edge_f16c8w_m(const EdgeParams& p, hipStream_t st);
 bool edge_f16c8w_supported(const EdgeParams& p);
 int init_edge_f16c8w_attributes();
-int pack_c8w_stream(const float* W, int Nout, int K, int ldw, int NP, int KP, void* out, float scale, const int* exps, hipStream_t st);
-int pack_c8_stream(const float* W, int Nout, int K, int ldw, int NP, int KP, void* out, float scale, int* exps, unsigned* maxbits,
-                   hipStream_t st);
+// exps: int[2] (e8m0 bytes of the block scales, written here); maxbits: one scratch word
+int pack_c8w_stream(const float* W, int Nout, int K, int ldw, int NP, int KP, void* out, float scale, int* exps, unsigned* maxbits,
+                    hipStream_t st);
 
 }  // namespace egnn

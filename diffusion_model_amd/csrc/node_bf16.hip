@@ -30,9 +30,9 @@ __host__ __device__ inline size_t nb_smem_bytes(int K1Q, int OB, bool split = fa
 // with a single H <= 256 instantiation the kernel took 464 registers per lane = ONE workgroup per CU, and a layer's 512
 // workgroups ran as two serial rounds of a latency-bound chain (88-98 us); at OBT = 2 (H <= 64, 224 VGPRs) two workgroups
 // share a CU: 49 us.
-// V8 = the MFMA operand type: bf16x8, or f16x8 for precision fp16 (p.w1h_bf16 / p.w2h_bf16p then point at the fp16 fragment
-// streams, packed x 2^8: both accumulators are divided by it where the biases are added).
-// SPLIT = true (fp32-grade node MLP on the half-precision matrix cores; used by precision fp16 and bf16x3): every operand of
+// V8 = the MFMA operand type: bf16x8, or f16x8 with SPLIT (p.w1h_bf16 / p.w2h_bf16p then point at the fp16 fragment streams,
+// packed x 2^8: both accumulators are divided by it where the biases are added).
+// SPLIT = true (fp32-grade node MLP on the half-precision matrix cores; used by precisions fp16, bf16x3 and f16c8): every operand of
 // both products is a head + remainder pair (X = X_hi + X_lo, W = W_hi + W_lo, hidden = h_hi + h_lo; with fp16 pairs 22
 // significant bits) and each product is three MFMAs, small terms first: lo x hi + hi x lo + hi x hi.  The node MLP is the
 // largest single rounding-error source of the fp16 path (tools/rounding_budget.py: 4.5e-4 of 5.3e-4 on h', 6.2e-4 of 8.3e-4
@@ -413,8 +413,6 @@ __global__ void node_post_finish_kernel(int N, int H, int hsplit, const float* _
 int init_node_bf16_attributes() {
   const void* fns[] = {reinterpret_cast<const void*>(&node_post_bf16_kernel<2>),
                        reinterpret_cast<const void*>(&node_post_bf16_kernel<kPostMaxOB>),
-                       reinterpret_cast<const void*>(&node_post_bf16_kernel<2, f16x8>),
-                       reinterpret_cast<const void*>(&node_post_bf16_kernel<kPostMaxOB, f16x8>),
                        reinterpret_cast<const void*>(&node_post_bf16_kernel<2, f16x8, true>),
                        reinterpret_cast<const void*>(&node_post_bf16_kernel<2, bf16x8, false, true>),
                        reinterpret_cast<const void*>(&node_post_bf16_kernel<2, f16x8, true, true>)};
@@ -434,14 +432,14 @@ bool node_post_split_supported(const PostParams& q) {
 }
 int node_post_split_k() { return kSplitK; }
 
-// f16: q.w1h_bf16 / q.w2h_bf16p are the fp16 fragment streams (precision fp16); split: + q.w1h_lo / q.w2h_lo (K = kSplitK)
 int launch_node_post_finish(int N, int H, int hs, const float* partial, const float* b2h, float* h_out, hipStream_t st) {
   hipLaunchKernelGGL(node_post_finish_kernel, dim3((N * H + 255) / 256), dim3(256), 0, st, N, H, hs, partial, b2h, h_out);
   EGNN_HIP(hipGetLastError());
   return EGNN_OK;
 }
 
-int launch_node_post_bf16(const PostParams& q, hipStream_t st, bool f16, bool split, bool defer_finish, int* hs_out) {
+// split: q.w1h_bf16 / q.w2h_bf16p are the fp16 head streams, q.w1h_lo / q.w2h_lo the remainders (K = kSplitK)
+int launch_node_post_bf16(const PostParams& q, hipStream_t st, bool split, bool defer_finish, int* hs_out) {
   const int tiles = (q.N + kNodes - 1) / kNodes;
   // Few node tiles (small graphs): a layer would wait for ONE workgroup's serial chain over all hidden blocks (40 us).
   // Split the hidden units over `hs` workgroups per tile (partial h' to scratch) and add them up in a second tiny launch:
@@ -456,11 +454,8 @@ int launch_node_post_bf16(const PostParams& q, hipStream_t st, bool f16, bool sp
   if (split) {
     if (hsk) hipLaunchKernelGGL((node_post_bf16_kernel<2, f16x8, true, true>), grid, dim3(kThreadsN), sm, st, q);
     else hipLaunchKernelGGL((node_post_bf16_kernel<2, f16x8, true>), grid, dim3(kThreadsN), sm, st, q);
-  } else if (hsk && !f16 && q.HP <= 64) {
+  } else if (hsk && q.HP <= 64) {
     hipLaunchKernelGGL((node_post_bf16_kernel<2, bf16x8, false, true>), grid, dim3(kThreadsN), sm, st, q);
-  } else if (f16) {
-    if (q.HP <= 64) hipLaunchKernelGGL((node_post_bf16_kernel<2, f16x8>), grid, dim3(kThreadsN), sm, st, q);
-    else hipLaunchKernelGGL((node_post_bf16_kernel<kPostMaxOB, f16x8>), grid, dim3(kThreadsN), sm, st, q);
   } else if (q.HP <= 64) hipLaunchKernelGGL(node_post_bf16_kernel<2>, grid, dim3(kThreadsN), sm, st, q);
   else hipLaunchKernelGGL(node_post_bf16_kernel<kPostMaxOB>, grid, dim3(kThreadsN), sm, st, q);
   if (hs_out) *hs_out = hs;

@@ -49,9 +49,9 @@ enum { EGNN_PREC_F32 = 0,   /* v_mfma_f32_32x32x2_f32: exact fp32 (parity mode) 
                                * rate, 11 significant bits instead of 8; overflow saturates at +-65504); inference only
                                * (egcl_forward_save stays bf16).  Hidden widths other than 512 / 1024 run as F32. */
        EGNN_PREC_F16C8 = 4 };/* fp32-grade accuracy for TWO bf16-equivalents of matrix work: fp16 heads on
-                               * v_mfma_f32_16x16x32_f16 + both remainder products on ONE block-scaled e4m3 instruction
-                               * (v_mfma_scale_f32_16x16x128_f8f6f4, twice the f16 rate) with fixed power-of-two block scales;
-                               * fp32 table, heads and split-operand node MLP as BF16X3 (csrc/edge_f16c8.hip); inference
+                               * v_mfma_f32_32x32x16_f16 + both remainder products on ONE block-scaled e4m3 instruction
+                               * (v_mfma_scale_f32_32x32x64_f8f6f4, twice the f16 rate) with fixed power-of-two block scales;
+                               * fp32 table, heads and split-operand node MLP as BF16X3 (csrc/edge_f16c8w.hip); inference
                                * only.  Hidden widths other than 512 / 1024 run as F32. */
 
 /* scope of the coordinate normaliser ||X_i - X_j||_F of EquivariantGraphNeuralNetwork.py:64 */

@@ -1,8 +1,8 @@
 #!/bin/bash
 # f16c8 edge kernels: where the time goes -- timing-only builds (wrong results by construction) against the product library,
 # one box, one visit: rocprofv3 kernel-trace averages of the coordinate (X) and message (M) kernel per variant.
-# usage (GPU box): bash tools/c8_ab.sh   (the exp_c8_*.so were built in the container: tools/c8_build.sh)
-cd /tmp && export TMPDIR=/tmp EGNN_C8_TILE=${EGNN_C8_TILE:-32}
+# usage (GPU box): bash tools/c8w_decomp.sh   (the exp_c8_*.so were built in the container: tools/c8_build.sh)
+cd /tmp && export TMPDIR=/tmp
 run() {   # name lib EGNN_DEBUG
   if [ "$2" = "base" ]; then unset EGNN_LIB; else export EGNN_LIB=$GRAFT_REPO_ROOT/diffusion_model_amd/exp_$2.so; fi
   rm -rf /tmp/pp; EGNN_DEBUG=$3 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -- python3 $GRAFT_REPO_ROOT/bench.py --precision f16c8 --steps 5 --warmup 2 --reps 1 --no-cpu-baseline --no-train-leg --no-slab-leg --no-latency-leg --no-precision-legs > /dev/null 2>&1

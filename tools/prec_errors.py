@@ -146,7 +146,7 @@ def main():
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     precisions = a.precisions.split(",")
     with open(a.out, "a") as f:
-        log(f, f"# tools/prec_errors.py  EGNN_F16_NODE={os.environ.get('EGNN_F16_NODE', '2')}  lib {_lib.LIB_PATH}  "
+        log(f, f"# tools/prec_errors.py  lib {_lib.LIB_PATH}  "
                    f"forward_sources_sha256={_lib.forward_sources_sha256()}")
         if not a.skip_goldens:
             goldens(f, precisions)

@@ -183,7 +183,7 @@ def main():
         ("bf16 edges + split-operand node MLP (bf16x2 input / weights / hidden)", dict(T, act="bf16", w2="bf16", nin="bf16x2", nw="bf16x2", nact="bf16x2")),
         ("  only the bf16 node MLP", dict(nin="bf16", nw="bf16", nact="bf16")),
         ("precision fp16 as built (fp16 everywhere)", dict(T, act="fp16", w2="fp16", nin="fp16", nw="fp16", nact="fp16")),
-        ("fp16 edges, exact node MLP (EGNN_F16_NODE=0)", dict(T, act="fp16", w2="fp16")),
+        ("fp16 edges, exact node MLP", dict(T, act="fp16", w2="fp16")),
         ("  only the fp16 table entries P, Q", dict(tab="fp16")),
         ("  only the fp16 sum P + Q", dict(tabsum="fp16")),
         ("  only the fp16 hidden activation", dict(act="fp16")),

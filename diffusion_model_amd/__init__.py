@@ -7,7 +7,7 @@ from .diffusion import E3DiffusionProcess, E3DiffusionProcessLegacy, E3Diffusion
 from .graph import GraphPlan, fully_connected_edge_index, fully_connected_plan, plan_edge_index, radius_plan  # noqa: F401
 from . import partition, stats  # noqa: F401
 from .partition import PartitionedSampler  # noqa: F401
-from .optim import RAdamScheduleFree, define_optimizer  # noqa: F401
+from .optim import FusedAdam, FusedAdamW, FusedRAdamScheduleFree, RAdamScheduleFree, define_optimizer  # noqa: F401
 from .sampler import DeviceSampler, generate  # noqa: F401
 from .preprocessor import SpectrumCompressor  # noqa: F401
 from .snr import GammaNetwork, PositiveLinear  # noqa: F401

@@ -11,6 +11,7 @@ NORM_CALL, NORM_GRAPH = 0, 1
 PRECISIONS = {"fp32": PREC_F32, "f32": PREC_F32, "float32": PREC_F32, "bf16": PREC_BF16, "bfloat16": PREC_BF16,
               "bf16x3": PREC_BF16X3, "f16c8": PREC_F16C8, "fp16": PREC_F16, "f16": PREC_F16, "float16": PREC_F16}
 NORM_SCOPES = {"call": NORM_CALL, "graph": NORM_GRAPH}
+OPTIM_ADAM, OPTIM_ADAMW_AMSGRAD, OPTIM_RADAM_SF = 0, 1, 2
 
 
 
@@ -74,6 +75,17 @@ def training_sources_sha256() -> str:
 _vp, _i, _f, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_uint64
 _fp = C.POINTER(C.c_float)
 
+
+class OptimConsts(C.Structure):
+    """egnn_optim_consts of include/egnn_amd.h: the per-step scalars of one optimizer step, computed by the caller in double
+    (optim.py: adam_scalars / radam_schedule_free_scalars) and rounded to fp32 on assignment"""
+    _fields_ = [(name, C.c_float) for name in ("beta2", "one_minus_beta2", "eps", "weight_decay", "one_minus_beta1",
+                                               "bias_correction2_sqrt", "step_size", "decay_mul", "bias_correction2", "ckp1",
+                                               "adaptive_y_lr", "lr")] + [("rectified", C.c_int32)]
+
+
+_pp, _i64p = C.POINTER(C.c_void_p), C.POINTER(C.c_int64)
+
 # name -> (restype, argtypes); kept in one table so tests can check every header symbol is exported
 SIGNATURES = {
     "egnn_last_error": (C.c_char_p, []),
@@ -129,6 +141,9 @@ SIGNATURES = {
     "egnn_radius_graph_fill": (_i, [_vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "egnn_rdf": (_i, [_vp, _i, _vp, _vp, C.c_double, C.c_double, _f, _i, _i, _vp]),
     "egnn_si_o_si": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _vp]),
+    "egnn_optim_step": (_i, [_vp, _i, _i, _pp, _pp, _pp, _pp, _pp, _i64p, C.POINTER(OptimConsts)]),
+    "egnn_optim_interp": (_i, [_vp, _i, _pp, _pp, _i64p, _f]),
+    "egnn_optim_tensors_per_launch": (_i, []),
     "egnn_debug_stamps": (_i, [_vp, C.POINTER(C.c_uint64)]),
     "egnn_profile_enable": (_i, [_vp, _i]),
     "egnn_profile_read": (_i, [_vp, _fp, C.POINTER(_i), _fp]),

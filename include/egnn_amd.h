@@ -383,6 +383,45 @@ int egnn_gamma_tilde(void* stream, int n, int hidden, const float* d_t, const fl
 int egnn_dense_rows(void* stream, int N, int K, int J, const float* d_in, const float* d_W, const float* d_b, int relu,
                     float* d_out);
 
+/* ---- optimizer step (csrc/optim/optim_step.hip) ------------------------------------------------------
+ * The three optimizers of define_optimizer (parts/def_for_main.py:119-139) as ONE multi-tensor launch per step: replaces the
+ * per-tensor element-wise loops of torch.optim.Adam, torch.optim.AdamW(amsgrad=True) (torch's single-tensor form) and
+ * schedulefree's RAdamScheduleFree (restated in diffusion_model_amd/optim.py).  All arithmetic is fp32, one IEEE operation at
+ * a time (no contraction, correctly rounded sqrt / div, denormals kept), in the order tests/_optim_mirror.py restates.
+ * The kernels hold no step-count logic: the CALLER computes the per-step scalars in double (bias corrections, rectified
+ * learning rate, averaging weight c_{k+1}, ...) and passes them rounded to fp32. */
+enum { EGNN_OPTIM_ADAM = 0,            /* torch.optim.Adam: L2 weight decay (g += wd p)                             */
+       EGNN_OPTIM_ADAMW_AMSGRAD = 1,   /* torch.optim.AdamW(amsgrad=True): decoupled decay (p *= 1 - lr wd)         */
+       EGNN_OPTIM_RADAM_SF = 2 };      /* RAdamScheduleFree.step (optim.py), parameters hold y                      */
+typedef struct egnn_optim_consts {
+  float beta2, one_minus_beta2;        /* all kinds: v = v beta2 + (g g) (1 - beta2)                                 */
+  float eps;                           /* all kinds                                                                  */
+  float weight_decay;                  /* ADAM: g += wd p; RADAM_SF: gn += wd y; 0 = skipped.  ADAMW: unused        */
+  float one_minus_beta1;               /* ADAM / ADAMW: m += (1 - beta1) (g - m)                                     */
+  float bias_correction2_sqrt;         /* ADAM / ADAMW: sqrt(1 - beta2^step)                                         */
+  float step_size;                     /* ADAM / ADAMW: lr / (1 - beta1^step)                                        */
+  float decay_mul;                     /* ADAMW: 1 - lr wd                                                           */
+  float bias_correction2;              /* RADAM_SF: 1 - beta2^step                                                   */
+  float ckp1;                          /* RADAM_SF: c_{k+1} = weight / weight_sum (0 while weight_sum is 0)          */
+  float adaptive_y_lr;                 /* RADAM_SF: lr_t (beta1 (1 - c_{k+1}) - 1)                                   */
+  float lr;                            /* RADAM_SF: the rectified (scheduled) learning rate lr_t                     */
+  int32_t rectified;                   /* RADAM_SF: rho_t > 4 (gn = g / (sqrt(v / bc2) + eps)); 0: gn = g           */
+} egnn_optim_consts;
+/* One step over n tensors.  d_p / d_g / d_s0 / d_s1 / d_s2 are HOST arrays of n device pointers, numel the n element counts
+ * (fp32, contiguous; each pointer needs 4-byte alignment only, each on its own).  d_g[i] == NULL skips tensor i (p.grad is
+ * None).  States: ADAM s0 = exp_avg, s1 = exp_avg_sq (d_s2 may be NULL); ADAMW_AMSGRAD + s2 = max_exp_avg_sq; RADAM_SF s0 = z,
+ * s1 = exp_avg_sq (d_s2 may be NULL).  Tensor descriptors travel in the kernel arguments: one launch takes up to
+ * egnn_optim_tensors_per_launch() tensors whose state pointers share one spacing (s1[i] - s0[i] and s2[i] - s0[i] the same for
+ * every i, as with states laid out alike in flat buffers); a list is cut where the capacity or the spacing ends, so ANY list
+ * is valid and a flat-state list of n tensors takes ceil(n / capacity) launches.  No allocation, copy or synchronisation. */
+int egnn_optim_step(void* stream, int kind, int n, float* const* d_p, const float* const* d_g, float* const* d_s0,
+                    float* const* d_s1, float* const* d_s2, const int64_t* numel, const egnn_optim_consts* consts);
+/* p <- p + weight (z - p) over the list: the y <-> x switch of RAdamScheduleFree.train() / .eval() (optim.py;
+ * parts/train_per_iretation.py:103-104, :189-190), same launch rule. */
+int egnn_optim_interp(void* stream, int n, float* const* d_p, const float* const* d_z, const int64_t* numel, float weight);
+/* compile-time tensor capacity of one launch (pure host) */
+int egnn_optim_tensors_per_launch(void);
+
 /* timing helper for bench.py: average duration (ms) of the fused edge kernel over the launches
  * recorded since the last reset, measured with HIP events on the launch stream. */
 /* diagnostic builds only (-DEGNN_EXP_STAMP): s_memtime stamps [2][8][32][4] of one edge workgroup */

@@ -12,6 +12,8 @@ PRECISIONS = {"fp32": PREC_F32, "f32": PREC_F32, "float32": PREC_F32, "bf16": PR
               "bf16x3": PREC_BF16X3, "f16c8": PREC_F16C8, "fp16": PREC_F16, "f16": PREC_F16, "float16": PREC_F16}
 NORM_SCOPES = {"call": NORM_CALL, "graph": NORM_GRAPH}
 OPTIM_ADAM, OPTIM_ADAMW_AMSGRAD, OPTIM_RADAM_SF = 0, 1, 2
+KABSCH_CENTERS = {"centroid": 0, "first": 1}
+KABSCH_FLIPS = {"row": 0, "column": 1}
 
 
 
@@ -141,6 +143,9 @@ SIGNATURES = {
     "egnn_radius_graph_fill": (_i, [_vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "egnn_rdf": (_i, [_vp, _i, _vp, _vp, C.c_double, C.c_double, _f, _i, _i, _vp]),
     "egnn_si_o_si": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _vp]),
+    "egnn_kabsch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "egnn_kabsch_perm_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "egnn_kabsch_perm": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
     "egnn_optim_step": (_i, [_vp, _i, _i, _pp, _pp, _pp, _pp, _pp, _i64p, C.POINTER(OptimConsts)]),
     "egnn_optim_interp": (_i, [_vp, _i, _pp, _pp, _i64p, _f]),
     "egnn_optim_tensors_per_launch": (_i, []),

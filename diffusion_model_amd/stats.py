@@ -116,3 +116,151 @@ def compare_si_o_si(orig_pos, orig_onehot, gen_pos, gen_onehot, sizes):
     if out["n_selected"] >= 2:
         out["r2_angle"], out["r2_length"] = r2score(ao, ag), r2score(lo, lg)
     return out
+
+
+# ---- structural RMSD evaluation (csrc/eval/kabsch.hip) -------------------------------------------------------------
+def _kabsch_launch(P, Q, gp, B, center, flip, x_p=None, x_q=None):
+    """-> device float [B, 16]: R [9], t [3], rmsd, O rows of x_p, O rows of x_q, 0 (egnn_kabsch)"""
+    if center not in _lib.KABSCH_CENTERS or flip not in _lib.KABSCH_FLIPS:
+        raise ValueError("center must be 'centroid' or 'first', flip 'row' or 'column'")
+    out = torch.empty(B, 16, device=P.device)
+    A = 0 if x_p is None else int(x_p.shape[1])
+    _lib.check(_lib.lib().egnn_kabsch(_lib.stream_ptr(), B, _lib.ptr(P), _lib.ptr(Q), _lib.ptr(gp), _lib.KABSCH_CENTERS[center],
+                                      _lib.KABSCH_FLIPS[flip], _lib.ptr(x_p), _lib.ptr(x_q), A, _lib.ptr(out)))
+    return out
+
+
+def kabsch(P: torch.Tensor, Q: torch.Tensor, sizes: Sequence[int] | None = None, center="centroid", flip="column"):
+    """Kabsch fit of P onto Q -> (R, t, rmsd) with R p_i ~ q_i, for one graph ([n,3] -> [3,3], [3], 0-dim) or a batch of
+    graphs (``sizes`` given: [N,3] -> [B,3,3], [B,3], [B]) in one launch.  The defaults are kabsch_torch of
+    evaluate_rmsd_for_pos_generate.py:11-51, which parts/def_for_main.py:82,101 call; (center, flip) = ('centroid', 'row') is
+    kabsch_numpy of the same file (:53-92) and ('first', 'row') kabsch_numpy of evaluate_rmsd.py:10-42 (t = Q[0] - P[0], which
+    that spelling does not return).  'row' is the optimal proper rotation; 'column' reproduces the reference's non-optimal
+    reflection fix.  Where p^T q is rank deficient both return the optimal proper rotation (include/egnn_amd.h)."""
+    if not (P.is_cuda and Q.is_cuda):
+        raise RuntimeError("kabsch needs CUDA(ROCm) tensors; there is no CPU fallback")
+    if P.shape != Q.shape:
+        raise ValueError("Matrix dimensions must match")
+    single = sizes is None
+    if single:
+        sizes = [P.shape[0]]
+    gp, B, N = _graph_ptr(sizes, P.device)
+    if P.shape != (N, 3):
+        raise ValueError("P and Q must be [sum(sizes), 3]")
+    out = _kabsch_launch(P.detach().to(torch.float32).contiguous(), Q.detach().to(torch.float32).contiguous(), gp, B, center, flip)
+    R, t, rmsd = out[:, :9].reshape(B, 3, 3), out[:, 9:12], out[:, 12]
+    return (R[0], t[0], rmsd[0]) if single else (R, t, rmsd)
+
+
+def _collate_pairs(original_graph_list, generated_graph_list, with_types):
+    """positions (and atom types) of the originals -- the caller's records, possibly on the host: concatenated there and uploaded
+    once -- and of the samples (``generated_graph_list[i][-1]``, on the device as generate() leaves them)"""
+    if len(original_graph_list) != len(generated_graph_list):
+        raise ValueError("original_graph_list and generated_graph_list differ in length")
+    if not original_graph_list:
+        return None
+    gens = [g[-1] for g in generated_graph_list]
+    dev = gens[0].pos.device
+    if dev.type != "cuda":
+        raise RuntimeError("RMSD evaluation needs the samples on a CUDA(ROCm) device; there is no CPU fallback")
+    for o in original_graph_list:
+        if not hasattr(o, "pos"):
+            raise ValueError("RMSD evaluation needs the original structures (generate() of a conditional model)")
+    sizes = [int(o.pos.shape[0]) for o in original_graph_list]
+    if sizes != [int(g.pos.shape[0]) for g in gens]:
+        raise ValueError("Matrix dimensions must match")
+    po = torch.cat([o.pos.detach().to(torch.float32) for o in original_graph_list]).to(dev).contiguous()
+    pg = torch.cat([g.pos.detach().to(device=dev, dtype=torch.float32) for g in gens]).contiguous()
+    xo = xg = None
+    if with_types:
+        xo = torch.cat([o.x.detach().to(torch.int32) for o in original_graph_list]).to(dev).contiguous()
+        xg = torch.cat([g.x.detach().to(device=dev, dtype=torch.int32) for g in gens]).contiguous()
+    return sizes, gens, po, pg, xo, xg
+
+
+def _evaluate(original_graph_list, generated_graph_list, with_types):
+    col = _collate_pairs(original_graph_list, generated_graph_list, with_types)
+    if col is None:
+        return []
+    sizes, gens, po, pg, xo, xg = col
+    gp, B, _ = _graph_ptr(sizes, po.device)
+    out = _kabsch_launch(po, pg, gp, B, "centroid", "column", xo, xg).cpu()   # ONE launch, ONE download
+    rows = []
+    for i, n in enumerate(sizes):
+        if n == 1:
+            continue
+        original = original_graph_list[i]
+        row = (original.id, out[i, 12])
+        if with_types:
+            row += ([int(out[i, 13]) / n, int(out[i, 14]) / n],)
+        rows.append(row + (original, gens[i]))
+    return sorted(rows, key=lambda r: r[1])   # stable, as the reference's
+
+
+def evaluate_by_rmsd(original_graph_list, generated_graph_list):
+    """evaluate_by_rmsd(original_graph_list, generated_graph_list) of parts/def_for_main.py:73-89 on what generate() returns:
+    [(id, rmsd, original_graph, generated_graph)] sorted by RMSD (kabsch_torch: centroid, column flip), one-atom graphs
+    skipped; ``rmsd`` is a 0-dim tensor.  All graphs go through one launch and one download."""
+    return _evaluate(original_graph_list, generated_graph_list, False)
+
+
+def evaluate_by_rmsd_and_atom_type_eval(original_graph_list, generated_graph_list):
+    """parts/def_for_main.py:91-117: as evaluate_by_rmsd with [fraction of O rows ([1, 0]) in the original, in the sample]
+    after the RMSD: [(id, rmsd, [frac_original, frac_generated], original_graph, generated_graph)]."""
+    return _evaluate(original_graph_list, generated_graph_list, True)
+
+
+def kabsch_min_over_permutations(P: torch.Tensor, Q: torch.Tensor, sizes: Sequence[int], max_atoms=10, out=None):
+    """The correspondence search of evaluate_rmsd.py:93-107 on a batch: per graph with 2 <= n <= max_atoms (<= 12) the minimum
+    over all orderings [0] + perm(1..n-1) of the rows of P (generated) of the atom-0-anchored, row-flip Kabsch RMSD against Q
+    (original).  -> (min_rmsd [B], order int32 [N], R [B,3,3], searched bool [B]) on the device; rows of graphs that were not
+    searched keep what ``out`` = (min_rmsd, order, R) held (uninitialised without ``out``)."""
+    if not (P.is_cuda and Q.is_cuda):
+        raise RuntimeError("kabsch_min_over_permutations needs CUDA(ROCm) tensors; there is no CPU fallback")
+    gp, B, N = _graph_ptr(sizes, P.device)
+    if P.shape != (N, 3) or Q.shape != (N, 3):
+        raise ValueError("P and Q must be [sum(sizes), 3]")
+    P, Q = (t.detach().to(torch.float32).contiguous() for t in (P, Q))
+    if out is None:
+        out = (torch.empty(B, device=P.device), torch.empty(N, dtype=torch.int32, device=P.device), torch.empty(B, 3, 3, device=P.device))
+    rmsd, order, R = out
+    searched = torch.empty(B, dtype=torch.int32, device=P.device)
+    nbytes = int(_lib.lib().egnn_kabsch_perm_workspace_bytes(B, int(max_atoms)))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=P.device)
+    _lib.check(_lib.lib().egnn_kabsch_perm(_lib.stream_ptr(), B, _lib.ptr(P), _lib.ptr(Q), _lib.ptr(gp), int(max_atoms), _lib.ptr(rmsd),
+                                           _lib.ptr(order), _lib.ptr(R), _lib.ptr(searched), _lib.ptr(ws), nbytes))
+    return rmsd, order, R, searched != 0
+
+
+def min_rmsd_over_permutations(original_graph_list, generated_graph_list, max_atoms=10):
+    """What evaluate_rmsd.py:82-109 computes before it writes files: per graph with 2 <= n <= max_atoms
+    (id, min_rmsd, order, aligned_pos, x_reordered) -- id with the reference's occurrence suffix ``f'{id}_{k}'`` (k counts the
+    graphs of at most max_atoms atoms with that id, :88-92), min_rmsd a float, order a list, aligned_pos = the reordered sample
+    about its atom 0 rotated onto the original ([n,3]), x_reordered = sample.x[order]; host tensors, in list order."""
+    col = _collate_pairs(original_graph_list, generated_graph_list, True)
+    if col is None:
+        return []
+    sizes, gens, po, pg, xo, xg = col
+    rmsd, order, R, searched = kabsch_min_over_permutations(pg, po, sizes, max_atoms)
+    dev = pg.device
+    sz = torch.tensor(sizes, device=dev)
+    gid = torch.repeat_interleave(torch.arange(len(sizes), device=dev), sz)
+    first = torch.cumsum(sz, 0) - sz
+    atom_ok = searched[gid]
+    src = torch.where(atom_ok, first[gid] + order.long(), torch.arange(pg.shape[0], device=dev))
+    aligned = torch.einsum("nij,nj->ni", torch.where(atom_ok[:, None, None], R[gid], torch.zeros((), device=dev)),
+                           pg[src] - pg[first[gid]])
+    rmsd, order, searched, aligned, xr = (t.cpu() for t in (rmsd, order, searched, aligned, xg[src]))
+    seen, rows, lo = {}, [], 0
+    for i, n in enumerate(sizes):
+        sl = slice(lo, lo + n)
+        lo += n
+        if n > max_atoms:
+            continue
+        gid_ = original_graph_list[i].id
+        seen[gid_] = seen.get(gid_, 0) + 1
+        if not bool(searched[i]):
+            continue
+        rows.append((f"{gid_}_{seen[gid_]}", float(rmsd[i]), order[sl].tolist(), aligned[sl].clone(),
+                     xr[sl].to(gens[i].x.dtype)))
+    return rows

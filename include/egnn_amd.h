@@ -372,6 +372,38 @@ int egnn_rdf(void* stream, int B, const float* d_pos, const int32_t* d_graph_ptr
 int egnn_si_o_si(void* stream, int B, int A, const float* d_pos, const int32_t* d_onehot,
                  const int32_t* d_graph_ptr, float cutoff, float* d_out);
 
+/* ---- structural RMSD evaluation (csrc/eval/kabsch.hip) ---------------------------------------------------
+ * Batched Kabsch fit of P onto Q (both [N,3], graphs through d_graph_ptr int32[B+1] as for egnn_rdf), one wavefront per graph,
+ * fp64 inside.  The reference has three spellings that differ in the centre and in the reflection fix:
+ *   kabsch_torch  (evaluate_rmsd_for_pos_generate.py:11-51; what def_for_main.py:82,101 call)  CENTROID + FLIP_COLUMN
+ *   kabsch_numpy  (evaluate_rmsd_for_pos_generate.py:53-92)                                     CENTROID + FLIP_ROW
+ *   kabsch_numpy  (evaluate_rmsd.py:10-42, create_xyz.py:48-80)                                 FIRST    + FLIP_ROW
+ * FLIP_ROW (`Vt[-1, :] *= -1`) is the textbook fix: the optimal proper rotation.  FLIP_COLUMN (`Vt[:, -1] *= -1`) returns
+ * diag(1,1,-1) V U^T in a reflection case: a proper rotation, not the optimal one.  Where H = p^T q is rank deficient (two
+ * atoms; three atoms about their centroid; planar sets: sigma_3 <= 1e-12 sigma_1) the reference's answer in a reflection case
+ * depends on LAPACK's choice of null vector; the device result there is the optimal proper rotation for BOTH flips, with missing
+ * singular directions completed by a fixed rule (csrc/eval/kabsch_math.h).
+ * d_out float[B,16] per graph: R [3,3] row-major (R p_i ~ q_i), t [3] = c_Q - c_P (the centroids, or Q[0] - P[0] for FIRST),
+ * rmsd = sqrt(sum |R p - q|^2 / n) computed as that residual, then the number of rows of d_x_p / d_x_q (int32 [N,A], both or
+ * neither NULL) equal to one-hot O = [1, 0, ...] (the atom-type counts of def_for_main.py:103-111), and 0. */
+enum { EGNN_KABSCH_CENTROID = 0, EGNN_KABSCH_FIRST = 1 };
+enum { EGNN_KABSCH_FLIP_ROW = 0, EGNN_KABSCH_FLIP_COLUMN = 1 };
+int egnn_kabsch(void* stream, int B, const float* d_P, const float* d_Q, const int32_t* d_graph_ptr, int center, int flip,
+                const int32_t* d_x_p, const int32_t* d_x_q, int A, float* d_out);
+/* Correspondence search of evaluate_rmsd.py:93-107: per graph with 2 <= n <= max_atoms (max_atoms <= 12) the minimum over all
+ * orderings [0] + perm(1..n-1) of the rows of P (the generated structure) of the FIRST + FLIP_ROW RMSD against Q (the original).
+ * Orderings are ranked in fp64 by the trace of their optimal proper rotation (atom 0 is the centre of every ordering, so this
+ * is arg min RMSD without a difference of large numbers); equal scores go to the lexicographically first ordering
+ * (itertools.permutations order: the reference keeps the first strict minimum); the result is bitwise reproducible.
+ * Outputs per searched graph: d_min_rmsd [B] (residual of the winner), d_order int32 [N] (ragged through d_graph_ptr:
+ * row i of the result is row order[i] of P), d_R [B,9] (rotation of the winner), d_searched int32 [B] = 1.  Graphs with
+ * n < 2 or n > max_atoms cost no work: d_searched = 0 and their other outputs are not written.  1 <= B <= 65535 per call.
+ * d_workspace: egnn_kabsch_perm_workspace_bytes(B, max_atoms) bytes of device memory (the workgroups' partial results). */
+size_t egnn_kabsch_perm_workspace_bytes(int B, int max_atoms);
+int egnn_kabsch_perm(void* stream, int B, const float* d_P, const float* d_Q, const int32_t* d_graph_ptr, int max_atoms,
+                     float* d_min_rmsd, int32_t* d_order, float* d_R, int32_t* d_searched, void* d_workspace,
+                     size_t workspace_bytes);
+
 /* ---- the two small networks at the edge of the path ---------------------------------------------------
  * gamma_tilde(t_i) = l1(t_i) + l3(sigmoid(l2(l1(t_i)))) of GammaNetwork (SNR.py:50-52) with PositiveLinear's softplus weights
  * (:5-22) for n time points; d_l1_w [1], d_l2_w [hidden], d_l3_w [hidden] are the RAW parameters (l1.weight, l2.weight,

@@ -14,6 +14,8 @@ NORM_SCOPES = {"call": NORM_CALL, "graph": NORM_GRAPH}
 OPTIM_ADAM, OPTIM_ADAMW_AMSGRAD, OPTIM_RADAM_SF = 0, 1, 2
 KABSCH_CENTERS = {"centroid": 0, "first": 1}
 KABSCH_FLIPS = {"row": 0, "column": 1}
+ASSIGN_MAX_ATOMS = 1024   # EGNN_ASSIGN_MAX_ATOMS of include/egnn_amd.h (kAssignMaxAtoms)
+PREALIGN_MIN_ATOMS = 5    # kPrealignMinAtoms of csrc/eval/assign_host.h: atom 0 and its four nearest neighbours
 
 
 
@@ -146,6 +148,8 @@ SIGNATURES = {
     "egnn_kabsch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "egnn_kabsch_perm_workspace_bytes": (C.c_size_t, [_i, _i]),
     "egnn_kabsch_perm": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
+    "egnn_assign": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "egnn_assign_prealign": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "egnn_optim_step": (_i, [_vp, _i, _i, _pp, _pp, _pp, _pp, _pp, _i64p, C.POINTER(OptimConsts)]),
     "egnn_optim_interp": (_i, [_vp, _i, _pp, _pp, _i64p, _f]),
     "egnn_optim_tensors_per_launch": (_i, []),

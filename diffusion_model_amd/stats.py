@@ -264,3 +264,84 @@ def min_rmsd_over_permutations(original_graph_list, generated_graph_list, max_at
         rows.append((f"{gid_}_{seen[gid_]}", float(rmsd[i]), order[sl].tolist(), aligned[sl].clone(),
                      xr[sl].to(gens[i].x.dtype)))
     return rows
+
+
+# ---- atom matching of large graphs (csrc/eval/assign.hip) ----------------------------------------------------------
+def linear_assignment(P: torch.Tensor, Q: torch.Tensor, sizes: Sequence[int], out=None):
+    """Batched linear sum assignment on the Euclidean distance matrices of a batch of graphs (hungarian_algorithm of
+    create_xyz.py:82-85 = scipy.optimize.linear_sum_assignment(norm(P[:, None] - Q[None, :]))), one launch:
+    -> (col int32 [N], cost float64 [B], solved bool [B]) on the device.  Row i of a graph's P is matched to row col[i] of its
+    Q (local indices; scipy's row_ind is 0..n-1), cost = sum_i |P_i - Q_col[i]| is minimal.  Exact (shortest augmenting paths,
+    fp64 duals, fp32 distances as numpy computes them on float32 arrays); equal path costs go to the lowest column index, so
+    the result is bitwise reproducible and, where the optimum is unique, scipy's.  Graphs with 1 <= n <= 1024 (_lib.ASSIGN_MAX_ATOMS)
+    are solved; rows of the others keep what ``out`` = (col, cost) held (uninitialised without ``out``)."""
+    if not (P.is_cuda and Q.is_cuda):
+        raise RuntimeError("linear_assignment needs CUDA(ROCm) tensors; there is no CPU fallback")
+    if P.shape != Q.shape:
+        raise ValueError("Matrix dimensions must match")
+    gp, B, N = _graph_ptr(sizes, P.device)
+    if P.shape != (N, 3):
+        raise ValueError("P and Q must be [sum(sizes), 3]")
+    if B < 1:
+        raise ValueError("linear_assignment needs at least one graph")
+    P, Q = (t.detach().to(torch.float32).contiguous() for t in (P, Q))
+    if out is None:
+        out = (torch.empty(N, dtype=torch.int32, device=P.device), torch.empty(B, dtype=torch.float64, device=P.device))
+    col, cost = out
+    if col.shape != (N,) or col.dtype != torch.int32 or cost.shape != (B,) or cost.dtype != torch.float64 or not (
+            col.is_cuda and cost.is_cuda and col.is_contiguous() and cost.is_contiguous()):
+        raise ValueError("out must be (int32 [N], float64 [B]) contiguous device tensors")
+    solved = torch.empty(B, dtype=torch.int32, device=P.device)
+    max_atoms = max(1, min(max(int(s) for s in sizes), _lib.ASSIGN_MAX_ATOMS))   # <= 64: the one-wavefront launch
+    _lib.check(_lib.lib().egnn_assign(_lib.stream_ptr(), B, _lib.ptr(P), _lib.ptr(Q), _lib.ptr(gp), max_atoms, _lib.ptr(col),
+                                      _lib.ptr(cost), _lib.ptr(solved)))
+    return col, cost, solved != 0
+
+
+def align_by_assignment(original_graph_list, generated_graph_list, min_atoms=6):
+    """What create_xyz.py:157-192 computes before it writes files, on what generate() returns: per graph with
+    min_atoms <= n <= 1024 the sample is pre-aligned on the best of the 24 pairings of the four atoms nearest to atom 0 of either
+    structure (:158-181), its atoms are matched to the original's by a linear sum assignment on the distances (:182), both
+    structures are reordered (:183-190) and the atom-0-anchored, row-flip Kabsch RMSD of the matched pair is taken (:191).
+    -> [(id, rmsd, row_ind, col_ind, original_pos_reordered, generated_pos_aligned_reordered, original_x_reordered,
+    generated_x_reordered)] in list order: id = f'{original.id}_{i % 5 + 1}' (i the list index, :120), rmsd a float, row_ind /
+    col_ind int64 arrays (scipy's: row_ind = 0..n-1), positions about atom 0 (the sample's rotated), host tensors.  The whole list
+    is collated once, goes through three launches (pre-alignment, assignment, Kabsch) and is downloaded once; graphs below
+    min_atoms are min_rmsd_over_permutations' (the reference's exhaustive branch, :131-156)."""
+    if int(min_atoms) < _lib.PREALIGN_MIN_ATOMS:
+        raise ValueError(f"min_atoms must be at least {_lib.PREALIGN_MIN_ATOMS}: atom 0 and its four nearest neighbours")
+    col_ = _collate_pairs(original_graph_list, generated_graph_list, True)
+    if col_ is None:
+        return []
+    sizes, gens, po, pg, xo, xg = col_
+    dev = pg.device
+    gp, B, N = _graph_ptr(sizes, dev)
+    R = torch.zeros(B, 9, device=dev)
+    prealigned = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().egnn_assign_prealign(_lib.stream_ptr(), B, _lib.ptr(po), _lib.ptr(pg), _lib.ptr(gp), int(min_atoms),
+                                               _lib.ptr(R), _lib.ptr(prealigned)))
+    sz = torch.tensor(sizes, device=dev)
+    gid = torch.repeat_interleave(torch.arange(B, device=dev), sz)
+    first = torch.cumsum(sz, 0) - sz
+    oc = po - po[first[gid]]
+    aligned = torch.einsum("nij,nj->ni", R.reshape(B, 3, 3)[gid], pg - pg[first[gid]]).contiguous()
+    col = torch.zeros(N, dtype=torch.int32, device=dev)
+    col, _, solved = linear_assignment(oc, aligned, sizes, out=(col, torch.empty(B, dtype=torch.float64, device=dev)))
+    src = first[gid] + col.long()
+    matched = aligned[src].contiguous()
+    fit = _kabsch_launch(matched, oc, gp, B, "first", "row")
+    # one download: every result is 4 bytes wide, so they travel bit-cast in one int32 buffer
+    parts = ((solved & (prealigned != 0)).to(torch.int32), fit[:, 12], col, oc, matched, xg[src])
+    blob = torch.cat([t.contiguous().view(torch.int32).reshape(-1) for t in parts]).cpu()
+    keep, rmsd, col, oc, matched, xr = (piece.view(t.dtype).reshape(t.shape)
+                                        for piece, t in zip(blob.split([t.numel() for t in parts]), parts))
+    rows, lo = [], 0
+    for i, n in enumerate(sizes):
+        sl = slice(lo, lo + n)
+        lo += n
+        if n < min_atoms or not bool(keep[i]):
+            continue
+        original = original_graph_list[i]
+        rows.append((f"{original.id}_{i % 5 + 1}", float(rmsd[i]), np.arange(n), col[sl].numpy().astype(np.int64), oc[sl].clone(),
+                     matched[sl].clone(), original.x.detach().cpu().clone(), xr[sl].to(gens[i].x.dtype)))
+    return rows

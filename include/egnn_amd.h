@@ -404,6 +404,36 @@ int egnn_kabsch_perm(void* stream, int B, const float* d_P, const float* d_Q, co
                      float* d_min_rmsd, int32_t* d_order, float* d_R, int32_t* d_searched, void* d_workspace,
                      size_t workspace_bytes);
 
+/* ---- atom matching of large graphs (csrc/eval/assign.hip) --------------------------------------------------
+ * What create_xyz.py:157-192 computes for graphs of six atoms or more before it writes files: a pre-alignment on the four atoms
+ * nearest to atom 0, a linear sum assignment on the distance matrix of all atoms, and (through egnn_kabsch, FIRST + FLIP_ROW, on
+ * the reordered rows) the RMSD of the matched pair.  Both entries: caller-owned buffers, graphs through d_graph_ptr int32[B+1],
+ * one workgroup per graph, 1 <= B <= 2147483647 (grid x), no workspace, no allocation, copy or synchronisation.
+ *
+ * egnn_assign replaces hungarian_algorithm (create_xyz.py:82-85, called at :182): per graph with 1 <= n <= max_atoms
+ * (max_atoms <= EGNN_ASSIGN_MAX_ATOMS) the permutation col that minimises sum_i |P_i - Q_col[i]|, by an exact
+ * shortest-augmenting-path solver with fp64 duals.  A cost entry is the fp32 norm of the fp32 coordinate difference,
+ * sqrtf((dx*dx + dy*dy) + dz*dz), widened to fp64 -- what numpy.linalg.norm on float32 arrays hands to scipy; the matrix is
+ * never stored.  Rows are augmented in index order and equal path costs go to the lowest column index: where the optimum is
+ * unique the result is scipy.optimize.linear_sum_assignment's col_ind (its row_ind is 0..n-1), where it is not, one optimal
+ * assignment, always the same one, bitwise, wherever the graph sits in the batch.
+ * Outputs per solved graph: d_col int32 [N] (ragged through d_graph_ptr: row i of P is matched to row col[i] of Q, local
+ * indices), d_cost double [B] (the sum above, fp64), d_solved int32 [B] = 1.  Graphs with n < 1 or n > max_atoms cost no work,
+ * graphs with non-finite coordinates have no optimum: d_solved = 0 and their other outputs are not written.  Graphs of up to 64
+ * atoms run on one wavefront; pass max_atoms <= 64 where no graph is larger (64-thread workgroups, 2 KB of LDS). */
+#define EGNN_ASSIGN_MAX_ATOMS 1024
+int egnn_assign(void* stream, int B, const float* d_P, const float* d_Q, const int32_t* d_graph_ptr, int max_atoms,
+                int32_t* d_col, double* d_cost, int32_t* d_solved);
+/* egnn_assign_prealign replaces create_xyz.py:158-176 (with return_near_from_exO, :87-96): per graph with n >= min_atoms
+ * (min_atoms >= 5) the four atoms nearest to atom 0 of d_orig and of d_gen (ascending distance, equal distances to the lower
+ * index, as the reference's stable sort), the 24 FIRST + FLIP_ROW fits of [gen[0], gen[idx_gen[perm[0..3]]]] onto
+ * [orig[0], orig[idx_orig[0..3]]] in itertools.permutations(range(4)) order, fp64, and the rotation of the smallest five-point
+ * RMSD, equal values to the first permutation.  d_R float [B,9] row-major: R (gen_i - gen_0) ~ orig_i - orig_0, i.e. the
+ * reference's aligned_generated_pos (:177-181) is (gen - gen[0]) R^T.  d_prealigned int32 [B] = 1; graphs with n < min_atoms
+ * (or without four finite neighbour distances, or with no pairing of finite residual) get 0 and their R is not written. */
+int egnn_assign_prealign(void* stream, int B, const float* d_orig, const float* d_gen, const int32_t* d_graph_ptr, int min_atoms,
+                         float* d_R, int32_t* d_prealigned);
+
 /* ---- the two small networks at the edge of the path ---------------------------------------------------
  * gamma_tilde(t_i) = l1(t_i) + l3(sigmoid(l2(l1(t_i)))) of GammaNetwork (SNR.py:50-52) with PositiveLinear's softplus weights
  * (:5-22) for n time points; d_l1_w [1], d_l2_w [hidden], d_l3_w [hidden] are the RAW parameters (l1.weight, l2.weight,

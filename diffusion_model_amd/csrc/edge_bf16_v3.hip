@@ -31,9 +31,13 @@ constexpr int kKC3 = 64;
 constexpr size_t kA1_3 = (size_t)8 * kRPAD3 * 16;  // one activation chunk [8 k-groups][129][8 bf16]
 using namespace tile128;
 constexpr size_t kOffA1 = kOffLoop;      // 2 activation chunks, then wd[KP] (the per-tile arrays: edge_tile.h)
-__host__ __device__ inline size_t v3_smem_bytes(int KP, int MP, bool is_m) {
+// The BWD / SAVE epilogues stage their row-major bf16 stores in the K-loop region, 8 waves x [32][72] bf16: the allocation of a
+// kernel that stages is max(K-loop buffers, staging) -- the K-loop buffers alone cover the staging only at KP = 1024.
+constexpr size_t kStage3 = (size_t)8 * 32 * 72 * 2;
+__host__ __device__ inline size_t v3_smem_bytes(int KP, int MP, bool is_m, bool staged = true) {
   (void)MP; (void)is_m;
-  return kOffA1 + 2 * kA1_3 + (size_t)KP * 4;
+  const size_t loop = 2 * kA1_3 + (size_t)KP * 4;
+  return kOffA1 + (staged && kStage3 > loop ? kStage3 : loop);
 }
 
 // BWD = true: the training backward's recompute pass over a chunk of edges (egcl_backward_edge_recompute).  Same
@@ -407,14 +411,13 @@ bool edge_bf16_v3_supported(const EdgeParams& p) {
 int launch_edge_bf16_v3_x(const EdgeParams& p, hipStream_t st) {
   const int tiles = (p.E + kR3 - 1) / kR3;
   if (p.WxP != 256) { set_error("edge_bf16_v3: forward kernel kept for WxP = 256 only"); return EGNN_EINVAL; }
-  return launch_v3<1, false>(p, tiles, v3_smem_bytes(p.WxP, p.MP, false), st);
+  return launch_v3<1, false>(p, tiles, v3_smem_bytes(p.WxP, p.MP, false, false), st);   // (the plain forward stages nothing)
 }
 
 // backward recompute of the coordinate branch over the chunk of edges described by p (p.E edges, p.edge_dst / p.edge_src
 // already offset to the chunk)
 int launch_edge_bf16_v3_x_bwd(const EdgeParams& p, hipStream_t st) {
   const int tiles = (p.E + kR3 - 1) / kR3;
-  static_assert(8 * 32 * 72 * 2 <= 2 * kA1_3 + 1024 * 4, "store staging must fit the K-loop buffers");
   if (p.WxP >= 512) return launch_v3<2, false, true>(p, tiles * (p.WxP / 512), v3_smem_bytes(p.WxP, p.MP, false), st);
   return launch_v3<1, false, true>(p, tiles, v3_smem_bytes(p.WxP, p.MP, false), st);
 }

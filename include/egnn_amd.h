@@ -211,7 +211,10 @@ int egcl_backward_edge_recompute(egnn_ctx* ctx, void* stream, int layer, const f
  *   s1x [E, Wx], s1m [E, Wm]  bf16 as above (scaled by -log2(e)),
  *   t2x [E, Wx], t2m [E, M]   bf16 = -log2(e) * (second-layer pre-activation incl. bias),
  *   s_shares [Wx / 512][E]    fp32 column-split shares of s_e = w3 . SiLU(a2) + b3 (their sum is s_e);
- * (h_out, x_out) are bitwise those of egcl_forward, and the per-graph sums of d^2 stay readable (egcl_read_aggregates).
+ * (h_out, x_out) are those of egcl_forward in bf16 -- bitwise where egcl_forward runs the same 128-edge-tile kernels (hidden
+ * width 256, or more than 6,144 edges); for smaller batches at hidden width 512 / 1024 egcl_forward takes 32 / 64-edge tiles
+ * (csrc/edge_small.hip), whose per-edge products and per-node sums are the same terms accumulated in another order: the three
+ * aggregates then agree to fp32 accumulation error, not bitwise.  The per-graph sums of d^2 stay readable (egcl_read_aggregates).
  * egcl_backward_heads_saved then turns rows [e_first, e_first + n_edges) of t2x / t2m into dL/d(a2) IN PLACE (an
  * element-wise pass at HBM speed: loss.backward() of parts/train_per_iretation.py:172 for the two heads, :57-65) and adds
  * the column sums / writes g_diff exactly as egcl_backward_edge_recompute does.  d_t2x / d_t2m point at row e_first. */

@@ -733,16 +733,29 @@ def test_width_sweep_all_edge_kernel_variants(H, m_size, wm, wx, wh):
             assert ex <= tol, (scope, precision, "eps_x")
 
 
-@pytest.mark.parametrize("precision", ["bf16", "fp16"])
-@pytest.mark.parametrize("wx", [1024, 512])
-def test_persistent_coordinate_kernel_is_bitwise_the_per_tile_kernel(precision, wx, monkeypatch):
+# (the fully connected cases keep the ids they had before the graph parameter was added)
+@pytest.mark.parametrize("wx,precision,graph", [(wx, p, g) for g in ("fully_connected", "irregular") for p in ("bf16", "fp16") for wx in (1024, 512)],
+                         ids=[f"{wx}-{p}" + ("" if g == "fully_connected" else "-" + g) for g in ("fully_connected", "irregular")
+                              for p in ("bf16", "fp16") for wx in (1024, 512)])
+def test_persistent_coordinate_kernel_is_bitwise_the_per_tile_kernel(precision, wx, graph, monkeypatch):
     """csrc/edge_x_m16.hip, PERSIST form (one workgroup per CU walking over its units with the next unit's prologue requested under
     the current epilogue; chosen when there are more than two units per CU) against the one-workgroup-per-unit form (EGNN_X_PERSIST=0,
     read per launch): the same arithmetic in the same order, so every output bit must agree -- on a ragged batch whose tile count is
-    no multiple of anything (a last tile of a few rows, graphs that straddle tiles, a single-atom graph), one layer and two."""
-    sizes = [61, 64, 1, 57, 64, 33, 64, 64, 50, 64, 64, 63, 64, 17, 64, 64, 64, 59, 64, 64, 64, 64, 2, 64, 64, 64, 64, 64, 64, 64] * (1 if wx == 1024 else 2)
-    E = sum(n * (n - 1) for n in sizes)
+    no multiple of anything (a last tile of a few rows, graphs that straddle tiles, a single-atom graph), one layer and two.
+    graph "irregular": the 128-edge-tile irregular batch of the forward stage tests (tests/_fwd_ref.py: nodes whose edges span three
+    tiles, fill exactly one / two, tiles of 1 ... 25 segments, isolated nodes, graphs without edges, duplicates, self loops), repeated
+    until the persistent form is chosen."""
     props = torch.cuda.get_device_properties(0)
+    if graph == "irregular":
+        from tests import _fwd_ref
+        b = _fwd_ref.irregular_batch(128)
+        _fwd_ref.assert_features(b, 128)
+        reps = 2 * props.multi_processor_count * 128 // (b.E * (wx // 512)) + 2
+        sizes, E = b.sizes * reps, b.E * reps
+        ei_irregular = torch.cat([torch.stack((b.dst, b.src)) + r * b.N for r in range(reps)], 1)
+    else:
+        sizes = [61, 64, 1, 57, 64, 33, 64, 64, 50, 64, 64, 63, 64, 17, 64, 64, 64, 59, 64, 64, 64, 64, 2, 64, 64, 64, 64, 64, 64, 64] * (1 if wx == 1024 else 2)
+        E = sum(n * (n - 1) for n in sizes)
     assert (E + 127) // 128 * (wx // 512) > 2 * props.multi_processor_count, "the batch must be large enough for the persistent form"
     H = 36
     d = dims_for(H, 256, wx, wx, 128)
@@ -750,7 +763,7 @@ def test_persistent_coordinate_kernel_is_bitwise_the_per_tile_kernel(precision, 
     n = sum(sizes)
     g = torch.Generator().manual_seed(4)
     h, x = torch.randn(n, H, generator=g).to(DEV), torch.randn(n, 3, generator=g).to(DEV)
-    ei = dma.fully_connected_edge_index(sizes, device=DEV)
+    ei = ei_irregular.to(DEV) if graph == "irregular" else dma.fully_connected_edge_index(sizes, device=DEV)
     batch = torch.repeat_interleave(torch.arange(len(sizes)), torch.tensor(sizes)).to(DEV)
     net = build_net(sd, d, 2, precision=precision, norm_scope="graph")
     out = {}

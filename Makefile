@@ -8,10 +8,10 @@ HDRS  := $(CSRC)/edge_f16c8w_mphase2.inc $(CSRC)/edge_f16c8w_mphasek.inc $(CSRC)
 # -fvisibility=hidden: the library exports exactly the functions include/egnn_amd.h declares (the header wraps its
 # declarations in a visibility push(default)); tests/test_cabi_and_host.py compares the two sets
 FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -ffp-contract=off -fno-slp-vectorize -fvisibility=hidden
-# host_logic.cpp, eval/assign_host.cpp: the HIP-free part of the host side (validation, schedule builder, plans); plain C++ for
-# both builds
-HOSTSRC := $(CSRC)/host_logic.cpp $(CSRC)/eval/assign_host.cpp
-HOSTHDR := $(CSRC)/host_logic.h $(CSRC)/eval/assign_host.h include/egnn_amd.h
+# host_logic.cpp, eval/assign_host.cpp, eval/kabsch_host.cpp: the HIP-free part of the host side (validation, schedule builder,
+# plans, the host statement of the Kabsch gradient); plain C++ for both builds
+HOSTSRC := $(CSRC)/host_logic.cpp $(CSRC)/eval/assign_host.cpp $(CSRC)/eval/kabsch_host.cpp
+HOSTHDR := $(CSRC)/host_logic.h $(CSRC)/eval/assign_host.h $(CSRC)/eval/kabsch_math.h include/egnn_amd.h
 HOSTOBJ := $(HOSTSRC:.cpp=.o)
 ASAN_OUT := build/libegnn_host_asan.so
 

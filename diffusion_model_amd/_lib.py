@@ -88,7 +88,7 @@ class OptimConsts(C.Structure):
                                                "adaptive_y_lr", "lr")] + [("rectified", C.c_int32)]
 
 
-_pp, _i64p = C.POINTER(C.c_void_p), C.POINTER(C.c_int64)
+_pp, _i64p, _dp = C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 
 # name -> (restype, argtypes); kept in one table so tests can check every header symbol is exported
 SIGNATURES = {
@@ -146,6 +146,9 @@ SIGNATURES = {
     "egnn_rdf": (_i, [_vp, _i, _vp, _vp, C.c_double, C.c_double, _f, _i, _i, _vp]),
     "egnn_si_o_si": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _vp]),
     "egnn_kabsch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "egnn_kabsch_ordered": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "egnn_kabsch_backward": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "egnn_kabsch_grad_host": (_i, [_i, _dp, _dp, _i, _i, _dp, _dp, C.c_double, _dp, _dp]),
     "egnn_kabsch_perm_workspace_bytes": (C.c_size_t, [_i, _i]),
     "egnn_kabsch_perm": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
     "egnn_assign": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),

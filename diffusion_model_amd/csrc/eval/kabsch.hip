@@ -6,6 +6,11 @@
 //    fp64 (the data are tiny, as in rdf_kernel); the 3x3 part is kabsch_math.h.  The RMSD is the RESIDUAL
 //    sqrt(sum |R p - q|^2 / n), never E0 - 2 sum(sigma), which cancels for good fits.  The same launch counts the rows equal to
 //    one-hot O = [1, 0, ...] of the original and the generated atom types (def_for_main.py:103-111).
+//  * kabsch_backward_kernel: the gradient of (R, t, rmsd) with respect to P and Q, so that the RMSD can be a loss term
+//    (train_2024_11.py:233-236).  One wavefront per graph again.  Nothing is kept from the forward (a 64-atom pair is 768 B):
+//    centres, H, the factors of the fit and the residual are recomputed in fp64 by the forward's own routine, a second
+//    lane-strided pass reduces sum e_i p_i^T, sum p and sum q, the 3x3 part is kabsch_fit_backward_factors (kabsch_math.h), and a
+//    third pass writes every row of dP and dQ as fp32.  Butterfly sums only, no atomics: bitwise reproducible.
 //  * kabsch_perm_search_kernel + kabsch_perm_final_kernel: minimum over all orderings [0] + perm(1..n-1) of the generated
 //    structure of the atom-0-anchored, row-flip RMSD (evaluate_rmsd.py:93-107).  Atom 0 is the centre and stays put, so
 //    sum |p|^2 + sum |q|^2 is the same for every ordering and arg min RMSD = arg max of the optimal proper rotation's trace
@@ -34,9 +39,16 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // Kabsch fit of n atom pairs by one wavefront: P row order[i] (order == nullptr: row i) against Q row i.
-// All lanes return the same R [9], t [3] = c_Q - c_P and rmsd.
-__device__ void kabsch_wave(const float* __restrict__ P, const float* __restrict__ Q, const int* order, int n, int center,
-                            int flip, int lane, double* R, double* t, double& rmsd) {
+// All lanes return the same R [9], t [3] = c_Q - c_P and rmsd; the backward also takes the centres and the factors of the fit.
+struct KabschWaveFit {
+  double cp[3], cq[3];
+  KabschFactors F;
+};
+
+template <bool kKeep>
+__device__ __forceinline__ void kabsch_wave_fit(const float* __restrict__ P, const float* __restrict__ Q, const int* order, int n,
+                                                int center, int flip, int lane, double* R, double* t, double& rmsd,
+                                                KabschWaveFit* keep) {
   double cp[3] = {0.0, 0.0, 0.0}, cq[3] = {0.0, 0.0, 0.0};
   if (center == kKabschCentroid) {
     for (int i = lane; i < n; i += 64) {
@@ -57,7 +69,12 @@ __device__ void kabsch_wave(const float* __restrict__ P, const float* __restrict
       for (int c = 0; c < 3; ++c) H[3 * r + c] += p[r] * q[c];
   }
   for (int k = 0; k < 9; ++k) H[k] = wave_sum(H[k]);
-  kabsch_fit(H, flip, R);
+  if (kKeep) {
+    kabsch_fit_factors(H, flip, R, keep->F);
+    for (int d = 0; d < 3; ++d) { keep->cp[d] = cp[d]; keep->cq[d] = cq[d]; }
+  } else {
+    kabsch_fit(H, flip, R);
+  }
   double res = 0.0;
   for (int i = lane; i < n; i += 64) {
     const int ip = order ? order[i] : i;
@@ -72,10 +89,28 @@ __device__ void kabsch_wave(const float* __restrict__ P, const float* __restrict
   for (int d = 0; d < 3; ++d) t[d] = cq[d] - cp[d];
 }
 
+__device__ void kabsch_wave(const float* __restrict__ P, const float* __restrict__ Q, const int* order, int n, int center,
+                            int flip, int lane, double* R, double* t, double& rmsd) {
+  kabsch_wave_fit<false>(P, Q, order, n, center, flip, lane, R, t, rmsd, nullptr);
+}
+
+// The ordering of one graph as the kernels take it: `order` + lo (local indices: row i of the fit is row order[i] of P), or
+// nullptr -- the identity -- without an order or where an entry lies outside [0, n).  This guards ADDRESSES only (no such index
+// is ever used as one); it does not make an ordering valid: the caller passes a permutation of every graph's rows (an in-range
+// ordering with repeated indices is fitted as it stands, and the lanes that share a dP row then write it in no defined order).
+__device__ __forceinline__ const int* graph_order(const int* __restrict__ order, int lo, int n, int lane) {
+  if (!order) return nullptr;
+  int bad = 0;
+  for (int i = lane; i < n; i += 64) bad |= (unsigned)order[lo + i] >= (unsigned)n;
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) bad |= __shfl_xor(bad, m, 64);
+  return bad ? nullptr : order + lo;
+}
+
 __global__ __launch_bounds__(64) void kabsch_kernel(const float* __restrict__ P, const float* __restrict__ Q,
-                                                    const int* __restrict__ graph_ptr, int center, int flip,
-                                                    const int* __restrict__ x_p, const int* __restrict__ x_q, int A,
-                                                    float* __restrict__ out) {
+                                                    const int* __restrict__ graph_ptr, const int* __restrict__ order,
+                                                    int center, int flip, const int* __restrict__ x_p,
+                                                    const int* __restrict__ x_q, int A, float* __restrict__ out) {
   const int g = blockIdx.x, lane = threadIdx.x, lo = graph_ptr[g], n = graph_ptr[g + 1] - lo;
   float* o = out + (size_t)g * kKabschOutStride;
   if (n < 1) {
@@ -83,7 +118,7 @@ __global__ __launch_bounds__(64) void kabsch_kernel(const float* __restrict__ P,
     return;
   }
   double R[9], t[3], rmsd;
-  kabsch_wave(P + 3 * (size_t)lo, Q + 3 * (size_t)lo, nullptr, n, center, flip, lane, R, t, rmsd);
+  kabsch_wave(P + 3 * (size_t)lo, Q + 3 * (size_t)lo, graph_order(order, lo, n, lane), n, center, flip, lane, R, t, rmsd);
   int cnt_p = 0, cnt_q = 0;
   if (x_p && x_q) {
     for (int i = lane; i < n; i += 64) {
@@ -106,6 +141,75 @@ __global__ __launch_bounds__(64) void kabsch_kernel(const float* __restrict__ P,
     o[13] = (float)cnt_p;
     o[14] = (float)cnt_q;
     o[15] = 0.f;
+  }
+}
+
+// gout [B,16] in the forward's layout: dL/dR [9], dL/dt [3], dL/drmsd (the rest is not read).  With p, q the centred rows,
+// e_i = R p_i - q_i and c = g_rmsd / (n rmsd) (0 where rmsd = 0):
+//   Rbar = g_R + c sum e_i p_i^T,  Hbar = kabsch_fit_backward(Rbar),  pbar_i = c R^T e_i + Hbar q_i,  qbar_i = -c e_i + Hbar^T p_i,
+//   centroid:  dP_i = pbar_i - (sum pbar + g_t) / n,  dQ_i = qbar_i - (sum qbar - g_t) / n
+//   first:     dP_i = pbar_i, dQ_i = qbar_i, and row 0 takes -(sum pbar + g_t), -(sum qbar - g_t)
+// Every row of the graph is written (dP row i at row order[i]); one-atom graphs get zeros.
+__global__ __launch_bounds__(64) void kabsch_backward_kernel(const float* __restrict__ P, const float* __restrict__ Q,
+                                                             const int* __restrict__ graph_ptr, const int* __restrict__ order,
+                                                             int center, int flip, const float* __restrict__ gout,
+                                                             float* __restrict__ dP, float* __restrict__ dQ) {
+  const int g = blockIdx.x, lane = threadIdx.x, lo = graph_ptr[g], n = graph_ptr[g + 1] - lo;
+  if (n < 1) return;
+  const float* Pg = P + 3 * (size_t)lo;
+  const float* Qg = Q + 3 * (size_t)lo;
+  float* dPg = dP + 3 * (size_t)lo;
+  float* dQg = dQ ? dQ + 3 * (size_t)lo : nullptr;
+  if (n == 1) {
+    if (lane < 3) {
+      dPg[lane] = 0.f;
+      if (dQg) dQg[lane] = 0.f;
+    }
+    return;
+  }
+  const int* ord = graph_order(order, lo, n, lane);
+  double R[9], t[3], rmsd;
+  KabschWaveFit fit;
+  kabsch_wave_fit<true>(Pg, Qg, ord, n, center, flip, lane, R, t, rmsd, &fit);
+  double E[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, sp[3] = {0.0, 0.0, 0.0}, sq[3] = {0.0, 0.0, 0.0};
+  for (int i = lane; i < n; i += 64) {
+    const int ip = ord ? ord[i] : i;
+    double p[3], q[3];
+    for (int d = 0; d < 3; ++d) { p[d] = (double)Pg[3 * ip + d] - fit.cp[d]; q[d] = (double)Qg[3 * i + d] - fit.cq[d]; }
+    for (int r = 0; r < 3; ++r) {
+      const double e = (R[3 * r] * p[0] + R[3 * r + 1] * p[1] + R[3 * r + 2] * p[2]) - q[r];
+      for (int c = 0; c < 3; ++c) E[3 * r + c] += e * p[c];
+      sp[r] += p[r];
+      sq[r] += q[r];
+    }
+  }
+  for (int k = 0; k < 9; ++k) E[k] = wave_sum(E[k]);
+  for (int d = 0; d < 3; ++d) { sp[d] = wave_sum(sp[d]); sq[d] = wave_sum(sq[d]); }
+  const float* go = gout + (size_t)g * kKabschOutStride;
+  const double c = rmsd > 0.0 ? (double)go[12] / ((double)n * rmsd) : 0.0;
+  double Rbar[9], Hbar[9];
+  for (int k = 0; k < 9; ++k) Rbar[k] = (double)go[k] + c * E[k];
+  kabsch_fit_backward_factors(fit.F, Rbar, Hbar);
+  double se[3], mp[3], mq[3];
+  for (int r = 0; r < 3; ++r) se[r] = (R[3 * r] * sp[0] + R[3 * r + 1] * sp[1] + R[3 * r + 2] * sp[2]) - sq[r];
+  for (int d = 0; d < 3; ++d) {
+    const double gt = (double)go[9 + d];
+    mp[d] = c * (R[d] * se[0] + R[3 + d] * se[1] + R[6 + d] * se[2]) + (Hbar[3 * d] * sq[0] + Hbar[3 * d + 1] * sq[1] + Hbar[3 * d + 2] * sq[2]) + gt;
+    mq[d] = -c * se[d] + (Hbar[d] * sp[0] + Hbar[3 + d] * sp[1] + Hbar[6 + d] * sp[2]) - gt;
+    if (center == kKabschCentroid) { mp[d] /= (double)n; mq[d] /= (double)n; }
+  }
+  for (int i = lane; i < n; i += 64) {
+    const int ip = ord ? ord[i] : i;
+    double p[3], q[3], e[3];
+    for (int d = 0; d < 3; ++d) { p[d] = (double)Pg[3 * ip + d] - fit.cp[d]; q[d] = (double)Qg[3 * i + d] - fit.cq[d]; }
+    for (int r = 0; r < 3; ++r) e[r] = (R[3 * r] * p[0] + R[3 * r + 1] * p[1] + R[3 * r + 2] * p[2]) - q[r];
+    const bool takes_mean = center == kKabschCentroid || i == 0;
+    for (int d = 0; d < 3; ++d) {
+      const double pb = c * (R[d] * e[0] + R[3 + d] * e[1] + R[6 + d] * e[2]) + (Hbar[3 * d] * q[0] + Hbar[3 * d + 1] * q[1] + Hbar[3 * d + 2] * q[2]);
+      const double qb = -c * e[d] + (Hbar[d] * p[0] + Hbar[3 + d] * p[1] + Hbar[6 + d] * p[2]);
+      dPg[3 * ip + d] = (float)(takes_mean ? pb - mp[d] : pb);
+      if (dQg) dQg[3 * i + d] = (float)(takes_mean ? qb - mq[d] : qb);
+    }
   }
 }
 
@@ -308,8 +412,34 @@ int egnn_kabsch(void* stream, int B, const float* P, const float* Q, const int32
     set_error("bad egnn_kabsch arguments");
     return EGNN_EINVAL;
   }
-  hipLaunchKernelGGL(kabsch_kernel, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), P, Q, graph_ptr, center, flip,
-                     x_p, x_q, A, out);
+  hipLaunchKernelGGL(kabsch_kernel, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), P, Q, graph_ptr,
+                     (const int32_t*)nullptr, center, flip, x_p, x_q, A, out);
+  EGNN_HIP(hipGetLastError());
+  return EGNN_OK;
+}
+
+int egnn_kabsch_ordered(void* stream, int B, const float* P, const float* Q, const int32_t* graph_ptr, const int32_t* order,
+                        int center, int flip, float* out) {
+  if (B < 1 || !P || !Q || !graph_ptr || !out || (center != EGNN_KABSCH_CENTROID && center != EGNN_KABSCH_FIRST) ||
+      (flip != EGNN_KABSCH_FLIP_ROW && flip != EGNN_KABSCH_FLIP_COLUMN)) {
+    set_error("bad egnn_kabsch_ordered arguments");
+    return EGNN_EINVAL;
+  }
+  hipLaunchKernelGGL(kabsch_kernel, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), P, Q, graph_ptr, order, center,
+                     flip, (const int32_t*)nullptr, (const int32_t*)nullptr, 0, out);
+  EGNN_HIP(hipGetLastError());
+  return EGNN_OK;
+}
+
+int egnn_kabsch_backward(void* stream, int B, const float* P, const float* Q, const int32_t* graph_ptr, const int32_t* order,
+                         int center, int flip, const float* gout, float* dP, float* dQ) {
+  if (B < 1 || !P || !Q || !graph_ptr || !gout || !dP || (center != EGNN_KABSCH_CENTROID && center != EGNN_KABSCH_FIRST) ||
+      (flip != EGNN_KABSCH_FLIP_ROW && flip != EGNN_KABSCH_FLIP_COLUMN)) {
+    set_error("bad egnn_kabsch_backward arguments");
+    return EGNN_EINVAL;
+  }
+  hipLaunchKernelGGL(kabsch_backward_kernel, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), P, Q, graph_ptr, order,
+                     center, flip, gout, dP, dQ);
   EGNN_HIP(hipGetLastError());
   return EGNN_OK;
 }

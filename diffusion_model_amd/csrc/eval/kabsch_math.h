@@ -13,6 +13,7 @@
 //    matrix, the largest root of  x^4 - 2 |H|_F^2 x^2 - 8 det(H) x + (2 tr((H^T H)^2) - |H|_F^4),  by Newton's iteration from
 //    the upper bound sqrt(3) |H|_F.  All roots are real, so the iterates fall monotonically onto the largest root: every
 //    iterate is itself an upper bound and the caller may stop as soon as one drops below the score it has to beat.
+//  * kabsch_fit_backward: the derivative of kabsch_fit, dL/dH from dL/dR, from the same factors (for the RMSD loss).
 #pragma once
 #include <math.h>
 
@@ -58,8 +59,17 @@ KABSCH_HD void kabsch_swap_cols(double* A, double* V, double* s, int i, int j) {
   }
 }
 
-// R [9] row-major such that R p_i ~ q_i
-KABSCH_HD void kabsch_fit(const double* H, int flip, double* R) {
+// The factors kabsch_fit forms on its way to R:  H = U diag(s) V^T  with V and U = [u1, u2, u1 x u2] both right-handed, s[0] >=
+// s[1] >= 0 and s[2] SIGNED (sign(det H) sigma_3), and  R = J V J U^T  with J = diag(1, 1, w3): w3 = -1 in a column-flip
+// reflection case, else 1.  H = 0 leaves s = 0, U = V = I, w3 = 1.
+struct KabschFactors {
+  double V[9], U[9];   // row-major; the singular vectors are the COLUMNS
+  double s[3];
+  double w3;
+};
+
+// R [9] row-major such that R p_i ~ q_i, and the factors it was formed from
+KABSCH_HD void kabsch_fit_factors(const double* H, int flip, double* R, KabschFactors& F) {
   double A[9], V[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
   for (int k = 0; k < 9; ++k) A[k] = H[k];
   for (int sweep = 0; sweep < 16; ++sweep) {
@@ -78,7 +88,9 @@ KABSCH_HD void kabsch_fit(const double* H, int flip, double* R) {
   if (detV < 0.0)
     for (int r = 0; r < 3; ++r) { V[3 * r + 2] = -V[3 * r + 2]; A[3 * r + 2] = -A[3 * r + 2]; }
   if (!(s[0] > 0.0)) {   // H = 0: nothing to align
-    for (int k = 0; k < 9; ++k) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    for (int k = 0; k < 9; ++k) R[k] = F.V[k] = F.U[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    F.s[0] = F.s[1] = F.s[2] = 0.0;
+    F.w3 = 1.0;
     return;
   }
   double u1[3], u2[3], u3[3];
@@ -103,6 +115,54 @@ KABSCH_HD void kabsch_fit(const double* H, int flip, double* R) {
     for (int c = 0; c < 3; ++c) R[3 * r + c] = V[3 * r] * u1[c] + V[3 * r + 1] * u2[c] + w3 * (V[3 * r + 2] * u3[c]);
   if (reflect_column)
     for (int c = 0; c < 3; ++c) R[6 + c] = -R[6 + c];
+  for (int k = 0; k < 9; ++k) F.V[k] = V[k];
+  for (int r = 0; r < 3; ++r) { F.U[3 * r] = u1[r]; F.U[3 * r + 1] = u2[r]; F.U[3 * r + 2] = u3[r]; }
+  F.s[0] = s[0]; F.s[1] = s[1]; F.s[2] = s3;
+  F.w3 = w3;
+}
+
+// R [9] row-major such that R p_i ~ q_i
+KABSCH_HD void kabsch_fit(const double* H, int flip, double* R) {
+  KabschFactors F;
+  kabsch_fit_factors(H, flip, R, F);
+}
+
+// Hbar = dL/dH [9] of L(R(H)) from Rbar = dL/dR [9].  With dU = U Wu, dV = V Wv (Wu, Wv antisymmetric) and dA = U^T dH V,
+//   dA_ij = Wu_ij s_j - s_i Wv_ij  (i != j),   dR = J V (Wv J - J Wu) U^T,
+// which solved for (Wv J - J Wu)_ij = a_ij dA_ij + b_ij dA_ji gives, with K = V^T J Rbar U and j = diag(J),
+//   Abar_ij = -K_ij / (j_j s_i + j_i s_j) + K_ji / (j_i s_i + j_j s_j),   Abar_ii = 0,   Hbar = U Abar V^T.
+// No 1 / (s_i^2 - s_j^2): the denominators are s_i + s_j, which with the signed s[2] is sigma_i - sigma_3 in a row-flip reflection
+// case.  A term whose denominator is at most 1e-12 s[0] in magnitude is dropped (kabsch_fit's rank threshold: the forward
+// completes that direction by a fixed rule, which is locally constant), so the result is finite for every H.
+KABSCH_HD void kabsch_fit_backward_factors(const KabschFactors& F, const double* Rbar, double* Hbar) {
+  const double j[3] = {1.0, 1.0, F.w3};
+  double T[9], K[9], M[9];
+  for (int i = 0; i < 3; ++i)     // T = V^T J Rbar
+    for (int c = 0; c < 3; ++c) T[3 * i + c] = F.V[i] * Rbar[c] + F.V[3 + i] * Rbar[3 + c] + F.w3 * (F.V[6 + i] * Rbar[6 + c]);
+  for (int i = 0; i < 3; ++i)
+    for (int k = 0; k < 3; ++k) K[3 * i + k] = T[3 * i] * F.U[k] + T[3 * i + 1] * F.U[3 + k] + T[3 * i + 2] * F.U[6 + k];
+  const double tiny = 1e-12 * F.s[0];
+  for (int i = 0; i < 3; ++i)
+    for (int k = 0; k < 3; ++k) {
+      double m = 0.0;
+      if (i != k) {
+        const double den1 = j[k] * F.s[i] + j[i] * F.s[k], den2 = j[i] * F.s[i] + j[k] * F.s[k];
+        if (fabs(den1) > tiny) m -= K[3 * i + k] / den1;
+        if (fabs(den2) > tiny) m += K[3 * k + i] / den2;
+      }
+      M[3 * i + k] = m;
+    }
+  for (int r = 0; r < 3; ++r)     // T = U Abar
+    for (int k = 0; k < 3; ++k) T[3 * r + k] = F.U[3 * r] * M[k] + F.U[3 * r + 1] * M[3 + k] + F.U[3 * r + 2] * M[6 + k];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) Hbar[3 * r + c] = T[3 * r] * F.V[3 * c] + T[3 * r + 1] * F.V[3 * c + 1] + T[3 * r + 2] * F.V[3 * c + 2];
+}
+
+KABSCH_HD void kabsch_fit_backward(const double* H, int flip, const double* Rbar, double* Hbar) {
+  double R[9];
+  KabschFactors F;
+  kabsch_fit_factors(H, flip, R, F);
+  kabsch_fit_backward_factors(F, Rbar, Hbar);
 }
 
 // -> the largest eigenvalue of Horn's matrix of H, or -1 as soon as an iterate (an upper bound of it) is below `beat`

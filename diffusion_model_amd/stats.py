@@ -130,13 +130,54 @@ def _kabsch_launch(P, Q, gp, B, center, flip, x_p=None, x_q=None):
     return out
 
 
+class _KabschFit(torch.autograd.Function):
+    """(P, Q) float32 [N,3] -> the forward's [B,16] block (R [9], t [3], rmsd, ...), differentiable with respect to P and Q: one
+    launch forward (egnn_kabsch, or egnn_kabsch_ordered with an ordering), one launch backward (egnn_kabsch_backward), which
+    recomputes the fit from P and Q.  The slices the caller takes of the block hand back zeros for the outputs it does not use."""
+
+    @staticmethod
+    def forward(ctx, P, Q, gp, B, center, flip, order):
+        if order is None:
+            out = _kabsch_launch(P, Q, gp, B, center, flip)
+        else:
+            out = torch.empty(B, 16, device=P.device)
+            _lib.check(_lib.lib().egnn_kabsch_ordered(_lib.stream_ptr(), B, _lib.ptr(P), _lib.ptr(Q), _lib.ptr(gp), _lib.ptr(order),
+                                                      _lib.KABSCH_CENTERS[center], _lib.KABSCH_FLIPS[flip], _lib.ptr(out)))
+        ctx.save_for_backward(P, Q, gp)
+        ctx.order, ctx.B, ctx.center, ctx.flip = order, B, center, flip
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        P, Q, gp = ctx.saved_tensors
+        gout = gout.to(torch.float32).contiguous()
+        # the kernel always writes dP (it has no path without it), also where only Q requires grad; every row is written, except
+        # under an ordering that is no permutation, so those buffers start at zero
+        dP = torch.empty_like(P) if ctx.order is None else torch.zeros_like(P)
+        dQ = torch.empty_like(Q) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.lib().egnn_kabsch_backward(_lib.stream_ptr(), ctx.B, _lib.ptr(P), _lib.ptr(Q), _lib.ptr(gp), _lib.ptr(ctx.order),
+                                                   _lib.KABSCH_CENTERS[ctx.center], _lib.KABSCH_FLIPS[ctx.flip], _lib.ptr(gout),
+                                                   _lib.ptr(dP), _lib.ptr(dQ)))
+        return (dP if ctx.needs_input_grad[0] else None), dQ, None, None, None, None, None
+
+
+def _kabsch_differentiable(P, Q, gp, B, center, flip, order=None):
+    if center not in _lib.KABSCH_CENTERS or flip not in _lib.KABSCH_FLIPS:
+        raise ValueError("center must be 'centroid' or 'first', flip 'row' or 'column'")
+    return _KabschFit.apply(P.to(torch.float32).contiguous(), Q.to(torch.float32).contiguous(), gp, B, center, flip, order)
+
+
 def kabsch(P: torch.Tensor, Q: torch.Tensor, sizes: Sequence[int] | None = None, center="centroid", flip="column"):
     """Kabsch fit of P onto Q -> (R, t, rmsd) with R p_i ~ q_i, for one graph ([n,3] -> [3,3], [3], 0-dim) or a batch of
     graphs (``sizes`` given: [N,3] -> [B,3,3], [B,3], [B]) in one launch.  The defaults are kabsch_torch of
     evaluate_rmsd_for_pos_generate.py:11-51, which parts/def_for_main.py:82,101 call; (center, flip) = ('centroid', 'row') is
     kabsch_numpy of the same file (:53-92) and ('first', 'row') kabsch_numpy of evaluate_rmsd.py:10-42 (t = Q[0] - P[0], which
     that spelling does not return).  'row' is the optimal proper rotation; 'column' reproduces the reference's non-optimal
-    reflection fix.  Where p^T q is rank deficient both return the optimal proper rotation (include/egnn_amd.h)."""
+    reflection fix.  Where p^T q is rank deficient both return the optimal proper rotation (include/egnn_amd.h).
+    Like the reference's kabsch_torch, the fit is differentiable: where P or Q requires grad all three outputs carry gradients
+    to both (one more launch in backward; egnn_kabsch_backward of include/egnn_amd.h says what it returns where autograd through
+    an SVD would return NaN)."""
     if not (P.is_cuda and Q.is_cuda):
         raise RuntimeError("kabsch needs CUDA(ROCm) tensors; there is no CPU fallback")
     if P.shape != Q.shape:
@@ -147,9 +188,52 @@ def kabsch(P: torch.Tensor, Q: torch.Tensor, sizes: Sequence[int] | None = None,
     gp, B, N = _graph_ptr(sizes, P.device)
     if P.shape != (N, 3):
         raise ValueError("P and Q must be [sum(sizes), 3]")
-    out = _kabsch_launch(P.detach().to(torch.float32).contiguous(), Q.detach().to(torch.float32).contiguous(), gp, B, center, flip)
+    if torch.is_grad_enabled() and (P.requires_grad or Q.requires_grad):
+        out = _kabsch_differentiable(P, Q, gp, B, center, flip)
+    else:
+        out = _kabsch_launch(P.detach().to(torch.float32).contiguous(), Q.detach().to(torch.float32).contiguous(), gp, B, center, flip)
     R, t, rmsd = out[:, :9].reshape(B, 3, 3), out[:, 9:12], out[:, 12]
     return (R[0], t[0], rmsd[0]) if single else (R, t, rmsd)
+
+
+def rmsd_loss(P: torch.Tensor, Q: torch.Tensor, sizes: Sequence[int], center="centroid", flip="column", order=None,
+              reduction="mean", searched=None):
+    """The structural RMSD of a batch as a loss term: the batch form of train_2024_11.py:233-235 (`_, _, loss_coords =
+    kabsch_torch(pos_to_gen, pos)` per graph, summed, divided by num_graph).  P (e.g. the model's output) is fitted onto Q per
+    graph in one launch, backward is one launch; gradients flow to P and to Q where they require grad.  reduction 'mean' divides
+    the sum by the number of graphs, 'sum' does not, 'none' returns the RMSDs [B].  ``order`` (int32 [N], indices local to each
+    graph, as kabsch_min_over_permutations and linear_assignment return them: row order[i] of a graph's P is paired with row i
+    of its Q) is a constant of the loss and must be a permutation of every graph's rows.  Those two functions leave the rows of
+    graphs they did not search / solve UNWRITTEN: pass their third or fourth result (bool [B]) as ``searched`` and such graphs are
+    taken in identity order, or fill the identity there yourself.  The kernels never use an entry outside [0, n) as an address (a
+    graph that holds one is fitted in identity order), but that guards memory only: an in-range ordering that is no permutation
+    (all zeros, say) is fitted as it stands, and its gradient rows are unspecified."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError("reduction must be 'mean', 'sum' or 'none'")
+    if not (P.is_cuda and Q.is_cuda):
+        raise RuntimeError("rmsd_loss needs CUDA(ROCm) tensors; there is no CPU fallback")
+    if P.shape != Q.shape or P.device != Q.device:
+        raise ValueError("Matrix dimensions (and devices) must match")
+    gp, B, N = _graph_ptr(sizes, P.device)
+    if P.shape != (N, 3):
+        raise ValueError("P and Q must be [sum(sizes), 3]")
+    if B < 1:
+        raise ValueError("rmsd_loss needs at least one graph")
+    if order is not None:
+        if not (torch.is_tensor(order) and order.device == P.device and order.shape == (N,) and not order.dtype.is_floating_point):
+            raise ValueError("order must be an integer tensor [sum(sizes)] on the device of P")
+        order = order.detach().to(torch.int32)
+        if searched is not None:
+            if not (torch.is_tensor(searched) and searched.device == P.device and searched.shape == (B,)):
+                raise ValueError("searched must be a bool tensor [len(sizes)] on the device of P")
+            gid = torch.repeat_interleave(torch.arange(B, device=P.device), gp[1:].long() - gp[:-1].long(), output_size=N)
+            local = torch.arange(N, device=P.device, dtype=torch.int32) - gp[:-1][gid]
+            order = torch.where(searched.bool()[gid], order, local)
+        order = order.contiguous()
+    elif searched is not None:
+        raise ValueError("searched goes with order")
+    rmsd = _kabsch_differentiable(P, Q, gp, B, center, flip, order)[:, 12]
+    return rmsd if reduction == "none" else (rmsd.sum() / B if reduction == "mean" else rmsd.sum())
 
 
 def _collate_pairs(original_graph_list, generated_graph_list, with_types):

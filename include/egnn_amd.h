@@ -393,6 +393,28 @@ enum { EGNN_KABSCH_CENTROID = 0, EGNN_KABSCH_FIRST = 1 };
 enum { EGNN_KABSCH_FLIP_ROW = 0, EGNN_KABSCH_FLIP_COLUMN = 1 };
 int egnn_kabsch(void* stream, int B, const float* d_P, const float* d_Q, const int32_t* d_graph_ptr, int center, int flip,
                 const int32_t* d_x_p, const int32_t* d_x_q, int A, float* d_out);
+/* The same fit after a reordering of P: row i of a graph's fit is row d_order[lo + i] of its P (d_order int32 [N], indices local
+ * to the graph: the form in which egnn_kabsch_perm returns an ordering and egnn_assign a matching); d_order NULL is the
+ * identity.  The caller passes a permutation of every graph's rows; egnn_kabsch_perm and egnn_assign leave the rows of graphs
+ * they did not search / solve unwritten, so the identity has to be filled in there.  As a guard of ADDRESSES only, a graph whose
+ * ordering holds an index outside [0, n) is fitted in identity order (no such index is used as an address); an in-range ordering
+ * that is no permutation is fitted as it stands.  No atom-type counts: d_out[13..15] = 0. */
+int egnn_kabsch_ordered(void* stream, int B, const float* d_P, const float* d_Q, const int32_t* d_graph_ptr,
+                        const int32_t* d_order, int center, int flip, float* d_out);
+/* Gradient of egnn_kabsch / egnn_kabsch_ordered with respect to P and Q, so that the RMSD (train_2024_11.py:233-236) or any
+ * function of (R, t, rmsd) can be a loss term: one launch, one wavefront per graph, fp64 inside, nothing kept from the forward
+ * (centres, H, the fit and the residual are recomputed), no atomics, bitwise reproducible.  d_gout float[B,16] in the forward's
+ * layout: dL/dR [9], dL/dt [3], dL/drmsd; the rest is not read.  d_dP float[N,3] and d_dQ float[N,3] (or NULL) are fully written
+ * for every graph with n >= 1 (the d_dP row of fit row i is row d_order[lo + i]; a d_order with repeated indices leaves rows
+ * unwritten and the repeated rows unspecified).  Defined where autograd through an SVD returns NaN or inf: rmsd = 0 contributes no rmsd gradient; a pair of
+ * singular values whose sum (difference, in a FLIP_ROW reflection case) is at most 1e-12 sigma_1 contributes nothing (the
+ * forward completes such directions by a fixed rule); one-atom graphs get zeros. */
+int egnn_kabsch_backward(void* stream, int B, const float* d_P, const float* d_Q, const int32_t* d_graph_ptr,
+                         const int32_t* d_order, int center, int flip, const float* d_gout, float* d_dP, float* d_dQ);
+/* Host statement of egnn_kabsch_backward for ONE pair, everything in double, HOST pointers, no GPU: the same 3x3 numerics
+ * (csrc/eval/kabsch_math.h) in plain C++.  P, Q [n,3]; g_R [9] and g_t [3] may be NULL (zero); dP [n,3]; dQ [n,3] or NULL. */
+int egnn_kabsch_grad_host(int n, const double* P, const double* Q, int center, int flip, const double* g_R, const double* g_t,
+                          double g_rmsd, double* dP, double* dQ);
 /* Correspondence search of evaluate_rmsd.py:93-107: per graph with 2 <= n <= max_atoms (max_atoms <= 12) the minimum over all
  * orderings [0] + perm(1..n-1) of the rows of P (the generated structure) of the FIRST + FLIP_ROW RMSD against Q (the original).
  * Orderings are ranked in fp64 by the trace of their optimal proper rotation (atom 0 is the centre of every ordering, so this

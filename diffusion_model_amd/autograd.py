@@ -1,23 +1,32 @@
 """Differentiable EGNN forward for training.
 
-Forward: the fused HIP kernels (same call as inference); per layer the inputs (h_l, x_l) and the three segment
-sums the edge pass produced (egcl_read_aggregates) are kept.  Backward, per layer in reverse order:
+Forward: the fused HIP kernels (same call as inference); per layer the inputs (h_l, x_l) and the three segment sums the edge
+pass produced (egcl_read_aggregates) are kept.  decide_keep() settles once per shape whether the forward also keeps the edge
+activations (egcl_forward_save: the first-layer activations and the second-layer pre-activations of every edge, 7 GB per
+layer at 2^20 edges), so that the backward has no recompute pass.
 
-  node part  (N rows, small): h' = mlp_h([h | sum_m]), x' = x + sum_x / (G + 1), G = sqrt(sum d^2) -- differentiated
-             with torch ops on the saved sums; yields the gradients of the three segment sums.
-  edge part  (E rows, the cost): recomputed in edge chunks as the chain
-             egcl_backward_gather_in, egcl_backward_l1_act -> GEMM -> egcl_backward_heads -> GEMM, GEMM ->
-             egcl_backward_l1_grad -> GEMM, GEMM -> egcl_backward_scatter
-             where the stage functions are HIP kernels of the C ABI (gathers, SiLU and SiLU', scalar heads, gate,
-             row reductions, bias / w3 / wa column sums, in place on the GEMM buffers) and the GEMMs are the plain
-             dgrad / wgrad products of the four Linear layers, run by the BLAS library through torch.mm.
-             bf16 mode stores the [edges, W] buffers and runs the GEMMs in bf16 (fp32 accumulate, fp32 master
-             gradients); fp32 mode is fp32 end to end.
-             bf16 at the reference widths: the recompute half runs on the forward's own MFMA edge kernels
-             (egcl_backward_edge_recompute) and the dgrad half on egcl_backward_dgrad; and when HBM allows (default), the
-             forward runs as egcl_forward_save, which keeps the first-layer activations and the second-layer
-             pre-activations of every edge (7 GB per layer at 2^20 edges), so that the backward has NO recompute pass:
-             egcl_backward_heads_saved turns the kept pre-activations into dL/da2 in place at HBM speed.
+Backward: plan_backward() turns the precision, the widths, the graph and the switches (_switches(), the only reader of the
+environment; table in INTEGRATION.md) into ONE BackwardPlan at the top of the call; everything below follows that record and
+decides nothing.  Per layer, in reverse order:
+
+  node part  (N rows, small): x' = x + sum_x / (G + 1), G = sqrt(sum d^2), differentiated by torch (_coordinate_update), and
+             h' = mlp_h([h | sum_m]) in the plan's node form: "hip" (the library's own GEMM kernels, bf16 operands: bf16 / fp16
+             at the reference widths), "split" (head + remainder products on the same kernels: bf16x3 / f16c8, or EGNN_BWD_OWN=1)
+             or "torch" (exact fp32 products of the BLAS library: fp32, and every shape the own kernels do not tile).
+  edge part  (E rows, the cost): _edge_setup, then per chunk of edges four stages, each in the variant _stages() picks:
+               dL/da2   second-layer pre-activations -> dL/da2 in place, g_diff and the bias / w3 / wa column sums
+                        kept: egcl_backward_heads_saved on the kept buffers (default for bf16 when HBM allows) | fused:
+                        egcl_backward_edge_recompute on the forward's MFMA edge kernels | chain: l1_act, product, heads
+               w2       second-layer weight gradients: gemm_tn (own split-K kernel) | library products (_wgrad)
+               dL/da1   first == "graph": egcl_backward_dgrad_reduce, the first layers' per-node sums taken in the dgrad kernel's
+                        epilogue, dL/da1 never written (default for graphs of at most 64 nodes) | fused: egcl_backward_dgrad |
+                        chain: products, l1_grad
+               first    first-layer gradients and the scatter to dL/dh, dL/dx: factorised (first == "reduce": one extra pass,
+                        egcl_backward_first_reduce, the reference form; then scatter_geom for both forms) | gather + gemm_tn x 2
+                        + gemm_rows + scatter | gather + library products + scatter
+             and _edge_finish: the node-level products of the factorised forms and the hand-over of the parameter gradients.
+             bf16 storage keeps the [edges, W] buffers and runs the products in bf16 (fp32 accumulate, fp32 master gradients);
+             fp32 storage is fp32 end to end.  fp16 forwards take the bf16 backward, bf16x3 / f16c8 the fp32 one.
 
 Math (reference EquivariantGraphNeuralNetwork.py:55-71), per edge e = (i <- j):
   in = [h_i | h_j | d2],  d2 = |x_i - x_j|^2
@@ -26,59 +35,94 @@ Math (reference EquivariantGraphNeuralNetwork.py:55-71), per edge e = (i <- j):
 """
 from __future__ import annotations
 
+import bisect
 import math
 import os
+from dataclasses import InitVar, dataclass
+from functools import partial
+from types import SimpleNamespace
 
 import torch
 
 from . import _lib
 
-EDGE_CHUNK = int(os.environ.get("EGNN_BWD_CHUNK", 1 << 20))   # edges per backward chunk (workspace = up to 6 bf16 [chunk, W] buffers)
+
+def _switches(env=None):
+    """the switches of the training path as plain values (table: INTEGRATION.md); nothing else here reads the environment"""
+    g = (os.environ if env is None else env).get
+    return {"SAVE": g("EGNN_BWD_SAVE", "1") != "0", "FUSED": g("EGNN_BWD_FUSED", "1") != "0", "EDGE": int(g("EGNN_EDGE", "4")),
+            "FIRST": g("EGNN_BWD_FIRST", "0") == "1", "GRAPH": g("EGNN_BWD_GRAPH", "1") != "0",
+            "BLAS": g("EGNN_BWD_BLAS", "0") == "1", "OWN": g("EGNN_BWD_OWN", "0") == "1",
+            "CHUNK": int(g("EGNN_BWD_CHUNK", 1 << 20)), "POISON_KEPT": g("EGNN_DEBUG_POISON_KEPT", "0") == "1"}
+
+
+EDGE_CHUNK = _switches()["CHUNK"]   # edges per backward chunk (workspace = up to 6 bf16 [chunk, W] buffers); read at plan time
 
 # training.GradAllReducer.arm() puts itself here: the backward below hands it every layer's parameter gradients as soon
 # as they are final, so the bucket's all-reduce runs under the backward of the earlier layers
 ACTIVE_REDUCER = None
-LAST_FIRST_LAYER_FORM = None   # how the last edge backward took the first Linear layers: None (chain) / "graph" / "reduce" (tests)
-
-
-def _segment_scale(S, scope_graph, node_graph):
-    G = torch.sqrt(S.clamp_min(1e-30))   # graphs without edges: S = 0, zero gradient
-    c = 1.0 / (G + 1.0)
-    return c.index_select(0, node_graph).unsqueeze(1) if scope_graph else c
+LAST_PLAN = None               # the BackwardPlan of the last backward call (tests)
+LAST_FIRST_LAYER_FORM = None   # its `first` field, once an edge backward has run: None (chain) / "graph" / "reduce" (tests)
 
 
 def _round_up(v, m):
     return (v + m - 1) // m * m
 
 
-class _Workspace:
-    """[chunk, width] buffers of the edge part, allocated once per backward call"""
+@dataclass(frozen=True)
+class BackwardPlan:
+    """every decision of one backward call; combinations no stage routine exists for are rejected here"""
+    prec: int              # storage precision of the edge buffers and stage kernels: PREC_BF16 (bf16, fp16) or PREC_F32 (the rest)
+    split_products: bool   # fp32 products as head + remainder on the own kernels (gemm.mm_tn_split / mm_nn_split), not the BLAS library
+    fused: bool            # the context-handle kernels run: the forward's MFMA edge kernels recompute, egcl_backward_dgrad*
+    hip_gemms: bool        # the remaining products on gemm_tn.hip / gemm_rows.hip (widths that fit their tiles)
+    kept: bool             # the forward kept the edge activations: no recompute pass
+    first: str | None      # first Linear layers: None (chain over all edges) / "graph" / "reduce" (factorised, <= 64-node graphs)
+    rows: int              # rows of the [chunk, W] workspace buffers
+    chunks: tuple          # ((first edge, edges), ...); whole graphs in the "graph" form
+    K1P: int               # padded width of in = [h_i | h_j | d2 | 1 | 0...]: the own GEMMs' 128, else a multiple of 8
+    node: str              # node MLP form: "hip" / "split" / "torch"
+    graph_edge_ptr: InitVar[object] = None   # (checked against `chunks`, not kept)
 
-    def __init__(self, rows, H, Wx, Wm, M, dtype, device, saved_activations=False, hip_gemms=False):
-        rows = _round_up(rows, 64)
-        e = lambda *shape, dt=dtype: torch.empty(*shape, dtype=dt, device=device)
-        # [h_i | h_j | d2 | 1 | 0...]: 128 columns when the hand-written GEMMs run (their operand width), else padded to 8
-        self.hip_gemms = bool(hip_gemms)   # the decision itself: K1P == 128 also happens for H in 60..63 without it
-        self.K1P = 128 if hip_gemms else _round_up(2 * H + 2, 8)
-        self.rows, self.dtype = rows, dtype
-        if not saved_activations:   # (the saved-activation backward reads s1 / a2 from what the forward kept)
-            self.s1x, self.s1m = e(rows, Wx), e(rows, Wm)
-            self.a2x, self.a2m = e(rows, Wx), e(rows, M)
-        # dL/da1 and the gathered first-layer inputs / their gradients exist only in the forms that store them: the default
-        # 'graph' form of the first Linear layers never touches them (2 x 2 GiB + 2 x 256 MiB at 2^20 rows, W = 1024), so they
-        # are allocated on first use
-        self._lazy = {"g1x": (rows, Wx), "g1m": (rows, Wm), "inp": (rows, self.K1P), "g_in": (rows, self.K1P)}
-        self._e = e
-        self.d2 = e(rows, dt=torch.float32)
-        self.g_diff = e(rows, 3, dt=torch.float32)
+    def __post_init__(self, graph_edge_ptr):
+        cuts = set(graph_edge_ptr or ())
+        for bad, why in ((self.fused and self.prec != _lib.PREC_BF16, "the context-handle kernels are bf16 kernels"),
+                         (self.hip_gemms and not self.fused, "hip_gemms without fused"),
+                         (self.kept and not self.fused, "kept without fused"),
+                         (self.first is not None and not self.hip_gemms, "first without hip_gemms"),
+                         (self.first == "graph" and any(a not in cuts or a + n not in cuts for a, n in self.chunks),
+                          "'graph' with chunks not cut at graph boundaries"),
+                         (self.node == "hip" and not self.hip_gemms, "node form 'hip' without hip_gemms"),
+                         (self.node == "split" and not self.split_products, "node form 'split' without split_products")):
+            if bad:
+                raise ValueError(f"BackwardPlan: {why}")
 
-    def __getattr__(self, name):   # only reached for attributes not set yet
-        lazy = self.__dict__.get("_lazy", {})
-        if name in lazy:
-            t = self._e(*lazy[name])
-            setattr(self, name, t)
-            return t
-        raise AttributeError(name)
+    @property
+    def dtype(self):
+        return torch.bfloat16 if self.prec == _lib.PREC_BF16 else torch.float32
+
+
+def _keep_asked(prec, E, sw):
+    return E > 0 and prec == _lib.PREC_BF16 and sw["SAVE"] and sw["FUSED"] and sw["EDGE"] >= 4
+
+
+def decide_keep(prec, E, L, Wx, Wm, M, sw, fused_supported, free):
+    """keep the edge activations instead of recomputing them in the backward?  When the bf16 fast path runs and the buffers --
+    E x (2 Wx + Wm + M) bf16 per layer -- take less than half of the free HBM (`free`, bytes) and fit the keeping forward's
+    32-bit buffer descriptor: E x Wx x 2 B < 4 GiB"""
+    need = L * _round_up(E, 64) * (2 * Wx + Wm + M) * 2
+    return bool(_keep_asked(prec, E, sw) and fused_supported and need < 0.5 * free and E * Wx * 2 < 2 ** 32)
+
+
+def _storage_prec(prec):
+    """bf16x3 / f16c8 forward on the split-operand kernels, their backward is the fp32 chain; fp16 forwards recompute on the bf16
+    kernels (INTEGRATION.md)"""
+    return {_lib.PREC_BF16X3: _lib.PREC_F32, _lib.PREC_F16C8: _lib.PREC_F32, _lib.PREC_F16: _lib.PREC_BF16}.get(prec, prec)
+
+
+def fused_asked(prec, E, kept, sw):
+    """do the switches ask for the context-handle kernels?  (the caller then asks the library whether the widths have them)"""
+    return bool(kept or (E > 0 and _storage_prec(prec) == _lib.PREC_BF16 and sw["FUSED"]))
 
 
 def _hip_gemm_shapes(H, Wx, Wm, M):
@@ -89,7 +133,6 @@ def _hip_gemm_shapes(H, Wx, Wm, M):
 
 def _graph_chunks(plan, rows):
     """[(first edge, edges)] chunks of WHOLE graphs with at most `rows` edges each (None: a graph alone has more)"""
-    import bisect
     gep = getattr(plan, "graph_edge_ptr", None)
     if gep is None:
         return None
@@ -103,29 +146,61 @@ def _graph_chunks(plan, rows):
     return out
 
 
-_SPLIT_PRODUCTS = False   # set per backward call (see _EGNNFunction.backward)
+def plan_backward(prec, H, Wx, Wm, M, Wh, E, edge_chunk, graph_edge_ptr, max_graph_nodes, kept, fused_supported, sw):
+    """the BackwardPlan of one call.  `kept`: the forward kept the activations and they are not spent yet; `fused_supported`: the
+    library's answer (asked only when fused_asked()); `sw`: _switches()"""
+    # tolerance-grade precisions multiply through the own kernels, fp32 (parity mode) through the BLAS library unless
+    # EGNN_BWD_OWN=1; EGNN_BWD_BLAS=1 forces the BLAS library for every precision (A/B)
+    split = not sw["BLAS"] and (prec in (_lib.PREC_BF16X3, _lib.PREC_F16C8) or sw["OWN"])
+    fused = fused_asked(prec, E, kept, sw) and bool(fused_supported)
+    hip = fused and _hip_gemm_shapes(H, Wx, Wm, M)
+    rows = _round_up(min(edge_chunk, E), 64)
+    first, chunks = None, [(a, min(rows, E - a)) for a in range(0, E, rows or 1)]
+    if hip and max_graph_nodes <= 64:   # the factorised first layers: batches of graphs of at most 64 nodes
+        if sw["FIRST"]:
+            first = "reduce"
+        elif sw["GRAPH"]:
+            cut = _graph_chunks(SimpleNamespace(graph_edge_ptr=graph_edge_ptr), rows)
+            if cut is not None:         # (None: a graph with more edges than the chunk -- the chain, which may cut anywhere)
+                first, chunks = "graph", cut
+    node = "hip" if hip and Wh % 256 == 0 else "split" if split else "torch"
+    return BackwardPlan(prec=_storage_prec(prec), split_products=split, fused=fused, hip_gemms=hip, kept=bool(kept), first=first,
+                        rows=rows, chunks=tuple(chunks), K1P=128 if hip else _round_up(2 * H + 2, 8), node=node,
+                        graph_edge_ptr=graph_edge_ptr)
 
 
-def _own_fp32_products() -> bool:
-    """True while the backward of a tolerance-grade precision (bf16x3, f16c8) runs: its products go through the library's own
-    kernels as head + remainder products (gemm.mm_tn_split / mm_nn_split, 2^-16 per operand -- what those precisions' forward
-    carries) instead of through the BLAS library.  Precision fp32 keeps the exact fp32 products of torch.mm / bmm (parity mode)
-    unless EGNN_BWD_OWN=1; EGNN_BWD_BLAS=1 forces the BLAS library for every precision (A/B)."""
-    return _SPLIT_PRODUCTS
+class _Workspace:
+    """[chunk, width] buffers of the edge part, allocated once per backward call: the ones the plan's forms touch"""
+
+    def __init__(self, bp, Wx, Wm, M, device):
+        rows = bp.rows
+        e = lambda *shape, dt=bp.dtype: torch.empty(*shape, dtype=dt, device=device)
+        if not bp.kept:   # (the saved-activation backward reads s1 / a2 from what the forward kept)
+            self.s1x, self.s1m = e(rows, Wx), e(rows, Wm)
+            self.a2x, self.a2m = e(rows, Wx), e(rows, M)
+        self.d2 = e(rows, dt=torch.float32)
+        self.g_diff = e(rows, 3, dt=torch.float32)
+        # dL/da1 and the gathered first-layer inputs / their gradients exist only in the forms that store them: the default
+        # 'graph' form of the first Linear layers never touches them (2 x 2 GiB + 2 x 256 MiB at 2^20 rows, W = 1024)
+        if bp.first != "graph":
+            self.g1x, self.g1m = e(rows, Wx), e(rows, Wm)
+        if bp.first is None:
+            self.inp, self.g_in = e(rows, bp.K1P), e(rows, bp.K1P)
 
 
-def _mm(a, b, out=None):
-    """a @ b for fp32 operands of the fp32-grade chain"""
-    if _own_fp32_products() and a.is_cuda and a.dtype == torch.float32:
+def _mm(split, a, b, out=None):
+    """a @ b for fp32 operands of the fp32-grade chain; `split`: as head + remainder products (gemm.mm_nn_split, 2^-16 per
+    operand -- what the tolerance-grade precisions' forward carries)"""
+    if split and a.is_cuda and a.dtype == torch.float32:
         from .gemm import mm_nn_split
         return mm_nn_split(a, b.float(), out=out)
     return torch.mm(a, b, out=out) if out is not None else torch.mm(a, b)
 
 
-def _wgrad(g, a, n_pad, splits):
+def _wgrad(split, g, a, n_pad, splits):
     """g[:n_pad]^T . a[:n_pad] with the long edge dimension cut into `splits` batched products (the BLAS library's
     single-GEMM choice for K = 2^18 and a small output runs at a fraction of its batched rate); fp32 result"""
-    if _own_fp32_products() and g.is_cuda and g.dtype == torch.float32:
+    if split and g.is_cuda and g.dtype == torch.float32:
         from .gemm import mm_tn_split
         return mm_tn_split(g[:n_pad], a[:n_pad])
     S = splits
@@ -137,209 +212,275 @@ def _wgrad(g, a, n_pad, splits):
     return torch.bmm(gv.transpose(1, 2), av).float().sum(0)
 
 
-def _edge_backward(layer, prec, ws, h, x, dst32, src32, node_seg, g_am, g_ax, g_S, g_h, g_x, grads, fused=None, kept=None, plan=None):
-    """adds the edge part's contributions to g_h, g_x and to the parameter gradients in `grads`.
-    ``fused`` = (context handle, layer index) when the bf16 recompute runs on the forward's own MFMA edge kernels
-    (egcl_backward_edge_recompute) instead of l1_act -> GEMM -> heads.
-    ``kept`` = (s1x, s1m, t2x, t2m, s_shares) of this layer when the forward ran as egcl_forward_save: no recompute pass,
-    egcl_backward_heads_saved turns the kept pre-activations into dL/da2 in place."""
-    L = _lib.lib()
-    st = _lib.stream_ptr()
-    P = _lib.ptr
-    dt = ws.dtype
-    H, K1P = h.shape[1], ws.K1P
-    lin_x0, lin_x2, lin_x4 = layer.mlp_x[0], layer.mlp_x[2], layer.mlp_x[4]
-    lin_m0, lin_m2, att = layer.mlp_m[0], layer.mlp_m[2], layer.attention[0]
-    Wx, Wm, M = lin_x0.out_features, lin_m0.out_features, lin_m2.out_features
+def _acc(grads, p, g):
+    grads[p] = g if p not in grads else grads[p] + g        # (no `0 + g` launch for the first contribution)
+
+
+P = _lib.ptr
+
+
+# ---- edge part -------------------------------------------------------------------------------------------------------------
+def _first_layer_operands(s, lin):
+    """per-node halves P, Q of the first Linear layer (:56's concatenation factorised), its d2 column and its dgrad operand"""
+    w, H = lin.weight.detach(), s.H
+    if s.bp.hip_gemms:   # the fused kernels take P / Q from the forward's table; the dgrad runs on packed fragments
+        from .gemm import pack_rows_weights
+        return None, None, None, (None if s.bp.first else pack_rows_weights(w.float().contiguous(), 2 * H + 1))
+    Pn = (s.mm(s.h, w[:, :H].t().contiguous()) + lin.bias.detach()).contiguous()
+    Qn = s.mm(s.h, w[:, H:2 * H].t().contiguous()).contiguous()
+    wpad = torch.zeros(w.shape[0], s.bp.K1P, dtype=s.bp.dtype, device=s.h.device)
+    wpad[:, :2 * H + 1] = w
+    return Pn, Qn, w[:, 2 * H].contiguous(), wpad
+
+
+def _edge_setup(bp, layer, ws, fused, kept, h, x, graph, node_seg, g_am, g_ax, g_S, g_h, g_x):
+    """weights in the operand form the plan needs and the zero-filled fp32 accumulators of one layer"""
+    s = SimpleNamespace(bp=bp, ws=ws, kept=kept, h=h, x=x, graph=graph, node_seg=node_seg,
+                        g_S=g_S, g_h=g_h, g_x=g_x, L=_lib.lib(), st=_lib.stream_ptr(), H=h.shape[1], N=h.shape[0],
+                        dst32=graph.edge_dst, src32=graph.edge_src, E=graph.edge_dst.numel(),
+                        mm=partial(_mm, bp.split_products), wgrad=partial(_wgrad, bp.split_products))
+    s.lin_x0, s.lin_x2, s.lin_x4 = layer.mlp_x[0], layer.mlp_x[2], layer.mlp_x[4]
+    s.lin_m0, s.lin_m2, s.att = layer.mlp_m[0], layer.mlp_m[2], layer.attention[0]
+    H, K1P, dt = s.H, bp.K1P, bp.dtype
+    Wx, Wm, M = s.Wx, s.Wm, s.M = s.lin_x0.out_features, s.lin_m0.out_features, s.lin_m2.out_features
     f32 = dict(dtype=torch.float32, device=h.device)
-
-    hip = fused is not None and dt == torch.bfloat16 and ws.hip_gemms and _hip_gemm_shapes(H, Wx, Wm, M)
-    if hip:
-        from .gemm import gemm_rows, gemm_tn, pack_rows_weights
-
-    E = dst32.numel()
-    rows = ws.rows
-    # First Linear layers factorised as the forward factorises them: per-node sums of dL/da1 over the edges a node receives /
-    # sends, then node-level products -- instead of gather + 2 wgrad GEMMs over all edges + the row-streaming dgrad GEMM + the
-    # feature half of the scatter.  Batches of graphs of at most 64 nodes.  Two forms:
-    #   "graph"  (default; EGNN_BWD_GRAPH=0 turns it off): the sums are taken INSIDE the dgrad kernel's epilogue
-    #            (csrc/edge_bwd_dgrad_graph.hip, one workgroup per graph and 256 hidden units): dL/da1 is never written;
-    #   "reduce" (EGNN_BWD_FIRST=1): one extra pass over the stored dL/da1 (csrc/edge_bwd_first.hip) -- correct and tested, but
-    #            slower than the chain it replaces (profiles/r04f_first_layer_factorised.txt); kept as the reference form.
-    first = None
-    chunks = [(a, min(rows, E - a)) for a in range(0, E, rows)]
-    if hip and plan is not None and getattr(plan, "max_graph_nodes", 1 << 30) <= 64 and Wx % 256 == 0 and Wm % 256 == 0:
-        if os.environ.get("EGNN_BWD_FIRST", "0") == "1":
-            first = "reduce"
-        elif os.environ.get("EGNN_BWD_GRAPH", "1") != "0" and fused is not None:
-            cut = _graph_chunks(plan, rows)   # chunks of whole graphs
-            if cut is not None:
-                first, chunks = "graph", cut
-
-    def tables(lin):   # per-node halves of the first Linear layer (:56's concatenation factorised)
-        w = lin.weight.detach()
-        if hip:        # the fused kernels take P / Q from the forward's table; the dgrad runs on packed fragments
-            return None, None, None, (None if first else pack_rows_weights(w.float().contiguous(), 2 * H + 1))
-        Pn = (_mm(h, w[:, :H].t().contiguous()) + lin.bias.detach()).contiguous()
-        Qn = _mm(h, w[:, H:2 * H].t().contiguous()).contiguous()
-        wpad = torch.zeros(w.shape[0], K1P, dtype=dt, device=h.device)
-        wpad[:, :2 * H + 1] = w
-        return Pn, Qn, w[:, 2 * H].contiguous(), wpad
-
-    Px, Qx, wdx, w1x = tables(lin_x0)
-    Pm, Qm, wdm, w1m = tables(lin_m0)
-    w2x, w2m = lin_x2.weight.detach().to(dt), lin_m2.weight.detach().to(dt)
-    b2x, b2m = lin_x2.bias.detach().contiguous(), lin_m2.bias.detach().contiguous()
-    w3, b3 = lin_x4.weight.detach().reshape(-1).contiguous(), lin_x4.bias.detach().contiguous()
-    wa, ba = att.weight.detach().reshape(-1).contiguous(), att.bias.detach().contiguous()
+    s.Px, s.Qx, s.wdx, s.w1x = _first_layer_operands(s, s.lin_x0)
+    s.Pm, s.Qm, s.wdm, s.w1m = _first_layer_operands(s, s.lin_m0)
+    s.w2x, s.w2m = s.lin_x2.weight.detach().to(dt), s.lin_m2.weight.detach().to(dt)
+    s.b2x, s.b2m = s.lin_x2.bias.detach().contiguous(), s.lin_m2.bias.detach().contiguous()
+    s.w3, s.b3 = s.lin_x4.weight.detach().reshape(-1).contiguous(), s.lin_x4.bias.detach().contiguous()
+    s.wa, s.ba = s.att.weight.detach().reshape(-1).contiguous(), s.att.bias.detach().contiguous()
     # fp32 accumulators; the first Linear layers carry their bias gradient in column 2H+1 (ones column of `in`)
     # (one zero fill for all of them: a dozen 5-us launches per layer otherwise; every piece starts at a multiple of 4 floats)
-    shapes = [(Wx, K1P), (Wm, K1P), (Wx, Wx), (M, Wm), (Wx,), (Wx,), (4,), (M,), (M,), (4,)]
-    if plan is not None:
-        shapes += [(plan.B, Wx), (plan.B, Wm)]
-    sizes_ = [_round_up(math.prod(sh), 4) for sh in shapes]
-    flat = torch.zeros(sum(sizes_), **f32)
-    pieces, o = [], 0
-    for sh, sz in zip(shapes, sizes_):
-        pieces.append(flat[o:o + math.prod(sh)].view(*sh))
-        o += sz
-    g_w1x, g_w1m, g_w2x, g_w2m, g_b2x, g_w3, g_b3, g_b2m, g_wa, g_ba = pieces[:10]
-    g_b3, g_ba = g_b3[:1], g_ba[:1]
-    g_am, g_ax = g_am.contiguous(), g_ax.contiguous()
-    global LAST_FIRST_LAYER_FORM
-    LAST_FIRST_LAYER_FORM = first
-    if first:
-        N, nparts = h.shape[0], (Wx + Wm) // 256
-        cd_x, cd_m = pieces[10], pieces[11]
-        gd2_part = torch.empty(nparts * min(rows, E), **f32)
-    if first == "graph":     # the kernel leaves the sums as the bf16 operands of the node-level products: [Gd_x | Gs_x | Gd_m | Gs_m]
-        G = torch.zeros(N, 2 * Wx + 2 * Wm, dtype=torch.bfloat16, device=h.device)
-    elif first == "reduce":
-        Gd_x, Gs_x, Gd_m, Gs_m = (torch.zeros(N, w, **f32) for w in (Wx, Wx, Wm, Wm))
-    if first == "reduce":
-        wdx_f = lin_x0.weight.detach()[:, 2 * H].float().contiguous()
-        wdm_f = lin_m0.weight.detach()[:, 2 * H].float().contiguous()
-    if fused is not None:
-        _lib.check(L.egcl_backward_table(fused[0], st, fused[1], P(h)))
-    for a, n in chunks:
-        n_pad = _round_up(n, 64)
-        d32, s32 = dst32[a:a + n], src32[a:a + n]
-        if kept is not None:   # chunk views of the layer-long buffers (their rows beyond E are zero)
-            S1X, S1M, A2X, A2M = (t[a:a + n_pad] for t in kept[:4])
-        else:
-            S1X, S1M, A2X, A2M = ws.s1x, ws.s1m, ws.a2x, ws.a2m
-        s1x, s1m, a2x, a2m = S1X[:n], S1M[:n], A2X[:n], A2M[:n]
-        d2, g_diff = ws.d2[:n], ws.g_diff[:n]
-        if first != "graph":   # (the 'graph' form has no dL/da1 in memory)
-            g1x, g1m = ws.g1x[:n], ws.g1m[:n]
-        if not first:
-            inp, g_in = ws.inp[:n], ws.g_in[:n]
-        if n_pad > n and not hip:   # rows the split library products read beyond the chunk (the own GEMMs stop at row n)
-            for t in ((ws.g1x, ws.g1m, ws.inp) if kept is not None else (ws.s1x, ws.s1m, ws.a2x, ws.a2m, ws.g1x, ws.g1m, ws.inp)):
-                t[n:n_pad].zero_()
-        if not first:
-            _lib.check(L.egcl_backward_gather_in(st, prec, n, H, K1P, P(d32), P(s32), P(h), P(x), P(inp), P(d2)))
-        if kept is not None:
-            # dL/da2 in place over the kept pre-activations, g_diff and the bias / w3 / wa column sums: one element-wise pass
-            _lib.check(L.egcl_backward_heads_saved(fused[0], st, fused[1], P(x), P(g_ax), P(g_am), a, n, P(a2x), P(a2m),
-                                                   P(kept[4]), P(g_diff), P(g_b2x), P(g_w3), P(g_b3), P(g_b2m), P(g_wa),
-                                                   P(g_ba)))
-        elif fused is not None:
-            # s1 (scaled by -log2 e), dL/da2, g_diff and the bias / w3 / wa column sums in one pass of the MFMA edge kernels
-            _lib.check(L.egcl_backward_edge_recompute(fused[0], st, fused[1], P(x), P(g_ax), P(g_am), a, n, P(s1x), P(s1m),
-                                                      P(a2x), P(a2m), P(g_diff), P(g_b2x), P(g_w3), P(g_b3), P(g_b2m),
-                                                      P(g_wa), P(g_ba)))
-        else:
-            _lib.check(L.egcl_backward_l1_act(st, prec, n, Wx, P(d32), P(s32), P(Px), P(Qx), P(wdx), P(d2), P(s1x)))
-            _lib.check(L.egcl_backward_l1_act(st, prec, n, Wm, P(d32), P(s32), P(Pm), P(Qm), P(wdm), P(d2), P(s1m)))
-            _mm(s1x, w2x.t().contiguous(), out=a2x)
-            _mm(s1m, w2m.t().contiguous(), out=a2m)
-            _lib.check(L.egcl_backward_heads(st, prec, n, Wx, M, P(d32), P(s32), P(x), P(g_ax), P(g_am), P(a2x), P(a2m),
-                                             P(b2x), P(w3), P(b3), P(b2m), P(wa), P(ba), P(g_diff), P(g_b2x), P(g_w3),
-                                             P(g_b3), P(g_b2m), P(g_wa), P(g_ba)))
-        # a2x / a2m now hold dL/da2: wgrad and dgrad of the second Linear layers
-        if hip:   # reductions over the chunk's edges on the library's own split-K kernel (gemm_tn.hip), fp32 accumulate
-            # (the recompute / keeping kernels store s1 as the MFMA consumed it, -log2(e) * SiLU(a1): undone by the scale.
-            # Measured and dropped: the message head on a second stream beside the coordinate MLP's product -- HBM-bound
-            # beside MFMA-bound -- made the step 1.0 ms LONGER, 51.8 vs 50.8 ms on one box)
-            gemm_tn(a2x, s1x, out=g_w2x, accumulate=True, scale=-math.log(2.0))
-            gemm_tn(a2m, s1m, out=g_w2m, accumulate=True, scale=-math.log(2.0))
-        else:
-            g_w2x += _wgrad(A2X, S1X, n_pad, 16)
-            g_w2m += _wgrad(A2M, S1M, n_pad, 32)
-        if first == "graph":
-            # dgrad of the second layers, SiLU'(a1) and the first layers' per-node sums in one kernel: no dL/da1 in memory
-            _lib.check(L.egcl_backward_dgrad_reduce(fused[0], st, fused[1], P(x), a, n, P(a2x), P(a2m), P(G), P(cd_x), P(cd_m),
-                                                    P(gd2_part)))
-        elif fused is not None:
-            # dgrad of the second layers with SiLU'(a1) in the epilogue, on MFMA (no [n, W] round trip in between)
-            _lib.check(L.egcl_backward_dgrad(fused[0], st, fused[1], P(x), a, n, P(a2x), P(a2m), P(g1x), P(g1m)))
-        else:
-            _mm(a2x, w2x, out=g1x)
-            _mm(a2m, w2m, out=g1m)
-            _lib.check(L.egcl_backward_l1_grad(st, prec, n, Wx, P(d32), P(s32), P(Px), P(Qx), P(wdx), P(d2), P(g1x)))
-            _lib.check(L.egcl_backward_l1_grad(st, prec, n, Wm, P(d32), P(s32), P(Pm), P(Qm), P(wdm), P(d2), P(g1m)))
-        # first Linear layers: wgrad against in = [h_i | h_j | d2 | 1], dgrad back to the gathered inputs
-        if first:
-            if first == "reduce":
-                _lib.check(L.egcl_backward_first_reduce(st, plan.B, plan.max_graph_nodes, a, n, P(plan.graph_ptr), P(plan.row_ptr),
-                                                        P(src32), P(x), P(g1x), Wx, P(g1m), Wm, P(wdx_f), P(wdm_f), P(Gd_x),
-                                                        P(Gs_x), P(Gd_m), P(Gs_m), P(cd_x), P(cd_m), P(gd2_part)))
-            _lib.check(L.egcl_backward_scatter_geom(st, n, nparts, P(d32), P(s32), P(x), P(gd2_part), P(g_diff), P(g_S),
-                                                    P(node_seg), P(g_x)))
-            continue
-        if hip:
-            gemm_tn(g1x, inp, cols=2 * H + 2, out=g_w1x, accumulate=True)
-            gemm_tn(g1m, inp, cols=2 * H + 2, out=g_w1m, accumulate=True)
-            gemm_rows(g1x, w1x, g1m, w1m, out=g_in)      # row-streaming product (gemm_rows.hip): every dL/da1 row read once
-        else:
-            g_w1x += _wgrad(ws.g1x, ws.inp, n_pad, 32)
-            g_w1m += _wgrad(ws.g1m, ws.inp, n_pad, 32)
-            _mm(g1x, w1x, out=g_in)
-            g_in += _mm(g1m, w1m)
-        _lib.check(L.egcl_backward_scatter(st, prec, n, H, K1P, P(d32), P(s32), P(x), P(g_in), P(g_diff), P(g_S),
-                                           P(node_seg), P(g_h), P(g_x)))
+    shapes = [(Wx, K1P), (Wm, K1P), (Wx, Wx), (M, Wm), (Wx,), (Wx,), (4,), (M,), (M,), (4,), (graph.B, Wx), (graph.B, Wm)]
+    sizes = [_round_up(math.prod(sh), 4) for sh in shapes]
+    flat = torch.zeros(sum(sizes), **f32)
+    offs = [sum(sizes[:i]) for i in range(len(sizes))]
+    (s.g_w1x, s.g_w1m, s.g_w2x, s.g_w2m, s.g_b2x, s.g_w3, g_b3, s.g_b2m, s.g_wa, g_ba, s.cd_x,
+     s.cd_m) = (flat[o:o + math.prod(sh)].view(*sh) for o, sh in zip(offs, shapes))
+    s.g_b3, s.g_ba = g_b3[:1], g_ba[:1]
+    s.g_am, s.g_ax = g_am.contiguous(), g_ax.contiguous()
+    s.sums = tuple(P(t) for t in (s.g_b2x, s.g_w3, s.g_b3, s.g_b2m, s.g_wa, s.g_ba))   # the bias / w3 / wa column sums
+    s.handle_args = (fused[0], s.st, fused[1], P(x))                                   # head of every context-handle call
+    if bp.first:   # per-node sums of dL/da1 over the edges a node receives (Gd) / sends (Gs), and the partial sums of dL/d(d2)
+        s.nparts = (Wx + Wm) // 256
+        s.gd2_part = torch.empty(s.nparts * min(bp.rows, s.E), **f32)
+    if bp.first == "graph":     # the kernel leaves the sums as the bf16 operands of the node-level products: [Gd_x | Gs_x | Gd_m | Gs_m]
+        s.G = torch.zeros(s.N, 2 * Wx + 2 * Wm, dtype=torch.bfloat16, device=h.device)
+    elif bp.first == "reduce":
+        s.Gd_x, s.Gs_x, s.Gd_m, s.Gs_m = (torch.zeros(s.N, w, **f32) for w in (Wx, Wx, Wm, Wm))
+        s.wdx_f = s.lin_x0.weight.detach()[:, 2 * H].float().contiguous()
+        s.wdm_f = s.lin_m0.weight.detach()[:, 2 * H].float().contiguous()
+    return s
 
-    if fused is not None and not hip:   # the recompute kernels store s1 as the MFMA consumed it: -log2(e) * SiLU(a1)
-        g_w2x *= -math.log(2.0)
-        g_w2m *= -math.log(2.0)
-    if first == "graph":   # node-level products of the factorised first layers on the library's own GEMMs (N rows, bf16 operands)
-        hb = torch.zeros(N, 128, dtype=torch.bfloat16, device=h.device)
-        hb[:, :H] = h
-        hb[:, H] = 1.0                                       # (ones column: the bias gradients = column sums of Gd)
-        Wg = gemm_tn(G, hb, cols=H + 1)                      # [2 Wx + 2 Wm, H + 1] = G^T [h | 1]
-        for g_w1, o, W, cd in ((g_w1x, 0, Wx, cd_x), (g_w1m, 2 * Wx, Wm, cd_m)):
-            g_w1[:, :H] = Wg[o:o + W, :H]
-            g_w1[:, H:2 * H] = Wg[o + W:o + 2 * W, :H]
-            g_w1[:, 2 * H] = cd.sum(0)
-            g_w1[:, 2 * H + 1] = Wg[o:o + W, H]
-        # dL/dh += Gd W1[:, :H] + Gs W1[:, H:2H] for both MLPs: one row-streaming product over [Gd | Gs] (K = 2 W each)
-        wcat = [pack_rows_weights(torch.cat([lin.weight.detach()[:, :H], lin.weight.detach()[:, H:2 * H]], 0).float().contiguous(), H)
-                for lin in (lin_x0, lin_m0)]
-        gh_add = torch.empty(N, 128, **f32)
-        gemm_rows(G[:, :2 * Wx], wcat[0], G[:, 2 * Wx:], wcat[1], out=gh_add)
-        g_h += gh_add[:, :H]
-    elif first:   # ("reduce": the reference form, fp32 library products)
-        hf = h.float()
-        for g_w1, Gd, Gs, cd, lin in ((g_w1x, Gd_x, Gs_x, cd_x, lin_x0), (g_w1m, Gd_m, Gs_m, cd_m, lin_m0)):
-            g_w1[:, :H] = Gd.t() @ hf
-            g_w1[:, H:2 * H] = Gs.t() @ hf
-            g_w1[:, 2 * H] = cd.sum(0)
-            g_w1[:, 2 * H + 1] = Gd.sum(0)
-            w1 = lin.weight.detach().float()
-            g_h.addmm_(Gd, w1[:, :H])
-            g_h.addmm_(Gs, w1[:, H:2 * H])
 
-    def acc(p, g):
-        g = g.reshape(p.shape).contiguous()
-        grads[p] = g if p not in grads else grads[p] + g        # (no `0 + g` launch for the first contribution)
+def _chunk(s, a, n):
+    """views of edges [a, a + n) on the workspace (or on the layer-long kept buffers, whose rows beyond E are zero), and d2"""
+    ws, n_pad = s.ws, _round_up(n, 64)
+    c = SimpleNamespace(a=a, n=n, n_pad=n_pad, d32=s.dst32[a:a + n], s32=s.src32[a:a + n], d2=ws.d2[:n], g_diff=ws.g_diff[:n])
+    if s.bp.kept:
+        c.S1X, c.S1M, c.A2X, c.A2M = (t[a:a + n_pad] for t in s.kept[:4])
+    else:
+        c.S1X, c.S1M, c.A2X, c.A2M = ws.s1x, ws.s1m, ws.a2x, ws.a2m
+    c.s1x, c.s1m, c.a2x, c.a2m = c.S1X[:n], c.S1M[:n], c.A2X[:n], c.A2M[:n]
+    if s.bp.first != "graph":   # (the 'graph' form has no dL/da1 in memory)
+        c.g1x, c.g1m = ws.g1x[:n], ws.g1m[:n]
+    if s.bp.first is None:
+        c.inp, c.g_in = ws.inp[:n], ws.g_in[:n]
+    if n_pad > n and not s.bp.hip_gemms:   # rows the library products read beyond the chunk (the own GEMMs stop at row n)
+        for t in ((ws.g1x, ws.g1m, ws.inp) if s.bp.kept else (ws.s1x, ws.s1m, ws.a2x, ws.a2m, ws.g1x, ws.g1m, ws.inp)):
+            t[n:n_pad].zero_()
+    if s.bp.first is None:   # the chain's gathered inputs [h_i | h_j | d2 | 1]
+        _lib.check(s.L.egcl_backward_gather_in(s.st, s.bp.prec, n, s.H, s.bp.K1P, P(c.d32), P(c.s32), P(s.h), P(s.x), P(c.inp), P(c.d2)))
+    return c
 
-    acc(lin_x0.weight, g_w1x[:, :2 * H + 1]); acc(lin_x0.bias, g_w1x[:, 2 * H + 1])
-    acc(lin_m0.weight, g_w1m[:, :2 * H + 1]); acc(lin_m0.bias, g_w1m[:, 2 * H + 1])
-    acc(lin_x2.weight, g_w2x); acc(lin_x2.bias, g_b2x)
-    acc(lin_m2.weight, g_w2m); acc(lin_m2.bias, g_b2m)
-    acc(lin_x4.weight, g_w3); acc(lin_x4.bias, g_b3)
-    acc(att.weight, g_wa); acc(att.bias, g_ba)
+
+def _a2_saved(s, c):
+    """dL/da2 in place over the kept pre-activations, g_diff and the bias / w3 / wa column sums: one element-wise pass"""
+    _lib.check(s.L.egcl_backward_heads_saved(*s.handle_args, P(s.g_ax), P(s.g_am), c.a, c.n, P(c.a2x), P(c.a2m), P(s.kept[4]),
+                                             P(c.g_diff), *s.sums))
+
+
+def _a2_recompute(s, c):
+    """s1 (scaled by -log2 e), dL/da2, g_diff and the bias / w3 / wa column sums in one pass of the MFMA edge kernels"""
+    _lib.check(s.L.egcl_backward_edge_recompute(*s.handle_args, P(s.g_ax), P(s.g_am), c.a, c.n, P(c.s1x), P(c.s1m), P(c.a2x),
+                                                P(c.a2m), P(c.g_diff), *s.sums))
+
+
+def _a2_chain(s, c):
+    L, st, prec, n = s.L, s.st, s.bp.prec, c.n
+    _lib.check(L.egcl_backward_l1_act(st, prec, n, s.Wx, P(c.d32), P(c.s32), P(s.Px), P(s.Qx), P(s.wdx), P(c.d2), P(c.s1x)))
+    _lib.check(L.egcl_backward_l1_act(st, prec, n, s.Wm, P(c.d32), P(c.s32), P(s.Pm), P(s.Qm), P(s.wdm), P(c.d2), P(c.s1m)))
+    s.mm(c.s1x, s.w2x.t().contiguous(), out=c.a2x)
+    s.mm(c.s1m, s.w2m.t().contiguous(), out=c.a2m)
+    _lib.check(L.egcl_backward_heads(st, prec, n, s.Wx, s.M, P(c.d32), P(c.s32), P(s.x), P(s.g_ax), P(s.g_am), P(c.a2x), P(c.a2m),
+                                     P(s.b2x), P(s.w3), P(s.b3), P(s.b2m), P(s.wa), P(s.ba), P(c.g_diff), *s.sums))
+
+
+def _w2_own(s, c):
+    """reductions over the chunk's edges on the library's own split-K kernel (gemm_tn.hip), fp32 accumulate
+    (the recompute / keeping kernels store s1 as the MFMA consumed it, -log2(e) * SiLU(a1): undone by the scale.
+    Measured and dropped: the message head on a second stream beside the coordinate MLP's product -- HBM-bound
+    beside MFMA-bound -- made the step 1.0 ms LONGER, 51.8 vs 50.8 ms on one box)"""
+    from .gemm import gemm_tn
+    gemm_tn(c.a2x, c.s1x, out=s.g_w2x, accumulate=True, scale=-math.log(2.0))
+    gemm_tn(c.a2m, c.s1m, out=s.g_w2m, accumulate=True, scale=-math.log(2.0))
+
+
+def _w2_library(s, c):
+    s.g_w2x += s.wgrad(c.A2X, c.S1X, c.n_pad, 16)
+    s.g_w2m += s.wgrad(c.A2M, c.S1M, c.n_pad, 32)
+
+
+def _da1_graph(s, c):
+    """dgrad of the second layers, SiLU'(a1) and the first layers' per-node sums in one kernel: no dL/da1 in memory"""
+    _lib.check(s.L.egcl_backward_dgrad_reduce(*s.handle_args, c.a, c.n, P(c.a2x), P(c.a2m), P(s.G), P(s.cd_x), P(s.cd_m),
+                                              P(s.gd2_part)))
+
+
+def _da1_fused(s, c):
+    """dgrad of the second layers with SiLU'(a1) in the epilogue, on MFMA (no [n, W] round trip in between)"""
+    _lib.check(s.L.egcl_backward_dgrad(*s.handle_args, c.a, c.n, P(c.a2x), P(c.a2m), P(c.g1x), P(c.g1m)))
+
+
+def _da1_chain(s, c):
+    L, st, prec, n = s.L, s.st, s.bp.prec, c.n
+    s.mm(c.a2x, s.w2x, out=c.g1x)
+    s.mm(c.a2m, s.w2m, out=c.g1m)
+    _lib.check(L.egcl_backward_l1_grad(st, prec, n, s.Wx, P(c.d32), P(c.s32), P(s.Px), P(s.Qx), P(s.wdx), P(c.d2), P(c.g1x)))
+    _lib.check(L.egcl_backward_l1_grad(st, prec, n, s.Wm, P(c.d32), P(c.s32), P(s.Pm), P(s.Qm), P(s.wdm), P(c.d2), P(c.g1m)))
+
+
+def _first_factorised(s, c):
+    """per-node sums of dL/da1 (already taken by the "graph" form's dgrad kernel) and the geometric half of the scatter"""
+    g = s.graph
+    if s.bp.first == "reduce":
+        _lib.check(s.L.egcl_backward_first_reduce(s.st, g.B, g.max_graph_nodes, c.a, c.n, P(g.graph_ptr), P(g.row_ptr), P(s.src32),
+                                                  P(s.x), P(c.g1x), s.Wx, P(c.g1m), s.Wm, P(s.wdx_f), P(s.wdm_f), P(s.Gd_x),
+                                                  P(s.Gs_x), P(s.Gd_m), P(s.Gs_m), P(s.cd_x), P(s.cd_m), P(s.gd2_part)))
+    _lib.check(s.L.egcl_backward_scatter_geom(s.st, c.n, s.nparts, P(c.d32), P(c.s32), P(s.x), P(s.gd2_part), P(c.g_diff), P(s.g_S),
+                                              P(s.node_seg), P(s.g_x)))
+
+
+def _scatter(s, c):
+    _lib.check(s.L.egcl_backward_scatter(s.st, s.bp.prec, c.n, s.H, s.bp.K1P, P(c.d32), P(c.s32), P(s.x), P(c.g_in), P(c.g_diff),
+                                         P(s.g_S), P(s.node_seg), P(s.g_h), P(s.g_x)))
+
+
+def _first_own(s, c):
+    """wgrad against in = [h_i | h_j | d2 | 1] and dgrad back to the gathered inputs on the own kernels"""
+    from .gemm import gemm_rows, gemm_tn
+    gemm_tn(c.g1x, c.inp, cols=2 * s.H + 2, out=s.g_w1x, accumulate=True)
+    gemm_tn(c.g1m, c.inp, cols=2 * s.H + 2, out=s.g_w1m, accumulate=True)
+    gemm_rows(c.g1x, s.w1x, c.g1m, s.w1m, out=c.g_in)      # row-streaming product (gemm_rows.hip): every dL/da1 row read once
+    _scatter(s, c)
+
+
+def _first_library(s, c):
+    s.g_w1x += s.wgrad(s.ws.g1x, s.ws.inp, c.n_pad, 32)
+    s.g_w1m += s.wgrad(s.ws.g1m, s.ws.inp, c.n_pad, 32)
+    s.mm(c.g1x, s.w1x, out=c.g_in)
+    c.g_in += s.mm(c.g1m, s.w1m)
+    _scatter(s, c)
+
+
+def _stages(bp):
+    """the per-chunk routines of a plan: (dL/da2, second-layer wgrad, dL/da1, first layers + scatter)"""
+    return (_a2_saved if bp.kept else _a2_recompute if bp.fused else _a2_chain,
+            _w2_own if bp.hip_gemms else _w2_library,
+            _da1_graph if bp.first == "graph" else _da1_fused if bp.fused else _da1_chain,
+            _first_factorised if bp.first else _first_own if bp.hip_gemms else _first_library)
+
+
+def _finish_graph(s):
+    """node-level products of the factorised first layers on the library's own GEMMs (N rows, bf16 operands)"""
+    from .gemm import gemm_rows, gemm_tn, pack_rows_weights
+    H, N, Wx, Wm, G = s.H, s.N, s.Wx, s.Wm, s.G
+    hb = torch.zeros(N, 128, dtype=torch.bfloat16, device=s.h.device)
+    hb[:, :H] = s.h
+    hb[:, H] = 1.0                                       # (ones column: the bias gradients = column sums of Gd)
+    Wg = gemm_tn(G, hb, cols=H + 1)                      # [2 Wx + 2 Wm, H + 1] = G^T [h | 1]
+    for g_w1, o, W, cd in ((s.g_w1x, 0, Wx, s.cd_x), (s.g_w1m, 2 * Wx, Wm, s.cd_m)):
+        g_w1[:, :H] = Wg[o:o + W, :H]
+        g_w1[:, H:2 * H] = Wg[o + W:o + 2 * W, :H]
+        g_w1[:, 2 * H] = cd.sum(0)
+        g_w1[:, 2 * H + 1] = Wg[o:o + W, H]
+    # dL/dh += Gd W1[:, :H] + Gs W1[:, H:2H] for both MLPs: one row-streaming product over [Gd | Gs] (K = 2 W each)
+    wcat = [pack_rows_weights(torch.cat([lin.weight.detach()[:, :H], lin.weight.detach()[:, H:2 * H]], 0).float().contiguous(), H)
+            for lin in (s.lin_x0, s.lin_m0)]
+    gh_add = torch.empty(N, 128, dtype=torch.float32, device=s.h.device)
+    gemm_rows(G[:, :2 * Wx], wcat[0], G[:, 2 * Wx:], wcat[1], out=gh_add)
+    s.g_h += gh_add[:, :H]
+
+
+def _finish_reduce(s):
+    """the same products for the reference form: fp32 library products"""
+    H, hf = s.H, s.h.float()
+    for g_w1, Gd, Gs, cd, lin in ((s.g_w1x, s.Gd_x, s.Gs_x, s.cd_x, s.lin_x0), (s.g_w1m, s.Gd_m, s.Gs_m, s.cd_m, s.lin_m0)):
+        g_w1[:, :H] = Gd.t() @ hf
+        g_w1[:, H:2 * H] = Gs.t() @ hf
+        g_w1[:, 2 * H] = cd.sum(0)
+        g_w1[:, 2 * H + 1] = Gd.sum(0)
+        w1 = lin.weight.detach().float()
+        s.g_h.addmm_(Gd, w1[:, :H])
+        s.g_h.addmm_(Gs, w1[:, H:2 * H])
+
+
+def _edge_finish(s, grads):
+    H = s.H
+    if s.bp.fused and not s.bp.hip_gemms:   # the recompute kernels store s1 as the MFMA consumed it: -log2(e) * SiLU(a1)
+        s.g_w2x *= -math.log(2.0)
+        s.g_w2m *= -math.log(2.0)
+    if s.bp.first == "graph":
+        _finish_graph(s)
+    elif s.bp.first == "reduce":
+        _finish_reduce(s)
+    for p, g in ((s.lin_x0.weight, s.g_w1x[:, :2 * H + 1]), (s.lin_x0.bias, s.g_w1x[:, 2 * H + 1]),
+                 (s.lin_m0.weight, s.g_w1m[:, :2 * H + 1]), (s.lin_m0.bias, s.g_w1m[:, 2 * H + 1]),
+                 (s.lin_x2.weight, s.g_w2x), (s.lin_x2.bias, s.g_b2x), (s.lin_m2.weight, s.g_w2m), (s.lin_m2.bias, s.g_b2m),
+                 (s.lin_x4.weight, s.g_w3), (s.lin_x4.bias, s.g_b3), (s.att.weight, s.g_wa), (s.att.bias, s.g_ba)):
+        _acc(grads, p, g.reshape(p.shape).contiguous())
+
+
+def _edge_backward(bp, layer, ws, fused, kept, h, x, graph, node_seg, g_am, g_ax, g_S, g_h, g_x, grads):
+    """adds the edge part's contributions to g_h, g_x and to the parameter gradients in `grads`.  ``fused`` = (context handle or
+    None, layer index); ``kept`` = (s1x, s1m, t2x, t2m, s_shares) of this layer when the forward ran as egcl_forward_save."""
+    s = _edge_setup(bp, layer, ws, fused, kept, h, x, graph, node_seg, g_am, g_ax, g_S, g_h, g_x)
+    if bp.fused:
+        _lib.check(s.L.egcl_backward_table(*s.handle_args[:3], P(h)))
+    a2, w2, da1, first_layers = _stages(bp)
+    for a, n in bp.chunks:
+        c = _chunk(s, a, n)
+        a2(s, c)             # a2x / a2m now hold dL/da2
+        w2(s, c)
+        da1(s, c)
+        first_layers(s, c)
+    _edge_finish(s, grads)
+
+
+# ---- node part -------------------------------------------------------------------------------------------------------------
+def _zero(o, like):
+    return o.clone() if o is not None else torch.zeros_like(like)
+
+
+def _segment_scale(S, scope_graph, node_graph):
+    G = torch.sqrt(S.clamp_min(1e-30))   # graphs without edges: S = 0, zero gradient
+    c = 1.0 / (G + 1.0)
+    return c.index_select(0, node_graph).unsqueeze(1) if scope_graph else c
+
+
+def _coordinate_update(x_l, sum_x, S, scope_graph, node_graph):
+    """x' = x + sum_x / (G + 1) (:64, :70) on torch's tape (element-wise): x' and its leaves (x, sum_x, S)"""
+    leaves = [t.detach().requires_grad_(True) for t in (x_l, sum_x, S)]
+    return leaves[0] + leaves[1] * _segment_scale(leaves[2], scope_graph, node_graph), leaves
+
+
+def _coordinate_backward(x_l, sum_x, S, gx, scope_graph, node_graph):
+    """dL/dx, dL/d sum_x, dL/dS of the coordinate update"""
+    with torch.enable_grad():
+        x_new, leaves = _coordinate_update(x_l, sum_x, S, scope_graph, node_graph)
+        o = torch.autograd.grad([x_new], leaves, [gx], allow_unused=True)
+    return _zero(o[0], x_l), _zero(o[1], sum_x), _zero(o[2], S)
 
 
 def _node_backward_hip(layer, h_l, sum_m, gh, grads):
@@ -366,37 +507,52 @@ def _node_backward_hip(layer, h_l, sum_m, gh, grads):
     # s = SiLU(z1 + b1), dL/dz1 = dL/ds * SiLU'(z1 + b1) as bf16 operands and the bias gradient, in one pass (backward.hip)
     g_z1b, s_b = torch.empty(N, Wh, **bf), torch.empty(N, Wh, **bf)
     g_b1 = torch.zeros(Wh, dtype=torch.float32, device=h_l.device)
-    _lib.check(_lib.lib().egcl_backward_node_act(_lib.stream_ptr(), N, Wh, _lib.ptr(z1), z1.stride(0), _lib.ptr(lin1.bias.detach()),
-                                                 _lib.ptr(g_s), g_s.stride(0), _lib.ptr(g_z1b), _lib.ptr(s_b), Wh, _lib.ptr(g_b1)))
-    acc = lambda p_, g_: grads.__setitem__(p_, g_ if p_ not in grads else grads[p_] + g_)
-    acc(lin2.bias, gh.sum(0))
-    acc(lin1.bias, g_b1)
-    acc(lin2.weight, gemm_tn(s_b, ghb, rows=Wh, cols=H).t())                     # [Wh, H]^T
-    acc(lin1.weight, gemm_tn(g_z1b, hcat, rows=Wh, cols=K1))                     # [Wh, H + M]
-    g_cat = linear_rows(g_z1b, lin1.weight.detach().t())                         # [N, H + M] = dL/dz1 @ W1
+    _lib.check(_lib.lib().egcl_backward_node_act(_lib.stream_ptr(), N, Wh, P(z1), z1.stride(0), P(lin1.bias.detach()),
+                                                 P(g_s), g_s.stride(0), P(g_z1b), P(s_b), Wh, P(g_b1)))
+    _acc(grads, lin2.bias, gh.sum(0))
+    _acc(grads, lin1.bias, g_b1)
+    _acc(grads, lin2.weight, gemm_tn(s_b, ghb, rows=Wh, cols=H).t())                     # [Wh, H]^T
+    _acc(grads, lin1.weight, gemm_tn(g_z1b, hcat, rows=Wh, cols=K1))                     # [Wh, H + M]
+    g_cat = linear_rows(g_z1b, lin1.weight.detach().t())                                 # [N, H + M] = dL/dz1 @ W1
     return g_cat[:, :H].contiguous(), g_cat[:, H:K1].contiguous()
 
 
 def _node_backward_split(layer, h_l, sum_m, gh, grads):
-    """backward of h' = mlp_h([h | sum_m]) (EquivariantGraphNeuralNetwork.py:26-30, :69) for the fp32-grade precisions on the
-    library's own kernels: the formulas of _node_backward_hip with every product as head + remainder (gemm.mm_nn_split /
-    mm_tn_split) and the element-wise stages in fp32."""
-    lin1, lin2 = layer.mlp_h[0], layer.mlp_h[2]
+    """the formulas of _node_backward_hip for the fp32-grade precisions on the library's own kernels: every product as head +
+    remainder (gemm.mm_nn_split / mm_tn_split, no BLAS library) and the element-wise stages in fp32 by torch"""
+    lin1, lin2, split = layer.mlp_h[0], layer.mlp_h[2], True   # (the plan picks this form only with split_products)
     H = h_l.shape[1]
     w1, w2 = lin1.weight.detach().float(), lin2.weight.detach().float()
     hcat = torch.cat((h_l, sum_m), dim=1).float()
-    z1 = _mm(hcat, w1.t().contiguous()) + lin1.bias.detach()
+    z1 = _mm(split, hcat, w1.t().contiguous()) + lin1.bias.detach()
     sg = torch.sigmoid(z1)
     s = z1 * sg
-    g_s = _mm(gh.float().contiguous(), w2)                      # [N, Wh] = gh @ W2
+    g_s = _mm(split, gh.float().contiguous(), w2)               # [N, Wh] = gh @ W2
     g_z1 = g_s * (sg * (1.0 + z1 * (1.0 - sg)))                 # SiLU'(z1)
-    acc = lambda p_, g_: grads.__setitem__(p_, g_ if p_ not in grads else grads[p_] + g_)
-    acc(lin2.bias, gh.sum(0))
-    acc(lin1.bias, g_z1.sum(0))
-    acc(lin2.weight, _wgrad(gh.float().contiguous(), s, gh.shape[0], 1))        # [H, Wh]
-    acc(lin1.weight, _wgrad(g_z1, hcat, hcat.shape[0], 1))                     # [Wh, H + M]
-    g_cat = _mm(g_z1, w1)                                                      # [N, H + M]
+    _acc(grads, lin2.bias, gh.sum(0))
+    _acc(grads, lin1.bias, g_z1.sum(0))
+    _acc(grads, lin2.weight, _wgrad(split, gh.float().contiguous(), s, gh.shape[0], 1))     # [H, Wh]
+    _acc(grads, lin1.weight, _wgrad(split, g_z1, hcat, hcat.shape[0], 1))                   # [Wh, H + M]
+    g_cat = _mm(split, g_z1, w1)                                                            # [N, H + M]
     return g_cat[:, :H].contiguous(), g_cat[:, H:].contiguous()
+
+
+def _node_backward_torch(layer, h_l, sum_m, gh, grads, x_l, sum_x, S, gx, scope_graph, node_graph):
+    """the whole node part on ONE torch tape, the coordinate update included (its launch order is the one this form always had):
+    exact fp32 products of the BLAS library -- parity mode, and shapes the own kernels do not tile.
+    Returns dL/dh, dL/d sum_m, dL/dx, dL/d sum_x, dL/dS"""
+    node_params = list(layer.mlp_h.parameters())
+    with torch.enable_grad():
+        h_leaf, am = h_l.detach().requires_grad_(True), sum_m.detach().requires_grad_(True)
+        h_new = layer.mlp_h(torch.cat((h_leaf, am), dim=1))
+        x_new, (x_leaf, ax, S_leaf) = _coordinate_update(x_l, sum_x, S, scope_graph, node_graph)
+        outs = torch.autograd.grad([h_new, x_new], [h_leaf, x_leaf, am, ax, S_leaf] + node_params, [gh, gx], allow_unused=True)
+    g_h, g_x = _zero(outs[0], h_l), _zero(outs[1], x_l)
+    g_am, g_ax, g_S = _zero(outs[2], sum_m), _zero(outs[3], sum_x), _zero(outs[4], S)
+    for p, g in zip(node_params, outs[5:]):
+        if g is not None:
+            _acc(grads, p, g)
+    return g_h, g_am, g_x, g_ax, g_S
 
 
 class _EGNNFunction(torch.autograd.Function):
@@ -406,20 +562,14 @@ class _EGNNFunction(torch.autograd.Function):
         c = _context(owner, layers, h.device)
         c.set_graph(plan)
         c.pack(layers)
-        L = _lib.lib()
+        L, sw = _lib.lib(), _switches()
         nseg = plan.B if scope == _lib.NORM_GRAPH else 1
         saved = []
         hc, xc = h.detach().float().contiguous(), x.detach().float().contiguous()
-        # Keep the edge activations instead of recomputing them in the backward (EGNN_BWD_SAVE=0 turns it off) when the
-        # bf16 fast path runs and the buffers -- E x (2 Wx + Wm + M) bf16 per layer -- take less than half of the free HBM
         kept, E = None, plan.E
-        d0 = layers[0].dims
-        Wx, Wm, M = layers[0].mlp_x[0].out_features, layers[0].mlp_m[0].out_features, d0["M"]
-        if (E > 0 and prec == _lib.PREC_BF16 and os.environ.get("EGNN_BWD_SAVE", "1") != "0" and
-                os.environ.get("EGNN_BWD_FUSED", "1") != "0" and int(os.environ.get("EGNN_EDGE", "4")) >= 4 and
-                bool(L.egcl_backward_fused_supported(c.handle))):
-            Epad = _round_up(E, 64)
-            need = len(layers) * Epad * (2 * Wx + Wm + M) * 2
+        Wx, Wm, M = layers[0].mlp_x[0].out_features, layers[0].mlp_m[0].out_features, layers[0].dims["M"]
+        Epad = _round_up(E, 64)
+        if _keep_asked(prec, E, sw) and bool(L.egcl_backward_fused_supported(c.handle)):
             # decided ONCE per (edge count, widths) on the context: "free" = what the driver reports plus what the caching
             # allocator holds reserved but unallocated (after the first step the kept buffers sit there), so the path does
             # not flip between steps or between ranks that share a device
@@ -428,37 +578,31 @@ class _EGNNFunction(torch.autograd.Function):
             if cache is None or cache[0] != key:
                 free = torch.cuda.mem_get_info(hc.device)[0] + (torch.cuda.memory_reserved(hc.device) -
                                                                 torch.cuda.memory_allocated(hc.device))
-                # (the keeping forward stores its activation chunks through a 32-bit buffer descriptor: E x Wx x 2 B < 4 GiB)
-                cache = (key, need < 0.5 * free and E * Wx * 2 < 2 ** 32)
-                c._keep_decision = cache
+                cache = c._keep_decision = (key, decide_keep(prec, E, len(layers), Wx, Wm, M, sw, True, free))
             if cache[1]:
                 kept = []
-            c.last_backward_path = "kept activations" if cache[1] else "recompute"
-        elif E > 0 and prec == _lib.PREC_BF16:
-            c.last_backward_path = "recompute"   # EGNN_BWD_SAVE=0 / unsupported shapes: nothing is kept
+        if E > 0 and prec == _lib.PREC_BF16:   # (bench.py reads it; EGNN_BWD_SAVE=0 / unsupported shapes: nothing is kept)
+            c.last_backward_path = "kept activations" if kept is not None else "recompute"
         for l in range(len(layers)):
             ho, xo = torch.empty_like(hc), torch.empty_like(xc)
             if kept is not None:
                 bf = dict(dtype=torch.bfloat16, device=hc.device)
                 bufs = [torch.empty(Epad, Wx, **bf), torch.empty(Epad, Wm, **bf), torch.empty(Epad, Wx, **bf),
                         torch.empty(Epad, M, **bf), torch.empty(max(Wx // 512, 1), E, device=hc.device)]
-                if os.environ.get("EGNN_DEBUG_POISON_KEPT", "0") == "1":   # (tests: an element the forward leaves unwritten and
-                    for t in bufs:                                            # the backward reads shows up as NaN)
+                if sw["POISON_KEPT"]:   # (tests: an element the forward leaves unwritten and the backward reads shows up as NaN)
+                    for t in bufs:
                         t.fill_(float("nan"))
                 if Epad > E:
                     for t in bufs[:4]:
                         t[E:].zero_()
-                _lib.check(L.egcl_forward_save(c.handle, _lib.stream_ptr(), l, scope, _lib.ptr(hc), _lib.ptr(xc), _lib.ptr(ho),
-                                               _lib.ptr(xo), *[_lib.ptr(t) for t in bufs]))
+                _lib.check(L.egcl_forward_save(c.handle, _lib.stream_ptr(), l, scope, P(hc), P(xc), P(ho), P(xo), *[P(t) for t in bufs]))
                 kept.append(bufs)
             else:
-                _lib.check(L.egcl_forward(c.handle, _lib.stream_ptr(), l, prec, scope, _lib.ptr(hc), _lib.ptr(xc),
-                                          _lib.ptr(ho), _lib.ptr(xo)))
+                _lib.check(L.egcl_forward(c.handle, _lib.stream_ptr(), l, prec, scope, P(hc), P(xc), P(ho), P(xo)))
             sum_m = torch.empty(hc.shape[0], layers[l].dims["M"], device=hc.device)
             sum_x = torch.empty(hc.shape[0], 3, device=hc.device)
             S = torch.empty(nseg, device=hc.device)
-            _lib.check(L.egcl_read_aggregates(c.handle, _lib.stream_ptr(), scope, _lib.ptr(sum_m), _lib.ptr(sum_x),
-                                              _lib.ptr(S)))
+            _lib.check(L.egcl_read_aggregates(c.handle, _lib.stream_ptr(), scope, P(sum_m), P(sum_x), P(S)))
             saved += [hc, xc, sum_m, sum_x, S]
             hc, xc = ho, xo
         ctx.layers, ctx.plan, ctx.scope, ctx.prec, ctx.egnn_ctx, ctx.kept = layers, plan, scope, prec, c, kept
@@ -467,89 +611,42 @@ class _EGNNFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gh, gx):
-        layers, plan, prec = ctx.layers, ctx.plan, ctx.prec
-        global _SPLIT_PRODUCTS
-        _SPLIT_PRODUCTS = (os.environ.get("EGNN_BWD_BLAS", "0") != "1" and
-                           (prec in (_lib.PREC_BF16X3, _lib.PREC_F16C8) or os.environ.get("EGNN_BWD_OWN", "0") == "1"))
-        if prec in (_lib.PREC_BF16X3, _lib.PREC_F16C8):   # forward on the split-operand kernels; the backward is the fp32 chain of
-            prec = _lib.PREC_F32                          # stage kernels with head + remainder products on the own GEMM kernels
-        if prec == _lib.PREC_F16:      # forward on fp16 operands; the backward recomputes on the bf16 kernels
-            prec = _lib.PREC_BF16
+        global LAST_PLAN, LAST_FIRST_LAYER_FORM
+        layers, graph, c, sw = ctx.layers, ctx.plan, ctx.egnn_ctx, _switches()
         scope_graph = ctx.scope == _lib.NORM_GRAPH
         saved = ctx.saved_tensors
-        dst32, src32 = plan.edge_dst, plan.edge_src
-        node_graph = plan.node_graph.long()
-        node_seg = plan.node_graph if scope_graph else None   # int32 segment of the d^2 sum each node belongs to
+        node_graph = graph.node_graph.long()
+        node_seg = graph.node_graph if scope_graph else None   # int32 segment of the d^2 sum each node belongs to
         gh = torch.zeros_like(saved[0]) if gh is None else gh.contiguous().float()
         gx = torch.zeros_like(saved[1]) if gx is None else gx.contiguous().float()
         grads = {}
-        d0 = layers[0].dims
-        E = dst32.numel()
-        ws = None
+        d0, E = layers[0].dims, graph.edge_dst.numel()
+        Wx, Wm = layers[0].mlp_x[0].out_features, layers[0].mlp_m[0].out_features
         # the kept activations are spent by the first backward (dL/da2 is written over them): a second backward through
-        # the same graph (retain_graph=True) falls back to the recompute path
+        # the same graph (retain_graph=True) is planned as recompute
         kept = ctx.kept if ctx.kept is not None and all(k is not None for k in ctx.kept) else None
-        if E > 0:
-            pass
-        # bf16 at the reference widths: the recompute half of the edge backward runs on the forward's MFMA edge kernels
-        c = ctx.egnn_ctx
-        use_fused = kept is not None or (E > 0 and prec == _lib.PREC_BF16 and os.environ.get("EGNN_BWD_FUSED", "1") != "0")
-        if use_fused:
-            c.set_graph(plan)
+        supported = False
+        if fused_asked(ctx.prec, E, kept is not None, sw):
+            c.set_graph(graph)
             c.pack(layers)
-            use_fused = bool(_lib.lib().egcl_backward_fused_supported(c.handle))
+            supported = bool(_lib.lib().egcl_backward_fused_supported(c.handle))
+        bp = LAST_PLAN = plan_backward(ctx.prec, d0["H"], Wx, Wm, d0["M"], layers[0].mlp_h[0].weight.shape[0], E, EDGE_CHUNK,
+                                       getattr(graph, "graph_edge_ptr", None), getattr(graph, "max_graph_nodes", 1 << 30),
+                                       kept is not None, supported, sw)
         if E > 0:
-            Wx_, Wm_ = layers[0].mlp_x[0].out_features, layers[0].mlp_m[0].out_features
-            ws = _Workspace(min(EDGE_CHUNK, E), d0["H"], Wx_, Wm_, d0["M"],
-                            torch.bfloat16 if prec == _lib.PREC_BF16 else torch.float32, gh.device,
-                            saved_activations=kept is not None,
-                            hip_gemms=use_fused and prec == _lib.PREC_BF16 and _hip_gemm_shapes(d0["H"], Wx_, Wm_, d0["M"]))
+            LAST_FIRST_LAYER_FORM = bp.first
+            ws = _Workspace(bp, Wx, Wm, d0["M"], gh.device)
         for l in reversed(range(len(layers))):
             layer = layers[l]
             h_l, x_l, sum_m, sum_x, S = saved[5 * l:5 * l + 5]
-            # node part
-            zero = lambda o, like: o.clone() if o is not None else torch.zeros_like(like)
-            node_hip = (ws is not None and ws.hip_gemms and prec == _lib.PREC_BF16 and h_l.shape[1] <= 64 and
-                        layer.mlp_h[0].weight.shape[0] % 256 == 0)
-            if node_hip:
-                # x' = x + sum_x / (G + 1) (:64, :70): element-wise, differentiated by torch; the node MLP on the own GEMMs
-                with torch.enable_grad():
-                    x_leaf = x_l.detach().requires_grad_(True)
-                    ax, S_leaf = sum_x.detach().requires_grad_(True), S.detach().requires_grad_(True)
-                    x_new = x_leaf + ax * _segment_scale(S_leaf, scope_graph, node_graph)
-                    o = torch.autograd.grad([x_new], [x_leaf, ax, S_leaf], [gx], allow_unused=True)
-                g_x, g_ax, g_S = zero(o[0], x_l), zero(o[1], sum_x), zero(o[2], S)
-                g_h, g_am = _node_backward_hip(layer, h_l, sum_m, gh, grads)
-            elif _own_fp32_products() and h_l.dtype == torch.float32:
-                # the same formulas with head + remainder products (no BLAS library): fp32 element-wise stages by torch
-                with torch.enable_grad():
-                    x_leaf = x_l.detach().requires_grad_(True)
-                    ax, S_leaf = sum_x.detach().requires_grad_(True), S.detach().requires_grad_(True)
-                    x_new = x_leaf + ax * _segment_scale(S_leaf, scope_graph, node_graph)
-                    o = torch.autograd.grad([x_new], [x_leaf, ax, S_leaf], [gx], allow_unused=True)
-                g_x, g_ax, g_S = zero(o[0], x_l), zero(o[1], sum_x), zero(o[2], S)
-                g_h, g_am = _node_backward_split(layer, h_l, sum_m, gh, grads)
+            if bp.node == "torch":
+                g_h, g_am, g_x, g_ax, g_S = _node_backward_torch(layer, h_l, sum_m, gh, grads, x_l, sum_x, S, gx, scope_graph, node_graph)
             else:
-                node_params = list(layer.mlp_h.parameters())
-                with torch.enable_grad():
-                    h_leaf = h_l.detach().requires_grad_(True)
-                    x_leaf = x_l.detach().requires_grad_(True)
-                    am, ax = sum_m.detach().requires_grad_(True), sum_x.detach().requires_grad_(True)
-                    S_leaf = S.detach().requires_grad_(True)
-                    h_new = layer.mlp_h(torch.cat((h_leaf, am), dim=1))
-                    x_new = x_leaf + ax * _segment_scale(S_leaf, scope_graph, node_graph)
-                    outs = torch.autograd.grad([h_new, x_new], [h_leaf, x_leaf, am, ax, S_leaf] + node_params, [gh, gx],
-                                               allow_unused=True)
-                g_h, g_x = zero(outs[0], h_l), zero(outs[1], x_l)
-                g_am, g_ax, g_S = zero(outs[2], sum_m), zero(outs[3], sum_x), zero(outs[4], S)
-                for p, g in zip(node_params, outs[5:]):
-                    if g is not None:
-                        grads[p] = g if p not in grads else grads[p] + g
-            # edge part
+                g_x, g_ax, g_S = _coordinate_backward(x_l, sum_x, S, gx, scope_graph, node_graph)
+                g_h, g_am = (_node_backward_hip if bp.node == "hip" else _node_backward_split)(layer, h_l, sum_m, gh, grads)
             if E > 0:
-                _edge_backward(layer, prec, ws, h_l, x_l, dst32, src32, node_seg, g_am, g_ax, g_S.contiguous(), g_h, g_x, grads,
-                               fused=(c.handle, l) if use_fused else None,
-                               kept=kept[l] if kept is not None else None, plan=plan)
+                _edge_backward(bp, layer, ws, (c.handle if bp.fused else None, l), kept[l] if kept is not None else None, h_l, x_l,
+                               graph, node_seg, g_am, g_ax, g_S.contiguous(), g_h, g_x, grads)
                 if kept is not None:
                     ctx.kept[l] = None   # this layer's buffers are spent
             gh, gx = g_h, g_x

@@ -78,7 +78,7 @@ def geometry(x, dst, src, model=False):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 def tables(h, W1, b1, H, model=False):
-    """P = h W1[:, :H]^T + b1, Q = h W1[:, H:2H]^T, wd = W1[:, 2H] (egcl_backward_table; generic chain: autograd.py:179-187).
+    """P = h W1[:, :H]^T + b1, Q = h W1[:, H:2H]^T, wd = W1[:, 2H] (egcl_backward_table; generic chain: autograd.py:_first_layer_operands).
     model: the fast path's table -- weights and bias times -log2(e) rounded to fp32 (egnn_forward.hip:1626-1630 scale_copy),
     entries clamped to +-32000 and rounded to fp16 (egnn_forward.hip:165 table_store); returns SCALED values."""
     h, W1, b1 = d(h), d(W1), d(b1)
@@ -274,8 +274,8 @@ def scatter(g_in, g_diff, g_S, node_seg, diff, dst, src, H, g_h, g_x):
 def edge_backward(params, H, h, x, dst, src, node_graph, node_seg, B, g_sum_m, g_sum_x, g_S, form):
     """dL/dh, dL/dx (edge part) and the twelve parameter gradients from the stage functions in exact mode.
     params: dict with the keys mlp_x.0 / mlp_x.2 / mlp_x.4 / mlp_m.0 / mlp_m.2 / attention.0 + .weight / .bias.
-    form "chain": gather -> wgrad GEMMs over the edges -> scatter (autograd.py:291-301);
-    form "factorised": first_reduce + node-level products (autograd.py:306-331)."""
+    form "chain": gather -> wgrad GEMMs over the edges -> scatter (autograd.py:_first_own / _first_library);
+    form "factorised": first_reduce + node-level products (autograd.py:_finish_graph / _finish_reduce)."""
     p = {k: d(v) for k, v in params.items()}
     h, N = d(h), h.shape[0]
     diff, d2 = geometry(x, dst, src)

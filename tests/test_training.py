@@ -152,6 +152,8 @@ def test_gradients_full_width_64_atom_graphs(first_layer, sizes, monkeypatch):
             grads[prec] = {k: p.grad.detach().cpu() for k, p in m.named_parameters()}
             if prec in ("bf16", "fp16"):   # the form under test is the one that ran
                 assert _ag.LAST_FIRST_LAYER_FORM == {"chain": None, "factorised": "reduce", "graph": "graph"}[first_layer]
+                bp = _ag.LAST_PLAN
+                assert (bp.first, bp.fused, bp.hip_gemms, bp.node, bp.kept) == (_ag.LAST_FIRST_LAYER_FORM, True, True, "hip", prec == "bf16")
             if prec in ("fp32", "bf16x3", "f16c8"):
                 assert abs(float(loss.detach()) - float(loss_ref.detach())) <= 1e-4 * abs(float(loss_ref.detach()))
                 assert rel_err(ex.detach().cpu(), ex_ref.detach()) <= 1e-4 and rel_err(eh.detach().cpu(), eh_ref.detach()) <= 1e-4
@@ -584,6 +586,7 @@ def test_graph_form_backward_against_the_chain_and_fp32_incl_input_gradients(gra
         ho, xo = m(plan, h, x)
         ((ho * wh.to(dev)).sum() + (xo * wx.to(dev)).sum()).backward()
         assert _ag.LAST_FIRST_LAYER_FORM == ("graph" if form == "1" else None)
+        assert _ag.LAST_PLAN.first == _ag.LAST_FIRST_LAYER_FORM and _ag.LAST_PLAN.fused == _ag.LAST_PLAN.kept == (prec == "bf16")
         grads = {k: p.grad.detach().cpu() for k, p in m.named_parameters()}
         grads["input.h"], grads["input.x"] = h.grad.detach().cpu(), x.grad.detach().cpu()
         out[(form, prec)] = (ho.detach().cpu(), grads)
@@ -661,6 +664,8 @@ def test_input_and_parameter_gradients_match_oracle_autograd(form, graphs, monke
         if prec == "bf16":     # the form under test is the one that ran (fp16 forwards recompute on the bf16 kernels)
             assert _ag.LAST_FIRST_LAYER_FORM == {"graph": "graph", "chain": None, "factorised": "reduce", "recompute": "graph"}[form]
             assert m._ctx.last_backward_path == ("recompute" if form == "recompute" else "kept activations")
+            bp = _ag.LAST_PLAN
+            assert (bp.first, bp.kept, bp.fused, bp.hip_gemms, bp.node) == (_ag.LAST_FIRST_LAYER_FORM, form != "recompute", True, True, "hip")
         e_par = {k: rel_err(p.grad.detach().cpu(), want[k]) for k, p in m.named_parameters()}
         e_h, e_x = rel_err(h.grad.detach().cpu(), hr.grad), rel_err(x.grad.detach().cpu(), xr.grad)
         multi = {k: e for k, e in e_par.items() if want[k].numel() > 1}
@@ -673,6 +678,66 @@ def test_input_and_parameter_gradients_match_oracle_autograd(form, graphs, monke
     for prec, got in results.items():
         for name, g_, t_ in zip(("parameter tensors", "one-element parameters", "dL/dh", "dL/dx"), got, _INPUT_GRAD_TOL[prec]):
             assert g_ <= t_, (graphs, form, prec, name, g_, t_)
+
+
+# Fused kernels WITHOUT the library's own GEMMs: H = 64 makes in = [h_i | h_j | d2 | 1] 130 columns wide, more than the 128 of
+# gemm_tn.hip / gemm_rows.hip, so the context-handle kernels (heads_saved / edge_recompute, dgrad) run between library products
+# (_wgrad, _mm on bf16 buffers, the -ln 2 fix-up of the second-layer weight gradients) and torch's node MLP.
+# Bars: 1.5 x the measurement of the four quantities on the commit before the backward plan, which runs the same path
+# (profiles/bwd_plan_ab.txt), per case (parameter tensors, one-element parameters, dL/dh, dL/dx):
+#   kept      8.22e-3 (egcl_list.1.mlp_x.0.bias) / 7.16e-3 (egcl_list.0.attention.0.bias) / 4.94e-3 / 2.59e-3
+#   recompute 8.54e-3 (egcl_list.1.mlp_x.0.bias) / 8.19e-3 (egcl_list.0.attention.0.bias) / 4.89e-3 / 2.79e-3
+_H64_TOL = {"1": (1.23e-2, 1.07e-2, 7.4e-3, 3.87e-3), "0": (1.28e-2, 1.22e-2, 7.3e-3, 4.18e-3)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("save", ["1", "0"], ids=["kept", "recompute"])
+def test_fused_kernels_without_own_gemms_match_oracle_autograd(save, monkeypatch):
+    from diffusion_model_amd import autograd as _ag
+    from oracle.egnn_ref import egnn_forward as oracle_forward
+    H = 64
+    d = dims_for(H, 256, 256, 256, 256)
+    sizes = (64, 1, 33, 2, 17, 50)                        # the fully connected batch of tests/test_gpu_bwd_stages.py: 7,812 edges
+    n = sum(sizes)
+    dev = "cuda"
+    g = torch.Generator().manual_seed(12)
+    h0, x0 = torch.randn(n, H, generator=g), torch.randn(n, 3, generator=g) * 1.5
+    wh, wx = torch.randn(n, H, generator=g), torch.randn(n, 3, generator=g)
+    monkeypatch.setattr(_ag, "EDGE_CHUNK", 4300)          # two chunks, the second not a multiple of 64 rows
+    monkeypatch.setenv("EGNN_BWD_SAVE", save)
+    plan = dma.fully_connected_plan(list(sizes), torch.device(dev))
+    ei = dma.plan_edge_index(plan).cpu()
+    ptr = torch.tensor([0] + torch.cumsum(torch.tensor(sizes), 0).tolist())
+    torch.manual_seed(9)
+    ref_net = dma.EquivariantGNN(2, **d)
+    sd = {k: v.detach().clone().requires_grad_(True) for k, v in ref_net.state_dict().items()}
+    hr, xr = h0.clone().requires_grad_(True), x0.clone().requires_grad_(True)
+    ho_r, xo_r = oracle_forward(sd, ei, hr, xr, "graph", ptr)
+    ((ho_r * wh).sum() + (xo_r * wx).sum()).backward()
+    want = {k: v.grad for k, v in sd.items()}
+    m = dma.EquivariantGNN(2, **d)
+    m.load_state_dict({k: v.detach() for k, v in sd.items()})
+    m.to(dev).train()
+    m.precision, m.norm_scope = "bf16", "graph"
+    h = h0.to(dev).requires_grad_(True)
+    x = x0.to(dev).requires_grad_(True)
+    ho, xo = m(plan, h, x)
+    ((ho * wh.to(dev)).sum() + (xo * wx.to(dev)).sum()).backward()
+    bp = _ag.LAST_PLAN
+    assert bp.fused and not bp.hip_gemms and bp.first is None and bp.kept == (save == "1")
+    assert (bp.node, bp.K1P, bp.chunks) == ("torch", 136, ((0, 4352), (4352, 3460)))
+    assert m._ctx.last_backward_path == ("kept activations" if save == "1" else "recompute")
+    e_par = {k: rel_err(p.grad.detach().cpu(), want[k]) for k, p in m.named_parameters()}
+    e_h, e_x = rel_err(h.grad.detach().cpu(), hr.grad), rel_err(x.grad.detach().cpu(), xr.grad)
+    multi = {k: e for k, e in e_par.items() if want[k].numel() > 1}
+    single = {k: e for k, e in e_par.items() if want[k].numel() == 1}
+    wm, ws1 = max(multi, key=multi.get), max(single, key=single.get)
+    print(f"input gradients vs oracle autograd [H = 64, fused without own GEMMs, SAVE={save}] bf16: dL/dh {e_h:.2e} dL/dx {e_x:.2e} "
+          f"parameter tensors worst {multi[wm]:.2e} ({wm}), one-element parameters worst {single[ws1]:.2e} ({ws1})")
+    assert torch.isfinite(h.grad).all() and torch.isfinite(x.grad).all()
+    for name, g_, t_ in zip(("parameter tensors", "one-element parameters", "dL/dh", "dL/dx"), (multi[wm], single[ws1], e_h, e_x),
+                            _H64_TOL[save]):
+        assert g_ <= t_, (save, name, g_, t_)
 
 
 @pytest.mark.gpu

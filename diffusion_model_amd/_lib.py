@@ -15,6 +15,8 @@ OPTIM_ADAM, OPTIM_ADAMW_AMSGRAD, OPTIM_RADAM_SF = 0, 1, 2
 KABSCH_CENTERS = {"centroid": 0, "first": 1}
 KABSCH_FLIPS = {"row": 0, "column": 1}
 ASSIGN_MAX_ATOMS = 1024   # EGNN_ASSIGN_MAX_ATOMS of include/egnn_amd.h (kAssignMaxAtoms)
+STRUCT_MAX_TYPES, STRUCT_MAX_ATOMS = 4, 32768   # kStructMaxTypes, kStructMaxAtoms of csrc/eval/structure_math.h
+STRUCT_CENTRE_BLOCK, STRUCT_CHUNK, STRUCT_BOND_CENTRES = 64, 1024, 8   # the tiles of egnn_struct_pair_counts / egnn_struct_bonds
 PREALIGN_MIN_ATOMS = 5    # kPrealignMinAtoms of csrc/eval/assign_host.h: atom 0 and its four nearest neighbours
 
 
@@ -153,6 +155,10 @@ SIGNATURES = {
     "egnn_kabsch_perm": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
     "egnn_assign": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "egnn_assign_prealign": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "egnn_struct_pair_counts": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, C.c_double, _i, _vp]),
+    "egnn_struct_bonds": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _f, C.c_double, _i, _vp, _vp, _vp]),
+    "egnn_struct_rdf_finish": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _i, _vp]),
+    "egnn_struct_counts_host": (_i, [_i, _i, _vp, _vp, _vp, C.c_double, _i, _f, C.c_double, _i, _vp, _vp, _vp, _vp]),
     "egnn_optim_step": (_i, [_vp, _i, _i, _pp, _pp, _pp, _pp, _pp, _i64p, C.POINTER(OptimConsts)]),
     "egnn_optim_interp": (_i, [_vp, _i, _pp, _pp, _i64p, _f]),
     "egnn_optim_tensors_per_launch": (_i, []),

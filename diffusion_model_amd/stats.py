@@ -429,3 +429,175 @@ def align_by_assignment(original_graph_list, generated_graph_list, min_atoms=6):
         rows.append((f"{original.id}_{i % 5 + 1}", float(rmsd[i]), np.arange(n), col[sl].numpy().astype(np.int64), oc[sl].clone(),
                      matched[sl].clone(), original.x.detach().cpu().clone(), xr[sl].to(gens[i].x.dtype)))
     return rows
+
+
+# ---- whole-structure statistics (csrc/eval/structure.hip) ----------------------------------------------------------
+def _struct_tiles(sizes):
+    """The work lists of egnn_struct_pair_counts and egnn_struct_bonds (include/egnn_amd.h) from the graph sizes, on the host:
+    pair tiles {g, c0, j0} for every (64-centre block, 1024-atom neighbour chunk) of every graph -- so that 256 graphs of 64 atoms,
+    32 of 512 and one of 4096 atoms all give 256 workgroups -- and bond tiles {g, c0, 0} for every block of 8 centres.
+    -> (int32 [n_pair, 3], int32 [n_bond, 3])"""
+    sz = np.asarray(list(sizes), dtype=np.int64)
+    g = np.arange(sz.size, dtype=np.int64)
+
+    def blocks(per_graph):
+        gi = np.repeat(g, per_graph)
+        return gi, np.arange(int(per_graph.sum()), dtype=np.int64) - np.repeat(np.cumsum(per_graph) - per_graph, per_graph)
+
+    n_cb, n_jb = -(-sz // _lib.STRUCT_CENTRE_BLOCK), -(-sz // _lib.STRUCT_CHUNK)
+    gi, t = blocks(n_cb * n_jb)
+    pair = np.stack([gi, (t // n_jb[gi]) * _lib.STRUCT_CENTRE_BLOCK, (t % n_jb[gi]) * _lib.STRUCT_CHUNK], 1)
+    gi, t = blocks(-(-sz // _lib.STRUCT_BOND_CENTRES))
+    bond = np.stack([gi, t * _lib.STRUCT_BOND_CENTRES, np.zeros_like(t)], 1)
+    return pair.astype(np.int32).reshape(-1, 3), bond.astype(np.int32).reshape(-1, 3)
+
+
+class _StructInput:
+    """positions, type indices and the work lists of a batch on the device (one upload of graph_ptr and both tile lists)"""
+
+    def __init__(self, pos, onehot, sizes, what):
+        if not pos.is_cuda:
+            raise RuntimeError(f"{what} needs CUDA(ROCm) tensors; there is no CPU fallback")
+        sizes = [int(s) for s in sizes]
+        self.sizes, self.B, self.N = sizes, len(sizes), sum(sizes)
+        if self.B < 1 or min(sizes) < 0:
+            raise ValueError(f"{what} needs at least one graph and no negative size")
+        if pos.shape != (self.N, 3):
+            raise ValueError("position must be [sum(sizes), 3]")
+        oh = onehot.detach().to(pos.device)
+        if oh.dim() != 2 or oh.shape[0] != self.N or oh.shape[1] < 1:
+            raise ValueError("onehot must be [sum(sizes), A]")
+        self.A = int(oh.shape[1])
+        if self.N and not bool((((oh == 0) | (oh == 1)).all(1) & (oh.sum(1) == 1)).all()):
+            raise ValueError("every row of onehot must be exactly one-hot")
+        self.dev = pos.device
+        self.pos = pos.detach().to(torch.float32).contiguous()
+        self.type = (oh.argmax(1) if self.N else torch.zeros(0, dtype=torch.long, device=self.dev)).to(torch.int32).contiguous()
+        self.max_atoms = max(sizes)
+        pair, bond = _struct_tiles(sizes)
+        gp = np.zeros(self.B + 1, dtype=np.int64)
+        gp[1:] = np.cumsum(sizes)
+        blob = torch.from_numpy(np.concatenate([gp.astype(np.int32), pair.reshape(-1), bond.reshape(-1)])).to(self.dev)
+        self.gp, self.pair_tiles, self.bond_tiles = blob.split([self.B + 1, pair.size, bond.size])
+        self.n_pair, self.n_bond = len(pair), len(bond)
+
+    def n_type(self):
+        gid = torch.repeat_interleave(torch.arange(self.B, device=self.dev), torch.tensor(self.sizes, device=self.dev), output_size=self.N)
+        return torch.zeros(self.B * self.A, dtype=torch.int64, device=self.dev).index_add_(
+            0, gid * self.A + self.type.long(), torch.ones(self.N, dtype=torch.int64, device=self.dev)).view(self.B, self.A)
+
+
+def _nbins(R, dR):
+    return len(np.arange(0 + dR, R + dR, dR))
+
+
+def _pair_counts(inp, R, dR):
+    nbins = _nbins(R, dR)
+    counts = torch.empty(inp.B, inp.A, inp.A, nbins, dtype=torch.int32, device=inp.dev)
+    _lib.check(_lib.lib().egnn_struct_pair_counts(_lib.stream_ptr(), inp.B, inp.A, _lib.ptr(inp.pos), _lib.ptr(inp.type), _lib.ptr(inp.gp),
+                                                  inp.max_atoms, _lib.ptr(inp.pair_tiles), inp.n_pair, float(dR), nbins, _lib.ptr(counts)))
+    return counts
+
+
+def _rdf_finish(inp, counts, sigma, R, dR):
+    out = torch.empty(counts.shape, dtype=torch.float32, device=inp.dev)
+    _lib.check(_lib.lib().egnn_struct_rdf_finish(_lib.stream_ptr(), inp.B, inp.A, _lib.ptr(counts), _lib.ptr(inp.type), _lib.ptr(inp.gp),
+                                                 float(R), float(dR), float(sigma), int(counts.shape[-1]), _lib.ptr(out)))
+    return out
+
+
+def _bonds(inp, cutoff, dtheta, max_cn):
+    """-> (cn int32, angles int32, overflow int32 [B]): the raw outputs of egnn_struct_bonds"""
+    dtheta, max_cn = float(dtheta), int(max_cn)
+    nth = int(np.floor(180.0 / dtheta + 0.5)) + 1 if dtheta > 0 else 1
+    cn = torch.empty(inp.B, inp.A, inp.A, max(max_cn, 0) + 1, dtype=torch.int32, device=inp.dev)
+    ang = torch.empty(inp.B, inp.A, inp.A * (inp.A + 1) // 2, max(nth, 1), dtype=torch.int32, device=inp.dev)
+    over = torch.empty(inp.B, dtype=torch.int32, device=inp.dev)
+    _lib.check(_lib.lib().egnn_struct_bonds(_lib.stream_ptr(), inp.B, inp.A, _lib.ptr(inp.pos), _lib.ptr(inp.type), _lib.ptr(inp.gp),
+                                            inp.max_atoms, _lib.ptr(inp.bond_tiles), inp.n_bond, float(cutoff), dtheta, max_cn,
+                                            _lib.ptr(cn), _lib.ptr(ang), _lib.ptr(over)))
+    return cn, ang, over
+
+
+def _raise_on_overflow(over):
+    bad = torch.nonzero(over > 0)
+    if bad.numel():
+        g = int(bad[0])
+        raise RuntimeError(f"graph {g}: {int(over[g])} centre(s) with more than 64 bonded neighbours; their angles are not taken "
+                           "(lower the cutoff)")
+
+
+def pair_counts(pos: torch.Tensor, onehot: torch.Tensor, sizes: Sequence[int], R=5.0, dR=0.01) -> torch.Tensor:
+    """Ordered-pair counts by type over EVERY centre: int64 [B, A, A, nbins], c[g, a, b, k] = number of pairs i != j of graph g
+    with type(i) = a, type(j) = b and |p_j - p_i| in radial bin k -- length_from_exO and the counting loop of RDF
+    (evaluate_RDF.py:39-56) taken about every atom instead of atom 0, with rdf()'s bins (nbins = len(np.arange(dR, R + dR, dR)))
+    and its edge rule.  ``onehot`` [N, A] must be exactly one-hot (A <= 4); graphs of at most 32768 atoms."""
+    inp = _StructInput(pos, onehot, sizes, "pair_counts")
+    return _pair_counts(inp, R, dR).long()
+
+
+def partial_rdf(pos: torch.Tensor, onehot: torch.Tensor, sizes: Sequence[int], sigma=5, R=5.0, dR=0.01) -> torch.Tensor:
+    """Partial pair distributions g_ab of every graph: float32 [B, A, A, nbins], g[g, a, b] = gaussian_filter1d(c[g, a, b] /
+    max(n_a, 1) / (4 pi rho r^2 dR), sigma) with the reference's normaliser rho = n / (4/3 pi R^3) over ALL atoms of the graph
+    (evaluate_RDF.py:50-57).  The sum over b is the mean over the centres i of type a of the reference's RDF(roll(position, i));
+    an absent type gives rows of zeros."""
+    inp = _StructInput(pos, onehot, sizes, "partial_rdf")
+    return _rdf_finish(inp, _pair_counts(inp, R, dR), sigma, R, dR)
+
+
+def bond_statistics(pos: torch.Tensor, onehot: torch.Tensor, sizes: Sequence[int], cutoff=2.0, dtheta=1.0, max_cn=16):
+    """Coordination numbers and bond angles over every centre (j is bonded to i iff |p_j - p_i| < cutoff, the selection of
+    evaluate_Si-O-Si.py:23-41; the angle of CN2_evaluate.py:12-16 in fp64):
+    -> (cn int64 [B, A, A, max_cn+1], angles int64 [B, A, A(A+1)/2, ntheta]).  cn[g, a, b, m] = centres of type a with m bonded
+    neighbours of type b (the last bin: max_cn or more); angles[g, a, p, k] = bonded pairs j < k about centres of type a with
+    neighbour types (b <= c), p = b A - b(b-1)/2 + c - b, whose angle falls in the bin centred on k dtheta degrees
+    (ntheta = floor(180/dtheta + 0.5) + 1).  Raises RuntimeError, naming the first such graph, if a centre has more than 64 bonds."""
+    inp = _StructInput(pos, onehot, sizes, "bond_statistics")
+    cn, ang, over = _bonds(inp, cutoff, dtheta, max_cn)
+    _raise_on_overflow(over)
+    return cn.long(), ang.long()
+
+
+def structure_profile(pos: torch.Tensor, onehot: torch.Tensor, sizes: Sequence[int], sigma=5, R=5.0, dR=0.01, cutoff=2.0, dtheta=1.0,
+                      max_cn=16):
+    """pair_counts, partial_rdf, bond_statistics of one batch from one collation: a namespace with pair_counts, partial_rdf, cn,
+    angles (as those functions return them) and n_type int64 [B, A], the atoms of every type."""
+    from types import SimpleNamespace
+    inp = _StructInput(pos, onehot, sizes, "structure_profile")
+    counts = _pair_counts(inp, R, dR)
+    rdf_ = _rdf_finish(inp, counts, sigma, R, dR)
+    cn, ang, over = _bonds(inp, cutoff, dtheta, max_cn)
+    _raise_on_overflow(over)
+    return SimpleNamespace(pair_counts=counts.long(), partial_rdf=rdf_, cn=cn.long(), angles=ang.long(), n_type=inp.n_type(),
+                           sizes=list(inp.sizes))
+
+
+def _curve_metrics(a, b):
+    """cos_similarity / rdf_l2 / rdf_mse / wasserstein of curves along the last axis, batched on the device in float64 (equal
+    lengths: W1 of two samples is the mean distance of their sorted values)"""
+    a, b = a.double(), b.double()
+    diff = a - b
+    return dict(cos=(a * b).sum(-1) / (torch.linalg.vector_norm(a, dim=-1) * torch.linalg.vector_norm(b, dim=-1)),
+                l2=torch.linalg.vector_norm(diff, dim=-1), mse=(diff * diff).mean(-1),
+                wasserstein=(a.sort(-1).values - b.sort(-1).values).abs().mean(-1))
+
+
+def compare_structures(original_graph_list, generated_graph_list, sigma=5, R=5.0, dR=0.01, cutoff=2.0, dtheta=1.0, max_cn=16):
+    """Whole-structure comparison of what generate() returns with the originals (the list conventions of evaluate_by_rmsd): both
+    sides are collated once and profiled (structure_profile), then every partial RDF g_ab and every angle distribution of a sample
+    is compared with the original's by the reference's curve metrics (evaluate_RDF.py:13-37, :62-63, :82-83).
+    -> dict: 'rdf' and 'angles' = {cos, l2, mse, wasserstein} per graph (float64 [B, A, A] and [B, A, A(A+1)/2]; cos is NaN where
+    a curve is all zero), 'total' = the same metrics of the curves summed over all graphs ({'rdf': [A, A], 'angles': [A, P]}),
+    'cn_original' / 'cn_generated' int64 [B, A, A, max_cn+1], 'original' / 'generated' the two profiles, 'sizes'."""
+    col = _collate_pairs(original_graph_list, generated_graph_list, True)
+    if col is None:
+        return {}
+    sizes, _, po, pg, xo, xg = col
+    kw = dict(sigma=sigma, R=R, dR=dR, cutoff=cutoff, dtheta=dtheta, max_cn=max_cn)
+    o, g = structure_profile(po, xo, sizes, **kw), structure_profile(pg, xg, sizes, **kw)
+    if o.partial_rdf.shape != g.partial_rdf.shape:
+        raise ValueError("originals and samples differ in the number of atom types")
+    return dict(sizes=sizes, rdf=_curve_metrics(o.partial_rdf, g.partial_rdf), angles=_curve_metrics(o.angles, g.angles),
+                total=dict(rdf=_curve_metrics(o.partial_rdf.double().sum(0), g.partial_rdf.double().sum(0)),
+                           angles=_curve_metrics(o.angles.sum(0), g.angles.sum(0))),
+                cn_original=o.cn, cn_generated=g.cn, original=o, generated=g)

@@ -459,6 +459,49 @@ int egnn_assign(void* stream, int B, const float* d_P, const float* d_Q, const i
 int egnn_assign_prealign(void* stream, int B, const float* d_orig, const float* d_gen, const int32_t* d_graph_ptr, int min_atoms,
                          float* d_R, int32_t* d_prealigned);
 
+/* ---- whole-structure statistics (csrc/eval/structure.hip; definitions in csrc/eval/structure_math.h) --------------------
+ * The reference judges a structure by what surrounds atom 0: the RDF about it (evaluate_RDF.py:39-60), the atoms bonded to it
+ * (evaluate_Si-O-Si.py:23-41) and the angle they make (CN2_evaluate.py:12-21).  These entries take the same three statistics
+ * over EVERY centre of every graph, by atom type.  Atoms carry a type index d_type int32 [N] in [0, A), A <= 4; graphs through
+ * d_graph_ptr int32 [B+1]; max_atoms is the size of the largest graph, at most 32768 (the ordered pairs of one graph are counted
+ * in int32).  d_tiles int32 [n_tiles, 3] lists the work, one workgroup each, built from the graph sizes by the caller:
+ *   pair tiles  {g, c0, j0}: centres c0 .. c0+63 against neighbour atoms j0 .. j0+1023 of graph g (local indices), every
+ *               (multiple of 64, multiple of 1024) below the graph's size once;
+ *   bond tiles  {g, c0, 0}:  centres c0 .. c0+7 of graph g, every multiple of 8 below its size once.
+ * A kernel checks every entry against d_graph_ptr and reads no atom outside its graph; a tile listed twice is counted twice.
+ * All accumulators are integers (LDS atomics, then one global atomicAdd per non-zero bin): bitwise reproducible.  The outputs
+ * are zeroed by the call.  Bad arguments (nbins > 1024, A > 4, dtheta below 0.5 degrees = more than 361 angle bins, cutoff <= 0,
+ * max_cn outside [1, 64], max_atoms > 32768) return EGNN_EINVAL before anything is launched.
+ *
+ * egnn_struct_pair_counts generalises length_from_exO + the counting loop of RDF (evaluate_RDF.py:39-56): d_counts int32
+ * [B, A, A, nbins], c[g][a][b][k] = number of ordered pairs i != j of graph g with type(i) = a, type(j) = b and the float32
+ * distance sqrtf((dx*dx + dy*dy) + dz*dz) in bin k by egnn_rdf's rule, (float)(dR + k dR) < d < (float)(dR + k dR + dR). */
+int egnn_struct_pair_counts(void* stream, int B, int A, const float* d_pos, const int32_t* d_type, const int32_t* d_graph_ptr,
+                            int max_atoms, const int32_t* d_tiles, int n_tiles, double dR, int nbins, int32_t* d_counts);
+/* egnn_struct_bonds generalises the neighbour selection of evaluate_Si-O-Si.py:23-41 (j is bonded to i iff the float32 distance
+ * is below cutoff) and calculate_angle_for_CN2 (CN2_evaluate.py:12-16), one wavefront per centre:
+ *   d_cn int32 [B, A, A, max_cn+1]: cn[g][a][b][m] = centres of type a with m bonded neighbours of type b, m clamped to max_cn
+ *     (the last bin means "max_cn or more");
+ *   d_angles int32 [B, A, A(A+1)/2, nth], nth = floor(180/dtheta + 0.5) + 1: for centre i of type a and bonded neighbours j < k
+ *     of types (b <= c, pair index b A - b(b-1)/2 + c - b) the angle between the bond vectors, fp64 from the float32 positions,
+ *     in the bin floor(theta/dtheta + 0.5) CENTRED on a multiple of dtheta; a zero-length bond has no angle;
+ *   d_overflow int32 [B]: centres with more than 64 bonds; they are counted in d_cn, their angles are not taken. */
+int egnn_struct_bonds(void* stream, int B, int A, const float* d_pos, const int32_t* d_type, const int32_t* d_graph_ptr,
+                      int max_atoms, const int32_t* d_tiles, int n_tiles, float cutoff, double dtheta, int max_cn, int32_t* d_cn,
+                      int32_t* d_angles, int32_t* d_overflow);
+/* egnn_struct_rdf_finish generalises the normalisation and smoothing of RDF (evaluate_RDF.py:50-57): d_out float [B, A, A, nbins],
+ * g_ab(r_k) = gaussian_filter1d(c[g][a][b][.] / max(n_a, 1) / (4 pi rho r_k^2 dR), sigma) with rho = n / (4/3 pi R^3) over ALL
+ * atoms of the graph, fp64 inside.  The sum over b is the mean over the centres i of type a of RDF(roll(position, i)); an absent
+ * type gives rows of zeros. */
+int egnn_struct_rdf_finish(void* stream, int B, int A, const int32_t* d_counts, const int32_t* d_type, const int32_t* d_graph_ptr,
+                           double R, double dR, double sigma, int nbins, float* d_out);
+/* Host statement of egnn_struct_pair_counts + egnn_struct_bonds (evaluate_RDF.py:39-60, CN2_evaluate.py:12-21,
+ * evaluate_Si-O-Si.py:23-41 over every centre): HOST pointers, no GPU, no tiles, the same definitions in plain C++.  overflow may be
+ * NULL.  Types outside [0, A) and graphs above 32768 atoms are EGNN_EINVAL. */
+int egnn_struct_counts_host(int B, int A, const float* pos, const int32_t* type, const int32_t* graph_ptr, double dR, int nbins,
+                            float cutoff, double dtheta, int max_cn, int32_t* counts, int32_t* cn, int32_t* angles,
+                            int32_t* overflow);
+
 /* ---- the two small networks at the edge of the path ---------------------------------------------------
  * gamma_tilde(t_i) = l1(t_i) + l3(sigmoid(l2(l1(t_i)))) of GammaNetwork (SNR.py:50-52) with PositiveLinear's softplus weights
  * (:5-22) for n time points; d_l1_w [1], d_l2_w [hidden], d_l3_w [hidden] are the RAW parameters (l1.weight, l2.weight,

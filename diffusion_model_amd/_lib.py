@@ -48,17 +48,19 @@ def _sources_sha256(names) -> str:
 
 def edge_kernel_sources_sha256() -> str:
     """Fingerprint of the sources the dominant (edge) kernels are compiled from (every header they include, diag.h among them),
-    plus the compiler flags: what a PMC measurement of those kernels (profiles/traffic.json) is valid for.  A hash of the .so
-    itself would not survive a rebuild in another directory (hipcc derives its per-TU symbol ids from the path)."""
-    return _sources_sha256(("edge_x_m16.hip", "edge_bf16_v4.hip", "edge_tile.h", "kernels.h", "common.h", "diag.h"))
+    of the packing that writes the streams they read (pack.hip), and the compiler flags: what a PMC measurement of those kernels
+    (profiles/traffic.json) is valid for.  A hash of the .so itself would not survive a rebuild in another directory (hipcc
+    derives its per-TU symbol ids from the path)."""
+    return _sources_sha256(("edge_x_m16.hip", "edge_bf16_v4.hip", "pack.hip", "edge_tile.h", "kernels.h", "common.h", "layer_pack.h",
+                            "diag.h"))
 
 
 def forward_sources_sha256() -> str:
     """Fingerprint of every source an inference forward of any precision runs through (edge kernels of all precisions, node
     kernels, packing): what a measured error table (tools/prec_errors.py) is valid for."""
-    return _sources_sha256(("egnn_forward.hip", "edge_x_m16.hip", "edge_bf16_v4.hip", "edge_bf16_v3.hip", "edge_small.hip",
+    return _sources_sha256(("egnn_forward.hip", "pack.hip", "edge_x_m16.hip", "edge_bf16_v4.hip", "edge_bf16_v3.hip", "edge_small.hip",
                             "edge_bf16x3.hip", "edge_f16c8w.hip", "edge_f16c8w_mphase2.inc", "edge_f16c8w_mphasek.inc", "node_bf16.hip",
-                            "edge_tile.h", "kernels.h", "common.h", "diag.h"))
+                            "edge_tile.h", "kernels.h", "common.h", "layer_pack.h", "diag.h"))
 
 
 def training_sources_sha256() -> str:

@@ -500,7 +500,7 @@ int egcl_backward_edge_recompute(egnn_ctx* c, void* stream, int layer, const flo
     if (c->bwd_s) { (void)hipFree(c->bwd_s); c->bwd_s = nullptr; c->cap_bwd_s = 0; }
     EGNN_HIP(hipMalloc(reinterpret_cast<void**>(&c->bwd_s), (size_t)nsplit * n_edges * sizeof(float)));
     c->cap_bwd_s = (size_t)nsplit * n_edges;
-    const char* poison = getenv("EGNN_DEBUG_POISON");   // (tests: see dev_alloc in egnn_forward.hip)
+    const char* poison = getenv("EGNN_DEBUG_POISON");   // (tests: see dev_alloc in common.h)
     if (poison && poison[0] == '1') EGNN_HIP(hipMemset(c->bwd_s, 0xFF, c->cap_bwd_s * sizeof(float)));
   }
   int rc = backward_recompute(c, st, layer, x, g_sum_x, g_sum_m, e_first, n_edges, s1x, s1m, g_a2x, g_a2m, c->bwd_s, g_b2x,

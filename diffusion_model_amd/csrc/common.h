@@ -3,10 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <vector>
 
 #include "../../include/egnn_amd.h"
+#include "layer_pack.h"   // LayerPack: the packed parameters of one EGCL layer and the function that carves them
 #include "host_logic.h"   // set_error, padded model dimensions, argument checks, GEMM plan: the HIP-free part of the host side
 
 namespace egnn {
@@ -23,55 +25,27 @@ constexpr int kWaves = 4;
     }                                                                                       \
   } while (0)
 
-// Packed parameters of one EGCL layer (all device memory, owned by the context).
-struct LayerPack {
-  bool packed = false;
-  float* w1catT = nullptr;   // [H][TC]  transposed first-layer weights, columns = {Px|Qx|Pm|Qm}
-  float* b1cat = nullptr;    // [TC]     first-layer bias (P columns only)
-  float* wdx = nullptr;      // [WxP]    d^2 column of mlp_x.0
-  float* wdm = nullptr;      // [WmP]    d^2 column of mlp_m.0
-  float* w2x_f32 = nullptr;  // mlp_x.2 as f32 MFMA B fragments  [NB][KS4][64][4]
-  void* w2x_bf16 = nullptr;  // mlp_x.2 as bf16 MFMA B fragments [NB][KS][64][8]
-  float* b2x = nullptr;      // [WxP]
-  float* w3x = nullptr;      // [WxP]    mlp_x.4 weight
-  float* w2m_f32 = nullptr;  // mlp_m.2 fragments, N = MP, K = WmP
-  void* w2m_bf16 = nullptr;
-  float* b2m = nullptr;      // [MP]
-  float* wa = nullptr;       // [MP]     attention.0 weight
-  float* scal = nullptr;     // [4]      {mlp_x.4 bias, attention.0 bias}
-  float* w1h_f32 = nullptr;  // mlp_h.0 fragments, N = WhP, K = K1P (= pad8(H+MP))
-  float* b1h = nullptr;      // [WhP]
-  float* w2h_f32 = nullptr;  // mlp_h.2 fragments, N = HP, K = WhP
-  float* b2h = nullptr;      // [HP]
-  // bf16 fast path: SiLU is evaluated as t * rcp(1 + exp2(t)) on t = -log2(e) * z.  The first-layer table,
-  // biases and d^2 columns are pre-multiplied by -log2(e) and the following weights by -1/log2(e), which
-  // removes one multiply per SiLU.
-  float* sc = nullptr;       // [w1catT_s | b1cat_s | wdx_s | wdm_s | b2x_s | w3x_s | b2m_s | wa_s]
-  void* w2x_bf16s = nullptr;
-  void* w2m_bf16s = nullptr;
-  void* w2x_bf16s_lo = nullptr;   // bf16 remainders of the scaled second-layer weights (precision bf16x3)
-  void* w2m_bf16s_lo = nullptr;
-  void* w2x_bf16s16 = nullptr;  // mlp_x.2 scaled, as v_mfma_f32_16x16x32_bf16 B fragments [N/16][K/32][64][8]
-  void* w2m_bf16s16 = nullptr;  // mlp_m.2 scaled, same 16-column layout (edge_small.hip)
-  void* w2xT_bf16 = nullptr;  // mlp_x.2 TRANSPOSED bf16 fragments for the backward dgrad (k = output n, column = hidden k)
-  void* w2mT_bf16 = nullptr;  // mlp_m.2 transposed (K = MP, N = WmP)
-  void* w1hl_bf16 = nullptr;  // scaled first layers as bf16 hi/lo B fragments [TC/32][3][hi|lo][64][8] (node_pre_hilo_kernel)
-  void* w1h_bf16 = nullptr;   // mlp_h.0 bf16 fragments (N = WhP, K = K1Q)
-  void* w2h_bf16p = nullptr;  // mlp_h.2 bf16 fragments, k in accumulator-row order
-  // precision fp16: the streams of the bf16 path as fp16 fragments, every one multiplied by kF16WScale = 2^8 (kernels.h)
-  void* w2x_f16s16 = nullptr;  // mlp_x.2 scaled, v_mfma_f32_16x16x32_f16 B fragments
-  void* w2m_f16s = nullptr;    // mlp_m.2 scaled, v_mfma_f32_32x32x16_f16 B fragments
-  void* w2m_f16s16 = nullptr;  // mlp_m.2 scaled, v_mfma_f32_16x16x32_f16 B fragments (edge_small.hip)
-  void* w2h_f16p = nullptr;    // mlp_h.2, k in accumulator-row order
-  // split-operand node MLP (node_post_bf16_kernel<., f16x8, true>): mlp_h.0 head / remainder with K padded to its ring's two
-  // turns, mlp_h.2 remainder (its head is w2h_f16p); null when the shape is outside that kernel
-  void *w1h_f16k = nullptr, *w1h_f16k_lo = nullptr, *w2h_f16p_lo = nullptr;
-  // precision f16c8 (edge_f16c8w.hip): mlp_x.2 as v_mfma_f32_32x32x16_f16 B fragments (mlp_m.2: w2m_f16s above), e4m3 fragments
-  // [N/32][K/32][2][64][16 B] of the heads and remainders of the fp16 streams, and the e8m0 bytes of their block scales
-  // {x: hi, lo, m: hi, lo} (+ [4..5]: the packs' max |w| scratch words)
-  void *w2x_f16s = nullptr, *w2x_c8w = nullptr, *w2m_c8w = nullptr;
-  int* c8_exp = nullptr;
-};
+// (Re)allocates *p as `count` elements of device memory; *p is null after a failure.
+template <typename T>
+inline int dev_alloc(T** p, size_t count) {
+  if (*p) { (void)hipFree(*p); *p = nullptr; }
+  if (count == 0) return EGNN_OK;
+  if (hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)) != hipSuccess) {
+    set_error("hipMalloc of %zu bytes failed", count * sizeof(T));
+    *p = nullptr;
+    return EGNN_ENOMEM;
+  }
+  // EGNN_DEBUG_POISON=1 (tests): every scratch / pack buffer starts as 0xFF bytes -- NaN as fp32, fp16 and bf16, -1 as an index --
+  // so that an element a kernel reads before any kernel wrote it cannot pass for a plausible value (hipMalloc hands out zeros
+  // in a fresh process and whatever the previous owner left afterwards: tests/test_gpu_parity.py::test_no_scratch_read_before_write)
+  const char* poison = getenv("EGNN_DEBUG_POISON");
+  if (poison && poison[0] == '1' && hipMemset(*p, 0xFF, count * sizeof(T)) != hipSuccess) {
+    set_error("hipMemset (EGNN_DEBUG_POISON) failed");
+    (void)hipFree(*p); *p = nullptr;
+    return EGNN_EHIP;
+  }
+  return EGNN_OK;
+}
 
 // edge path of a layer's forward pass, chosen by launch_layer_begin (egnn_forward.hip: plan_edge) and read by launch_layer_end
 enum class EdgePath {
@@ -154,7 +128,7 @@ namespace egnn {
 int reserve(egnn_ctx* c);
 int launch_layer(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_scope, const float* h,
                  const float* x, float* h_out, float* x_out, bool need_gscale = false, bool defer_finish = false);
-int edge_rows_per_tile(int prec);
+void free_layer(LayerPack& lp);   // pack.hip
 // backward recompute on the forward's bf16 edge kernels (egcl_backward_edge_recompute)
 int backward_recompute_supported(egnn_ctx* c);
 int backward_table(egnn_ctx* c, hipStream_t st, int layer, const float* h);

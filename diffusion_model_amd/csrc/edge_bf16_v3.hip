@@ -397,10 +397,8 @@ int init_edge_bf16_v3_attributes() {
   return EGNN_OK;
 }
 
-int edge_v3_rows() { return kR3; }
-
 bool edge_bf16_v3_supported(const EdgeParams& p) {
-  return (p.WxP == 256 || p.WxP == 512 || p.WxP == 1024) && p.MP == 256 && p.WmP % 64 == 0 &&
+  return (p.WxP == 256 || p.WxP == 512 || p.WxP == 1024) && p.MP == 256 && p.WmP % 64 == 0 && p.w2x &&
          v3_smem_bytes(p.WmP, p.MP, true) <= 160 * 1024 && v3_smem_bytes(p.WxP, p.MP, false) <= 160 * 1024 &&
          (size_t)p.N * p.TC * 4 < ((size_t)1 << 32);
 }

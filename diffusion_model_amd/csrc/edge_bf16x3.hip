@@ -192,7 +192,7 @@ int init_edge_bf16x3_attributes() {
 }
 
 bool edge_bf16x3_supported(const EdgeParams& p) {
-  return (p.WxP == 256 || p.WxP == 512 || p.WxP == 1024) && p.MP == 256 && p.WmP % 64 == 0 && p.w2x_lo && p.w2m_lo &&
+  return (p.WxP == 256 || p.WxP == 512 || p.WxP == 1024) && p.MP == 256 && p.WmP % 64 == 0 && p.w2x && p.w2m && p.w2x_lo && p.w2m_lo &&
          x3_smem_bytes(p.WxP) <= 160 * 1024 && x3_smem_bytes(p.WmP) <= 160 * 1024 && (size_t)p.N * p.TC * 4 < ((size_t)1 << 32);
 }
 

@@ -30,131 +30,6 @@
 namespace egnn {
 
 // ------------------------------------------------------------------------------------------------
-// parameter packing
-// ------------------------------------------------------------------------------------------------
-// B fragments of D = A.B with B[k][n] = W[n][k] (nn.Linear weight [Nout, K], leading dim ldw,
-// column offset koff) for v_mfma_f32_32x32x2_f32: lane l holds B[k = 2*ks + (l>>5)][n = 32*nb + (l&31)].
-// Four consecutive k-steps are stored together so one 16-byte load per lane feeds 4 MFMAs:
-// out[((nb*KS4 + ks4)*64 + lane)*4 + s] = W[32nb + (l&31)][8*ks4 + 2*s + (l>>5)].
-__global__ void pack_frags_f32(const float* __restrict__ W, int Nout, int K, int ldw, int NP, int KP,
-                               float* __restrict__ out) {
-  const int KS4 = KP / 8;
-  const size_t total = (size_t)(NP / 32) * KS4 * 64 * 4;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int s = i & 3, lane = (i >> 2) & 63;
-    const size_t f = i >> 8;
-    const int ks4 = f % KS4, nb = f / KS4;
-    const int n = 32 * nb + (lane & 31), k = 8 * ks4 + 2 * s + (lane >> 5);
-    out[i] = (n < Nout && k < K) ? W[(size_t)n * ldw + k] : 0.f;
-  }
-}
-// v_mfma_f32_32x32x16_bf16: lane l holds B[k = 16*ks + 8*(l>>5) + j][n = 32*nb + (l&31)], j = 0..7.
-// out[((nb*KS + ks)*64 + lane)*8 + j]
-// OT = __bf16, or _Float16 for precision fp16 (scale then carries kF16WScale; clamped to the finite fp16 range)
-// LO: the remainder v - OT(v) of the same element (split-operand products)
-template <typename OT, bool LO = false>
-__device__ __forceinline__ OT to_operand(float v) {
-  if constexpr (sizeof(OT) == 2 && !__is_same(OT, __bf16)) v = fminf(fmaxf(v, -65504.f), 65504.f);
-  if constexpr (LO) return (OT)(v - (float)(OT)v);
-  return (OT)v;
-}
-template <typename OT, bool LO = false>
-__global__ void pack_frags_bf16(const float* __restrict__ W, int Nout, int K, int ldw, int NP, int KP,
-                                OT* __restrict__ out, float scale) {
-  const int KS = KP / 16;
-  const size_t total = (size_t)(NP / 32) * KS * 64 * 8;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int j = i & 7, lane = (i >> 3) & 63;
-    const size_t f = i >> 9;
-    const int ks = f % KS, nb = f / KS;
-    const int n = 32 * nb + (lane & 31), k = 16 * ks + 8 * (lane >> 5) + j;
-    out[i] = to_operand<OT, LO>((n < Nout && k < K) ? W[(size_t)n * ldw + k] * scale : 0.f);
-  }
-}
-// v_mfma_f32_16x16x32_bf16: lane l holds B[k = 32*ks + 8*(l>>4) + j][n = 16*nb + (l&15)], j = 0..7.
-// out[((nb*KS + ks)*64 + lane)*8 + j]
-template <typename OT>
-__global__ void pack_frags_bf16_n16(const float* __restrict__ W, int Nout, int K, int ldw, int NP, int KP,
-                                    OT* __restrict__ out, float scale) {
-  const int KS = KP / 32;
-  const size_t total = (size_t)(NP / 16) * KS * 64 * 8;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int j = i & 7, lane = (i >> 3) & 63;
-    const size_t f = i >> 9;
-    const int ks = f % KS, nb = f / KS;
-    const int n = 16 * nb + (lane & 15), k = 32 * ks + 8 * (lane >> 4) + j;
-    out[i] = to_operand<OT>((n < Nout && k < K) ? W[(size_t)n * ldw + k] * scale : 0.f);
-  }
-}
-// bf16 remainder of the same fragments: out = bf16(v - bf16(v)), v = W * scale (precision bf16x3)
-__global__ void pack_frags_bf16_lo(const float* __restrict__ W, int Nout, int K, int ldw, int NP, int KP,
-                                   __bf16* __restrict__ out, float scale) {
-  const int KS = KP / 16;
-  const size_t total = (size_t)(NP / 32) * KS * 64 * 8;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int j = i & 7, lane = (i >> 3) & 63;
-    const size_t f = i >> 9;
-    const int ks = f % KS, nb = f / KS;
-    const int n = 32 * nb + (lane & 31), k = 16 * ks + 8 * (lane >> 5) + j;
-    const float v = (n < Nout && k < K) ? W[(size_t)n * ldw + k] * scale : 0.f;
-    out[i] = (__bf16)(v - (float)(__bf16)v);
-  }
-}
-// mlp_h.2 as the A operand of out^T = W2h . hidden^T where hidden^T comes straight from an accumulator tile:
-// element j of lane half hh in k-step ks is hidden unit 32*(ks/2) + 16*(ks%2) + 8*(j>>2) + 4*hh + (j&3).
-template <typename OT, bool LO = false>
-__global__ void pack_frags_bf16_accperm(const float* __restrict__ W, int Nout, int K, int ldw, int NP, int KP,
-                                        OT* __restrict__ out, float scale) {
-  const int KS = KP / 16;
-  const size_t total = (size_t)(NP / 32) * KS * 64 * 8;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int j = i & 7, lane = (i >> 3) & 63;
-    const size_t f = i >> 9;
-    const int ks = f % KS, nb = f / KS;
-    const int n = 32 * nb + (lane & 31);
-    const int k = 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * (lane >> 5) + (j & 3);
-    out[i] = to_operand<OT, LO>((n < Nout && k < K) ? W[(size_t)n * ldw + k] * scale : 0.f);
-  }
-}
-// the same fragment layout for B[k][n] = W[k][n] (the transposed use of an nn.Linear weight: dgrad g . W)
-__global__ void pack_frags_bf16_T(const float* __restrict__ W, int Krows, int Ncols, int ldw, int NP, int KP,
-                                  __bf16* __restrict__ out) {
-  const int KS = KP / 16;
-  const size_t total = (size_t)(NP / 32) * KS * 64 * 8;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int j = i & 7, lane = (i >> 3) & 63;
-    const size_t f = i >> 9;
-    const int ks = f % KS, nb = f / KS;
-    const int n = 32 * nb + (lane & 31), k = 16 * ks + 8 * (lane >> 5) + j;
-    out[i] = (__bf16)((n < Ncols && k < Krows) ? W[(size_t)k * ldw + n] : 0.f);
-  }
-}
-__global__ void scale_copy(const float* __restrict__ src, size_t n, float scale, float* __restrict__ dst) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i] * scale;
-}
-__global__ void pad_copy(const float* __restrict__ src, int n, int stride, float* __restrict__ dst, int nP) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nP; i += gridDim.x * blockDim.x)
-    dst[i] = i < n ? src[(size_t)i * stride] : 0.f;
-}
-// first layers of mlp_x / mlp_m, split per input block and transposed: w1catT[h][col]
-__global__ void pack_first(const float* __restrict__ x0_w, const float* __restrict__ x0_b,
-                           const float* __restrict__ m0_w, const float* __restrict__ m0_b, int H, int Wx,
-                           int Wm, int WxP, int WmP, float* __restrict__ w1catT, float* __restrict__ b1cat) {
-  const int TC = 2 * WxP + 2 * WmP, ld = 2 * H + 1;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < TC * (H + 1); i += gridDim.x * blockDim.x) {
-    const int col = i % TC, h = i / TC;  // h == H -> bias row
-    int k, W, hoff;
-    const float *w, *b;
-    if (col < WxP) { k = col; W = Wx; hoff = 0; w = x0_w; b = x0_b; }
-    else if (col < 2 * WxP) { k = col - WxP; W = Wx; hoff = H; w = x0_w; b = nullptr; }
-    else if (col < 2 * WxP + WmP) { k = col - 2 * WxP; W = Wm; hoff = 0; w = m0_w; b = m0_b; }
-    else { k = col - 2 * WxP - WmP; W = Wm; hoff = H; w = m0_w; b = nullptr; }
-    if (h < H) w1catT[(size_t)h * TC + col] = k < W ? w[(size_t)k * ld + hoff + h] : 0.f;
-    else b1cat[col] = (k < W && b) ? b[k] : 0.f;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
 // node_pre: table[n][col] = b1cat[col] + sum_h h[n][h] * w1catT[h][col]
 // ------------------------------------------------------------------------------------------------
 constexpr int kPreNodes = 16;
@@ -279,23 +154,7 @@ __global__ __launch_bounds__(kThreads) void node_pre_mfma_kernel(const float* __
 // h_hi.W_hi + h_hi.W_lo + h_lo.W_hi: three v_mfma_f32_32x32x16_bf16 per 16-deep k-step with fp32 accumulation.  The dropped
 // h_lo.W_lo term and the 16-bit representation bound the error at ~2^-16 relative -- 30x below the half-precision rounding
 // of the table entry itself (2^-11); K = H <= 48 is 3 k-steps, so a 32 x 32 tile costs 9 x 32 = 288 MFMA cycles
-// instead of 18 x 64 = 1152.
-// B fragments of the (pre-scaled) first-layer weights: [TC/32 column blocks][3 k-steps][hi|lo][64 lanes][8 bf16].
-__global__ void pack_w1_hilo(const float* __restrict__ w1catT, int H, int TC, __bf16* __restrict__ out) {
-  const size_t total = (size_t)(TC / 32) * 3 * 64 * 8;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int j = i & 7, lane = (i >> 3) & 63;
-    const size_t f = i >> 9;
-    const int ks = f % 3, nb = f / 3;
-    const int n = 32 * nb + (lane & 31), k = 16 * ks + 8 * (lane >> 5) + j;
-    const float v = k < H ? w1catT[(size_t)k * TC + n] : 0.f;
-    const __bf16 hi = (__bf16)v;
-    const __bf16 lo = (__bf16)(v - (float)hi);
-    const size_t base = (f * 2) * 512 + (size_t)lane * 8 + j;
-    out[base] = hi;
-    out[base + 512] = lo;
-  }
-}
+// instead of 18 x 64 = 1152.  (The B fragments [TC/32 column blocks][3 k-steps][hi|lo][64 lanes][8 bf16]: pack.hip: pack_w1_hilo)
 
 // workgroup = 32 nodes x (4 waves x NBW column blocks): NBW = 8 (1024 columns) to amortise the h tile at large N,
 // NBW = 2 (256 columns) when the whole launch is a handful of workgroups and their serial length is the layer's latency
@@ -770,12 +629,6 @@ __global__ __launch_bounds__(kThreads, 1) void edge_kernel(const EdgeParams p) {
 // node_post: h' = mlp_h([h | sum_m]) (:69), x' = x + sum_x / (G + 1) (:64, :70)
 // ------------------------------------------------------------------------------------------------
 constexpr int kPostNodes = 32;
-constexpr int kPostHC = 512;   // hidden columns kept in LDS at a time
-__host__ __device__ inline size_t post_smem_bytes(int K1P, int WhP) {
-  const int hc = WhP < kPostHC ? WhP : kPostHC;
-  size_t hs = (size_t)hc * 33 * 4, red = (size_t)4 * 16 * 64 * 4;
-  return (size_t)K1P * 33 * 4 + (hs > red ? hs : red);
-}
 
 __global__ __launch_bounds__(kThreads, 1) void node_post_kernel(const PostParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -906,31 +759,11 @@ __global__ __launch_bounds__(kThreads, 1) void node_post_kernel(const PostParams
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-int edge_rows_per_tile(int prec) { (void)prec; return 64; }
-
-template <typename T>
-static int dev_alloc(T** p, size_t count) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (count == 0) return EGNN_OK;
-  if (hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)) != hipSuccess) {
-    set_error("hipMalloc of %zu bytes failed", count * sizeof(T));
-    *p = nullptr;
-    return EGNN_ENOMEM;
-  }
-  // EGNN_DEBUG_POISON=1 (tests): every scratch / pack buffer starts as 0xFF bytes -- NaN as fp32, fp16 and bf16, -1 as an index --
-  // so that an element a kernel reads before any kernel wrote it cannot pass for a plausible value (hipMalloc hands out zeros
-  // in a fresh process and whatever the previous owner left afterwards: tests/test_gpu_parity.py::test_no_scratch_read_before_write)
-  const char* poison = getenv("EGNN_DEBUG_POISON");
-  if (poison && poison[0] == '1' && hipMemset(*p, 0xFF, count * sizeof(T)) != hipSuccess) {
-    set_error("hipMemset (EGNN_DEBUG_POISON) failed");
-    return EGNN_EHIP;
-  }
-  return EGNN_OK;
-}
+constexpr int kEdgeRows = 64;   // edges per tile of the generic kernel (edge_kernel<PREC, 2>)
 
 int reserve(egnn_ctx* c) {
   if (c->L == 0 || c->N == 0) { set_error("model and graph must be set first"); return EGNN_ESTATE; }
-  const int R = edge_rows_per_tile(0);
+  const int R = kEdgeRows;
   // partial slots per tile: 64-row tiles are the smallest, except for small graphs, which may run on 32-row tiles
   c->small_ok = c->E <= (1 << 16);
   const size_t tiles = c->small_ok ? (size_t)(c->E + 31) / 32 : (size_t)(c->E + R - 1) / R;
@@ -1053,18 +886,14 @@ static int small_tiles(const egnn_ctx* c, const EdgeParams& p) {
   return (long)c->E <= limit ? 32 : ((long)c->E <= limit64 ? 64 : 0);
 }
 
-// EdgeParams of layer `layer` over the graph set on the context (unscaled parameter vectors, fp32 / bf16 fragments)
-static void fill_edge_params(egnn_ctx* c, int layer, int prec, const float* x, EdgeParams& p) {
-  const LayerPack& lp = c->layers[layer];
+// EdgeParams over the graph set on the context: dimensions, graph and scratch; every parameter stream is left null
+// (set_edge_streams)
+static void fill_edge_params(egnn_ctx* c, const float* x, EdgeParams& p) {
   memset(&p, 0, sizeof(p));
   p.N = c->N; p.E = c->E;
   p.edge_dst = c->edge_dst; p.edge_src = c->edge_src; p.row_ptr = c->row_ptr;
   p.x = x; p.table = c->table;
   p.TC = c->TC; p.WxP = c->WxP; p.WmP = c->WmP; p.MP = c->MP; p.cbx = c->cbx; p.cbm = c->cbm;
-  p.wdx = lp.wdx; p.wdm = lp.wdm; p.b2x = lp.b2x; p.w3x = lp.w3x; p.b2m = lp.b2m; p.wa = lp.wa;
-  p.scal = lp.scal;
-  p.w2x = prec == EGNN_PREC_BF16 ? lp.w2x_bf16 : (const void*)lp.w2x_f32;
-  p.w2m = prec == EGNN_PREC_BF16 ? lp.w2m_bf16 : (const void*)lp.w2m_f32;
   p.agg_m = c->agg_m; p.agg_x = c->agg_x; p.part_m = c->part_m; p.part_x = c->part_x;
   p.agg_x_stride = (size_t)c->cap_nodes * 4; p.part_x_stride = (c->cap_tiles + 1) * 2 * 4;
   p.stamps = c->stamps;
@@ -1073,22 +902,44 @@ static void fill_edge_params(egnn_ctx* c, int layer, int prec, const float* x, E
   p.dbg = dbg;
 #endif
 }
-// the bf16 fast kernels (v2..v4) use the copies pre-scaled by -log2(e) / -1/log2(e) (LayerPack::sc)
-static void use_scaled_pack(egnn_ctx* c, int layer, EdgeParams& p, const float*& w1catT, const float*& b1cat) {
-  const LayerPack& lp = c->layers[layer];
-  const float* o = lp.sc;
-  w1catT = o; o += (size_t)c->H * c->TC;
-  b1cat = o; o += c->TC;
-  p.wdx = o; o += c->WxP;
-  p.wdm = o; o += c->WmP;
-  p.b2x = o; o += c->WxP;
-  p.w3x = o; o += c->WxP;
-  p.b2m = o; o += c->MP;
-  p.wa = o;
-  p.w2x = lp.w2x_bf16s; p.w2m = lp.w2m_bf16s;
-  p.w2x16 = lp.w2x_bf16s16; p.w2m16 = lp.w2m_bf16s16;
-  p.w2x_lo = lp.w2x_bf16s_lo; p.w2m_lo = lp.w2m_bf16s_lo;
-  p.w2x_c8 = lp.w2x_c8w; p.w2m_c8 = lp.w2m_c8w; p.c8_exp = lp.c8_exp;
+// The parameter streams a path's kernels read -- the only reader of LayerPack's edge-MLP streams on the forward side
+// (the node kernels' streams, w1hl_bf16 and mlp_h's, are read where those kernels are launched).  The tiled
+// paths take the vectors pre-scaled by -log2(e) / -1/log2(e) (LayerPack::w1catT_s ...) and w1catT / b1cat then point at the
+// scaled first layers; the generic kernel takes the plain ones (prec: bf16 or fp32 fragments).  What a path does not read stays
+// null, and the *_supported() predicates send a layer with a missing stream to the generic kernel.
+//   path      w2x / w2m                      w2x16 / w2m16   others
+//   generic   *_bf16 (prec bf16) or *_f32    -               -
+//   bf16      *_bf16s                        *_bf16s16       -
+//   bf16x3    *_bf16s                        -               *_bf16s_lo
+//   fp16      - / w2m_f16s                   *_f16s16        -
+//   f16c8     *_f16s                         -               *_c8w, c8_exp
+static void set_edge_streams(const LayerPack& lp, EdgePath path, int prec, EdgeParams& p, const float*& w1catT,
+                             const float*& b1cat) {
+  const bool sc = path != EdgePath::kGeneric;
+  w1catT = sc ? lp.w1catT_s : lp.w1catT; b1cat = sc ? lp.b1cat_s : lp.b1cat;
+  p.wdx = sc ? lp.wdx_s : lp.wdx; p.wdm = sc ? lp.wdm_s : lp.wdm; p.b2x = sc ? lp.b2x_s : lp.b2x;
+  p.w3x = sc ? lp.w3x_s : lp.w3x; p.b2m = sc ? lp.b2m_s : lp.b2m; p.wa = sc ? lp.wa_s : lp.wa;
+  p.scal = lp.scal;
+  p.w2x = p.w2m = p.w2x16 = p.w2m16 = p.w2x_lo = p.w2m_lo = p.w2x_c8 = p.w2m_c8 = nullptr;
+  p.c8_exp = nullptr;
+  switch (path) {
+    case EdgePath::kGeneric:
+      p.w2x = prec == EGNN_PREC_BF16 ? lp.w2x_bf16 : (const void*)lp.w2x_f32;
+      p.w2m = prec == EGNN_PREC_BF16 ? lp.w2m_bf16 : (const void*)lp.w2m_f32;
+      break;
+    case EdgePath::kBf16:
+      p.w2x = lp.w2x_bf16s; p.w2m = lp.w2m_bf16s; p.w2x16 = lp.w2x_bf16s16; p.w2m16 = lp.w2m_bf16s16;
+      break;
+    case EdgePath::kBf16x3:
+      p.w2x = lp.w2x_bf16s; p.w2m = lp.w2m_bf16s; p.w2x_lo = lp.w2x_bf16s_lo; p.w2m_lo = lp.w2m_bf16s_lo;
+      break;
+    case EdgePath::kF16:
+      p.w2m = lp.w2m_f16s; p.w2x16 = lp.w2x_f16s16; p.w2m16 = lp.w2m_f16s16;
+      break;
+    case EdgePath::kF16c8:
+      p.w2x = lp.w2x_f16s; p.w2m = lp.w2m_f16s; p.w2x_c8 = lp.w2x_c8w; p.w2m_c8 = lp.w2m_c8w; p.c8_exp = lp.c8_exp;
+      break;
+  }
 }
 // first-layer table of the v3 / v4 kernels (fp16, pre-scaled) for node features h
 static int launch_node_pre_f16(egnn_ctx* c, hipStream_t st, int layer, const float* h, const float* w1catT,
@@ -1129,23 +980,22 @@ static int launch_node_pre_f16(egnn_ctx* c, hipStream_t st, int layer, const flo
 // Backward recompute (bf16 fast path), see egcl_backward_edge_recompute in include/egnn_amd.h
 int backward_recompute_supported(egnn_ctx* c) {
   EdgeParams p;
-  fill_edge_params(c, 0, EGNN_PREC_BF16, nullptr, p);
+  const float *w1catT, *b1cat;
+  fill_edge_params(c, nullptr, p);
+  set_edge_streams(c->layers[0], EdgePath::kBf16, EGNN_PREC_BF16, p, w1catT, b1cat);
   return edge_bf16_v4_supported(p) && edge_bf16_v3_supported(p) && c->Wx == c->WxP && c->Wm == c->WmP && c->M == c->MP;
 }
 int backward_table(egnn_ctx* c, hipStream_t st, int layer, const float* h) {
-  EdgeParams p;
-  fill_edge_params(c, layer, EGNN_PREC_BF16, nullptr, p);
-  const float *w1catT, *b1cat;
-  use_scaled_pack(c, layer, p, w1catT, b1cat);
-  return launch_node_pre_f16(c, st, layer, h, w1catT, b1cat);
+  const LayerPack& lp = c->layers[layer];
+  return launch_node_pre_f16(c, st, layer, h, lp.w1catT_s, lp.b1cat_s);
 }
 int backward_recompute(egnn_ctx* c, hipStream_t st, int layer, const float* x, const float* g_sum_x, const float* g_sum_m,
                        int e_first, int n_edges, void* s1x, void* s1m, void* g_a2x, void* g_a2m, float* s_halves,
                        float* g_b2x, float* g_w3, float* g_b3, float* g_b2m, float* g_wa, float* g_ba) {
   EdgeParams p;
-  fill_edge_params(c, layer, EGNN_PREC_BF16, x, p);
+  fill_edge_params(c, x, p);
   const float *w1catT, *b1cat;
-  use_scaled_pack(c, layer, p, w1catT, b1cat);
+  set_edge_streams(c->layers[layer], EdgePath::kBf16, EGNN_PREC_BF16, p, w1catT, b1cat);
   p.edge_dst = c->edge_dst + e_first; p.edge_src = c->edge_src + e_first; p.E = n_edges;
   p.g_sum_x = g_sum_x; p.g_sum_m = g_sum_m;
   p.s1_out = s1x; p.g_a2_out = g_a2x; p.s_half_out = s_halves;
@@ -1161,24 +1011,19 @@ int backward_recompute(egnn_ctx* c, hipStream_t st, int layer, const float* x, c
 int backward_heads_saved(egnn_ctx* c, hipStream_t st, int layer, const float* x, const float* g_sum_x, const float* g_sum_m,
                          int e_first, int n_edges, void* t2x, void* t2m, float* g_b2x, float* g_w3, float* g_b3, float* g_b2m,
                          float* g_wa, float* g_ba) {
-  EdgeParams p;
-  fill_edge_params(c, layer, EGNN_PREC_BF16, x, p);
-  const float *w1catT, *b1cat;
-  use_scaled_pack(c, layer, p, w1catT, b1cat);
-  return launch_heads_saved(n_edges, c->edge_dst + e_first, c->edge_src + e_first, x, g_sum_x, g_sum_m, c->WxP, c->MP, p.w3x, p.wa,
-                            p.scal, t2x, t2m, g_b2x, g_w3, g_b3, g_b2m, g_wa, g_ba, st);
+  const LayerPack& lp = c->layers[layer];
+  return launch_heads_saved(n_edges, c->edge_dst + e_first, c->edge_src + e_first, x, g_sum_x, g_sum_m, c->WxP, c->MP, lp.w3x_s, lp.wa_s,
+                            lp.scal, t2x, t2m, g_b2x, g_w3, g_b3, g_b2m, g_wa, g_ba, st);
 }
 
 int backward_dgrad(egnn_ctx* c, hipStream_t st, int layer, const float* x, int e_first, int n_edges, const void* g_a2x,
                    const void* g_a2m, void* g_a1x, void* g_a1m) {
   const LayerPack& lp = c->layers[layer];
-  const float* wdx_s = lp.sc + (size_t)(c->H + 1) * c->TC;   // scaled copies: [w1catT | b1cat | wdx | wdm | ...]
-  const float* wdm_s = wdx_s + c->WxP;
-  int rc = launch_edge_dgrad(c->N, n_edges, c->edge_dst + e_first, c->edge_src + e_first, x, c->table, c->TC, 0, c->WxP, wdx_s,
+  int rc = launch_edge_dgrad(c->N, n_edges, c->edge_dst + e_first, c->edge_src + e_first, x, c->table, c->TC, 0, c->WxP, lp.wdx_s,
                              g_a2x, c->WxP, lp.w2xT_bf16, c->WxP, g_a1x, st);
   if (rc) return rc;
   return launch_edge_dgrad(c->N, n_edges, c->edge_dst + e_first, c->edge_src + e_first, x, c->table, c->TC, 2 * c->WxP,
-                           2 * c->WxP + c->WmP, wdm_s, g_a2m, c->MP, lp.w2mT_bf16, c->WmP, g_a1m, st);
+                           2 * c->WxP + c->WmP, lp.wdm_s, g_a2m, c->MP, lp.w2mT_bf16, c->WmP, g_a1m, st);
 }
 
 // the same dgrad WITHOUT dL/da1 in memory: per-graph workgroups that also reduce it for the first Linear layers
@@ -1186,54 +1031,48 @@ int backward_dgrad(egnn_ctx* c, hipStream_t st, int layer, const float* x, int e
 int backward_dgrad_graph(egnn_ctx* c, hipStream_t st, int layer, const float* x, int e_first, int n_edges, const void* g_a2x,
                          const void* g_a2m, void* G, float* cd_x, float* cd_m, float* gd2_part) {
   const LayerPack& lp = c->layers[layer];
-  const float* wdx_s = lp.sc + (size_t)(c->H + 1) * c->TC;
-  const float* wdm_s = wdx_s + c->WxP;
   const int ldg = 2 * c->WxP + 2 * c->WmP;
   __bf16* g = static_cast<__bf16*>(G);
   int rc = launch_edge_dgrad_graph(c->N, c->B, c->graph_ptr, c->row_ptr, c->edge_dst, c->edge_src, e_first, n_edges, x, c->table,
-                                   c->TC, 0, c->WxP, wdx_s, g_a2x, c->WxP, lp.w2xT_bf16, c->WxP, g, g + c->WxP, ldg, cd_x,
+                                   c->TC, 0, c->WxP, lp.wdx_s, g_a2x, c->WxP, lp.w2xT_bf16, c->WxP, g, g + c->WxP, ldg, cd_x,
                                    gd2_part, st);
   if (rc) return rc;
   return launch_edge_dgrad_graph(c->N, c->B, c->graph_ptr, c->row_ptr, c->edge_dst, c->edge_src, e_first, n_edges, x, c->table,
-                                 c->TC, 2 * c->WxP, 2 * c->WxP + c->WmP, wdm_s, g_a2m, c->MP, lp.w2mT_bf16, c->WmP,
+                                 c->TC, 2 * c->WxP, 2 * c->WxP + c->WmP, lp.wdm_s, g_a2m, c->MP, lp.w2mT_bf16, c->WmP,
                                  g + 2 * c->WxP, g + 2 * c->WxP + c->WmP, ldg, cd_m,
                                  gd2_part + (size_t)(c->WxP / 256) * n_edges, st);
 }
 
-// Edge path of a layer and its EdgeParams.  The 128-edge-tile kernels take the pre-scaled parameters (use_scaled_pack: w1catT /
-// b1cat then point at the scaled first layers), the generic kernel the plain ones:
+// Edge path of a layer and its EdgeParams (streams: set_edge_streams).  The candidate of a precision:
 //   bf16    edge_x_m16.hip (hidden width 512 / 1024) or edge_bf16_v3.hip (256) + edge_bf16_v4.hip, fp16 table
 //   bf16x3  edge_bf16x3.hip (head / remainder operands, fp32 table)
 //   fp16    the bf16 path's kernels on fp16 operands (hidden width 512 / 1024)
 //   f16c8   edge_f16c8w.hip (fp16 heads + e4m3 corrections, fp32 table)
-// A precision whose tiled kernels do not take the shape runs the generic kernel: bf16 as bf16, the others as the exact fp32 path
-// (prec is set to EGNN_PREC_F32; their EdgeParams are the fp32 ones already).  EGNN_EDGE=1 forces the generic kernel (the one
-// switch kept: the fallback kernels' own parity test runs the reference widths on them).
+// Its kernels are asked on the very EdgeParams they would be launched with.  A precision whose tiled kernels do not take the
+// shape runs the generic kernel: bf16 as bf16, the others as the exact fp32 path (prec is set to EGNN_PREC_F32).  EGNN_EDGE=1
+// forces the generic kernel (the one switch kept: the fallback kernels' own parity test runs the reference widths on them).
 static EdgePath plan_edge(egnn_ctx* c, int layer, int& prec, const float* x, EdgeParams& p, const float*& w1catT,
                           const float*& b1cat) {
   static const int edge_sel = getenv("EGNN_EDGE") ? atoi(getenv("EGNN_EDGE")) : 4;
   const LayerPack& lp = c->layers[layer];
-  fill_edge_params(c, layer, prec, x, p);
-  w1catT = lp.w1catT; b1cat = lp.b1cat;
-  EdgePath path = EdgePath::kGeneric;
-  if (edge_sel >= 4) {
-    EdgeParams q = p;
-    const float *w1c, *b1c;
-    use_scaled_pack(c, layer, q, w1c, b1c);
-    if (prec == EGNN_PREC_BF16) {
-      if (edge_bf16_v4_supported(p) && edge_bf16_v3_supported(p)) path = EdgePath::kBf16;
-    } else if (prec == EGNN_PREC_BF16X3) {
-      if (edge_bf16x3_supported(q)) path = EdgePath::kBf16x3;
-    } else if (prec == EGNN_PREC_F16C8) {
-      q.w2x = lp.w2x_f16s; q.w2m = lp.w2m_f16s;
-      if (!c->save_s1x && edge_f16c8w_supported(q)) path = EdgePath::kF16c8;
-    } else if (prec == EGNN_PREC_F16) {
-      if (!c->save_s1x && edge_bf16_v4_supported(q) && edge_x_m16_supported(q)) path = EdgePath::kF16;
+  fill_edge_params(c, x, p);
+  const EdgePath want = prec == EGNN_PREC_BF16 ? EdgePath::kBf16 : prec == EGNN_PREC_BF16X3 ? EdgePath::kBf16x3
+                      : prec == EGNN_PREC_F16 ? EdgePath::kF16 : prec == EGNN_PREC_F16C8 ? EdgePath::kF16c8 : EdgePath::kGeneric;
+  if (edge_sel >= 4 && want != EdgePath::kGeneric) {
+    set_edge_streams(lp, want, prec, p, w1catT, b1cat);
+    bool ok = false;
+    switch (want) {
+      case EdgePath::kBf16: ok = edge_bf16_v4_supported(p) && edge_bf16_v3_supported(p); break;
+      case EdgePath::kBf16x3: ok = edge_bf16x3_supported(p); break;
+      case EdgePath::kF16: ok = !c->save_s1x && edge_bf16_v4_supported(p) && edge_x_m16_supported(p); break;
+      case EdgePath::kF16c8: ok = !c->save_s1x && edge_f16c8w_supported(p); break;
+      default: break;
     }
+    if (ok) return want;
   }
-  if (path == EdgePath::kGeneric && prec != EGNN_PREC_BF16) prec = EGNN_PREC_F32;
-  if (path != EdgePath::kGeneric) use_scaled_pack(c, layer, p, w1catT, b1cat);
-  return path;
+  if (prec != EGNN_PREC_BF16) prec = EGNN_PREC_F32;
+  set_edge_streams(lp, EdgePath::kGeneric, prec, p, w1catT, b1cat);
+  return EdgePath::kGeneric;
 }
 
 // fp32 first-layer table (exact: the generic path, and the fp32 table of bf16x3 / f16c8)
@@ -1305,7 +1144,7 @@ int launch_layer_begin(egnn_ctx* c, hipStream_t st, int layer, int prec, int nor
   prof_end(c, st);
   EGNN_HIP(hipGetLastError());
 
-  int R = edge_rows_per_tile(prec), nsplit_x = 1;
+  int R = kEdgeRows, nsplit_x = 1;
   if (E > 0) {
     prof_begin(c, st, 0);
     // fork_candidate(): whether the message kernel fits the shadow of the coordinate kernel's last round (small-tile kernels:
@@ -1321,8 +1160,6 @@ int launch_layer_begin(egnn_ctx* c, hipStream_t st, int layer, int prec, int nor
     } else if (path == EdgePath::kF16c8) {   // fp16 32-column streams + e4m3 correction streams
       R = 128;
       nsplit_x = p.WxP / 512;
-      p.w2x16 = lp.w2x_f16s16; p.w2m16 = lp.w2m_f16s16;
-      p.w2x = lp.w2x_f16s; p.w2m = lp.w2m_f16s;
       rc = launch_edge_pair(c, st, fork, [&](hipStream_t s) { return launch_edge_f16c8w_x(p, s); },
                             [&](hipStream_t s) { return launch_edge_f16c8w_m(p, s); });
     } else if (small != 0) {
@@ -1330,13 +1167,11 @@ int launch_layer_begin(egnn_ctx* c, hipStream_t st, int layer, int prec, int nor
       const bool f16 = path == EdgePath::kF16;
       R = small;
       nsplit_x = p.WxP / 512;
-      if (f16) { p.w2x16 = lp.w2x_f16s16; p.w2m16 = lp.w2m_f16s16; }
       rc = launch_edge_pair(c, st, can_fork, [&](hipStream_t s) { return launch_edge_small_x(p, s, f16, R); },
                             [&](hipStream_t s) { return launch_edge_small_m(p, s, f16, R); });
     } else if (path == EdgePath::kF16) {   // the bf16 path's kernels on fp16 operands (same tiles, same launch structure)
       R = edge_v4_rows();
       nsplit_x = p.WxP / 512;
-      p.w2x16 = lp.w2x_f16s16; p.w2m = lp.w2m_f16s;
       rc = launch_edge_pair(c, st, fork, [&](hipStream_t s) { return launch_edge_x_m16_f16(p, s); },
                             [&](hipStream_t s) { return launch_edge_f16_v4_m(p, s); });
     } else if (path == EdgePath::kBf16) {
@@ -1464,17 +1299,6 @@ int egnn_create(egnn_ctx** out, int device) {
   return EGNN_OK;
 }
 
-static void free_layer(LayerPack& lp) {
-  void* ptrs[] = {lp.w1catT, lp.b1cat, lp.wdx, lp.wdm, lp.w2x_f32, lp.w2x_bf16, lp.b2x, lp.w3x, lp.w2m_f32,
-                  lp.w2m_bf16, lp.b2m, lp.wa, lp.scal, lp.w1h_f32, lp.b1h, lp.w2h_f32, lp.b2h, lp.sc, lp.w2x_bf16s, lp.w2m_bf16s, lp.w1h_bf16, lp.w2h_bf16p,
-                  lp.w2xT_bf16, lp.w2mT_bf16, lp.w1hl_bf16, lp.w2x_bf16s16, lp.w2x_bf16s_lo, lp.w2m_bf16s_lo,
-                  lp.w2x_f16s16, lp.w2m_f16s, lp.w2h_f16p, lp.w1h_f16k, lp.w1h_f16k_lo, lp.w2h_f16p_lo,
-                  lp.w2m_bf16s16, lp.w2m_f16s16, lp.c8_exp, lp.w2x_f16s, lp.w2x_c8w, lp.w2m_c8w};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  lp = LayerPack();
-}
-
 void sampler_free(egnn_ctx* c);
 
 int egnn_destroy(egnn_ctx* c) {
@@ -1483,7 +1307,7 @@ int egnn_destroy(egnn_ctx* c) {
   (void)hipDeviceSynchronize();
   for (auto& lp : c->layers) free_layer(lp);
   void* ptrs[] = {c->table, c->agg_m, c->agg_x, c->part_m, c->part_x, c->node_d2, c->gscale, c->bwd_s, c->h_partial,
-                  c->h_tmp[0], c->h_tmp[1], c->x_tmp[0], c->x_tmp[1]};
+                  c->h_tmp[0], c->h_tmp[1], c->x_tmp[0], c->x_tmp[1], c->stamps};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   sampler_free(c);
@@ -1492,178 +1316,6 @@ int egnn_destroy(egnn_ctx* c) {
   c->side = nullptr;   // the caller's stream (egnn_set_side_stream)
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
   delete c;
-  return EGNN_OK;
-}
-
-int egnn_set_model(egnn_ctx* c, int L, int H, int M, int Wm, int Wx, int Wh) {
-  if (!c) return EGNN_EINVAL;
-  ModelDims md;
-  {
-    const int rc = model_dims(L, H, M, Wm, Wx, Wh, &md);   // validation + padded widths (host_logic.cpp)
-    if (rc) return rc;
-  }
-  (void)hipSetDevice(c->device);
-  (void)hipDeviceSynchronize();
-  for (auto& lp : c->layers) free_layer(lp);
-  c->layers.assign(L, LayerPack());
-  c->L = L; c->H = H; c->M = M; c->Wm = Wm; c->Wx = Wx; c->Wh = Wh;
-  c->WxP = md.WxP; c->WmP = md.WmP; c->MP = md.MP; c->cbx = md.cbx; c->cbm = md.cbm;
-  c->WhP = md.WhP; c->HP = md.HP; c->K1P = md.K1P; c->K1Q = md.K1Q; c->TC = md.TC;
-  c->cap_nodes = c->cap_tiles = c->cap_graphs = 0;  // MP / TC may have changed
-  if (post_smem_bytes(c->K1P, c->WhP) > 160 * 1024 || edge_smem_bytes(64, c->MP) > 160 * 1024) {
-    set_error("model does not fit the 160 KiB LDS budget");
-    return EGNN_EINVAL;
-  }
-  return EGNN_OK;
-}
-
-int egnn_pack_layer(egnn_ctx* c, void* stream, int l, const float* m0_w, const float* m0_b, const float* m2_w,
-                    const float* m2_b, const float* x0_w, const float* x0_b, const float* x2_w,
-                    const float* x2_b, const float* x4_w, const float* x4_b, const float* h0_w,
-                    const float* h0_b, const float* h2_w, const float* h2_b, const float* a_w,
-                    const float* a_b) {
-  if (!c || c->L == 0) { set_error("egnn_set_model first"); return EGNN_ESTATE; }
-  if (l < 0 || l >= c->L) { set_error("layer %d out of range", l); return EGNN_EINVAL; }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  EGNN_HIP(hipSetDevice(c->device));
-  LayerPack& lp = c->layers[l];
-  const int H = c->H, M = c->M, Wm = c->Wm, Wx = c->Wx, Wh = c->Wh;
-  const int WxP = c->WxP, WmP = c->WmP, MP = c->MP, WhP = c->WhP, HP = c->HP, K1P = c->K1P, TC = c->TC;
-  int rc;
-  if (!lp.w1catT) {
-    if ((rc = dev_alloc(&lp.w1catT, (size_t)H * TC))) return rc;
-    if ((rc = dev_alloc(&lp.b1cat, (size_t)TC))) return rc;
-    if ((rc = dev_alloc(&lp.wdx, (size_t)WxP))) return rc;
-    if ((rc = dev_alloc(&lp.wdm, (size_t)WmP))) return rc;
-    if ((rc = dev_alloc(&lp.w2x_f32, (size_t)WxP * WxP))) return rc;
-    __bf16* tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)WxP * WxP))) return rc;
-    lp.w2x_bf16 = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&lp.b2x, (size_t)WxP))) return rc;
-    if ((rc = dev_alloc(&lp.w3x, (size_t)WxP))) return rc;
-    if ((rc = dev_alloc(&lp.w2m_f32, (size_t)MP * WmP))) return rc;
-    if ((rc = dev_alloc(&tmp, (size_t)MP * WmP))) return rc;
-    lp.w2m_bf16 = tmp;
-    if ((rc = dev_alloc(&lp.b2m, (size_t)MP))) return rc;
-    if ((rc = dev_alloc(&lp.wa, (size_t)MP))) return rc;
-    if ((rc = dev_alloc(&lp.scal, (size_t)4))) return rc;
-    if ((rc = dev_alloc(&lp.w1h_f32, (size_t)WhP * K1P))) return rc;
-    if ((rc = dev_alloc(&lp.b1h, (size_t)WhP))) return rc;
-    if ((rc = dev_alloc(&lp.w2h_f32, (size_t)HP * WhP))) return rc;
-    if ((rc = dev_alloc(&lp.b2h, (size_t)HP))) return rc;
-    if ((rc = dev_alloc(&lp.sc, (size_t)(H + 1) * TC + 3 * (size_t)WxP + WmP + 2 * (size_t)MP))) return rc;
-    tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)WhP * c->K1Q))) return rc;
-    lp.w1h_bf16 = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)HP * WhP))) return rc;
-    lp.w2h_bf16p = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)WxP * WxP))) return rc;
-    lp.w2x_bf16s = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)MP * WmP))) return rc;
-    lp.w2m_bf16s = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)WxP * WxP))) return rc;
-    lp.w2x_bf16s16 = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)WxP * WxP))) return rc;
-    lp.w2x_bf16s_lo = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)MP * WmP))) return rc;
-    lp.w2m_bf16s_lo = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)WxP * WxP))) return rc;
-    lp.w2xT_bf16 = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)MP * WmP))) return rc;
-    lp.w2mT_bf16 = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)(TC / 32) * 3 * 2 * 512))) return rc;
-    lp.w1hl_bf16 = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)MP * WmP))) return rc;
-    lp.w2m_bf16s16 = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)MP * WmP))) return rc;
-    lp.w2m_f16s16 = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)WxP * WxP))) return rc;      // fp16 streams: same sizes as their bf16 twins
-    lp.w2x_f16s16 = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)MP * WmP))) return rc;
-    lp.w2m_f16s = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)HP * WhP))) return rc;
-    lp.w2h_f16p = tmp; tmp = nullptr;
-    if (HP <= 64 && H + MP > node_post_split_k() / 2 && H + MP <= node_post_split_k()) {   // shapes of the split-operand node MLP
-      if ((rc = dev_alloc(&tmp, (size_t)WhP * node_post_split_k()))) return rc;
-      lp.w1h_f16k = tmp; tmp = nullptr;
-      if ((rc = dev_alloc(&tmp, (size_t)WhP * node_post_split_k()))) return rc;
-      lp.w1h_f16k_lo = tmp; tmp = nullptr;
-      if ((rc = dev_alloc(&tmp, (size_t)HP * WhP))) return rc;
-      lp.w2h_f16p_lo = tmp;
-    }
-    // precision f16c8: mlp_x.2 as 32-column fp16 fragments, e4m3 fragments of heads + remainders (2 bytes per weight) and the
-    // block-scale exponents
-    tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)WxP * WxP))) return rc;
-    lp.w2x_f16s = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)WxP * WxP))) return rc;
-    lp.w2x_c8w = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&tmp, (size_t)MP * WmP))) return rc;
-    lp.w2m_c8w = tmp; tmp = nullptr;
-    if ((rc = dev_alloc(&lp.c8_exp, (size_t)8))) return rc;   // [0..3] scale exponents {x: hi, lo, m: hi, lo}, [4..5] max |w| scratch
-  }
-  const dim3 g(256), b(256);
-  hipLaunchKernelGGL(pack_first, g, b, 0, st, x0_w, x0_b, m0_w, m0_b, H, Wx, Wm, WxP, WmP, lp.w1catT, lp.b1cat);
-  hipLaunchKernelGGL(pad_copy, dim3(8), b, 0, st, x0_w + 2 * H, Wx, 2 * H + 1, lp.wdx, WxP);
-  hipLaunchKernelGGL(pad_copy, dim3(8), b, 0, st, m0_w + 2 * H, Wm, 2 * H + 1, lp.wdm, WmP);
-  hipLaunchKernelGGL(pack_frags_f32, g, b, 0, st, x2_w, Wx, Wx, Wx, WxP, WxP, lp.w2x_f32);
-  hipLaunchKernelGGL(pack_frags_bf16<__bf16>, g, b, 0, st, x2_w, Wx, Wx, Wx, WxP, WxP, reinterpret_cast<__bf16*>(lp.w2x_bf16), 1.0f);
-  hipLaunchKernelGGL(pad_copy, dim3(8), b, 0, st, x2_b, Wx, 1, lp.b2x, WxP);
-  hipLaunchKernelGGL(pad_copy, dim3(8), b, 0, st, x4_w, Wx, 1, lp.w3x, WxP);
-  hipLaunchKernelGGL(pack_frags_f32, g, b, 0, st, m2_w, M, Wm, Wm, MP, WmP, lp.w2m_f32);
-  hipLaunchKernelGGL(pack_frags_bf16<__bf16>, g, b, 0, st, m2_w, M, Wm, Wm, MP, WmP, reinterpret_cast<__bf16*>(lp.w2m_bf16), 1.0f);
-  hipLaunchKernelGGL(pad_copy, dim3(8), b, 0, st, m2_b, M, 1, lp.b2m, MP);
-  hipLaunchKernelGGL(pad_copy, dim3(8), b, 0, st, a_w, M, 1, lp.wa, MP);
-  hipLaunchKernelGGL(pad_copy, dim3(1), dim3(64), 0, st, x4_b, 1, 1, lp.scal, 1);
-  hipLaunchKernelGGL(pad_copy, dim3(1), dim3(64), 0, st, a_b, 1, 1, lp.scal + 1, 1);
-  // mlp_h.0 sees [h | sum_m]; the kernel's K index is [h (H) | sum_m (MP, zero-padded beyond M)]
-  hipLaunchKernelGGL(pack_frags_f32, g, b, 0, st, h0_w, Wh, H + M, H + M, WhP, K1P, lp.w1h_f32);
-  hipLaunchKernelGGL(pad_copy, dim3(8), b, 0, st, h0_b, Wh, 1, lp.b1h, WhP);
-  hipLaunchKernelGGL(pack_frags_f32, g, b, 0, st, h2_w, H, Wh, Wh, HP, WhP, lp.w2h_f32);
-  hipLaunchKernelGGL(pad_copy, dim3(8), b, 0, st, h2_b, H, 1, lp.b2h, HP);
-  {  // scaled copies for the bf16 fast path (see LayerPack::sc)
-    float* o = lp.sc;
-    const float s1 = kNegLog2e, s2 = kNegInvLog2e;
-    hipLaunchKernelGGL(scale_copy, g, b, 0, st, lp.w1catT, (size_t)H * TC, s1, o); o += (size_t)H * TC;
-    hipLaunchKernelGGL(scale_copy, dim3(8), b, 0, st, lp.b1cat, (size_t)TC, s1, o); o += TC;
-    hipLaunchKernelGGL(scale_copy, dim3(8), b, 0, st, lp.wdx, (size_t)WxP, s1, o); o += WxP;
-    hipLaunchKernelGGL(scale_copy, dim3(8), b, 0, st, lp.wdm, (size_t)WmP, s1, o); o += WmP;
-    hipLaunchKernelGGL(scale_copy, dim3(8), b, 0, st, lp.b2x, (size_t)WxP, s1, o); o += WxP;
-    hipLaunchKernelGGL(scale_copy, dim3(8), b, 0, st, lp.w3x, (size_t)WxP, s2, o); o += WxP;
-    hipLaunchKernelGGL(scale_copy, dim3(8), b, 0, st, lp.b2m, (size_t)MP, s1, o); o += MP;
-    hipLaunchKernelGGL(scale_copy, dim3(8), b, 0, st, lp.wa, (size_t)MP, s2, o);
-    hipLaunchKernelGGL(pack_frags_bf16<__bf16>, g, b, 0, st, x2_w, Wx, Wx, Wx, WxP, WxP, reinterpret_cast<__bf16*>(lp.w2x_bf16s), s2);
-    hipLaunchKernelGGL(pack_frags_bf16<__bf16>, g, b, 0, st, m2_w, M, Wm, Wm, MP, WmP, reinterpret_cast<__bf16*>(lp.w2m_bf16s), s2);
-    hipLaunchKernelGGL(pack_frags_bf16_n16<__bf16>, g, b, 0, st, x2_w, Wx, Wx, Wx, WxP, WxP, reinterpret_cast<__bf16*>(lp.w2x_bf16s16), s2);
-    hipLaunchKernelGGL(pack_frags_bf16_n16<__bf16>, g, b, 0, st, m2_w, M, Wm, Wm, MP, WmP, reinterpret_cast<__bf16*>(lp.w2m_bf16s16), s2);
-    hipLaunchKernelGGL(pack_frags_bf16_n16<_Float16>, g, b, 0, st, m2_w, M, Wm, Wm, MP, WmP, reinterpret_cast<_Float16*>(lp.w2m_f16s16), s2 * kF16WScale);
-    // precision fp16: the same streams as fp16 fragments, times 2^8 (kernels.h "MFMA operand type")
-    hipLaunchKernelGGL(pack_frags_bf16_n16<_Float16>, g, b, 0, st, x2_w, Wx, Wx, Wx, WxP, WxP, reinterpret_cast<_Float16*>(lp.w2x_f16s16), s2 * kF16WScale);
-    hipLaunchKernelGGL(pack_frags_bf16<_Float16>, g, b, 0, st, m2_w, M, Wm, Wm, MP, WmP, reinterpret_cast<_Float16*>(lp.w2m_f16s), s2 * kF16WScale);
-    hipLaunchKernelGGL(pack_frags_bf16_accperm<_Float16>, g, b, 0, st, h2_w, H, Wh, Wh, HP, WhP, reinterpret_cast<_Float16*>(lp.w2h_f16p), kF16WScale);
-    if (lp.w1h_f16k) {   // split-operand node MLP: heads + remainders, mlp_h.0 with K padded to the ring's two turns
-      const int KS = node_post_split_k();
-      hipLaunchKernelGGL(pack_frags_bf16<_Float16>, g, b, 0, st, h0_w, Wh, H + M, H + M, WhP, KS, reinterpret_cast<_Float16*>(lp.w1h_f16k), kF16WScale);
-      hipLaunchKernelGGL((pack_frags_bf16<_Float16, true>), g, b, 0, st, h0_w, Wh, H + M, H + M, WhP, KS, reinterpret_cast<_Float16*>(lp.w1h_f16k_lo), kF16WScale);
-      hipLaunchKernelGGL((pack_frags_bf16_accperm<_Float16, true>), g, b, 0, st, h2_w, H, Wh, Wh, HP, WhP, reinterpret_cast<_Float16*>(lp.w2h_f16p_lo), kF16WScale);
-    }
-    // precision f16c8 (edge_f16c8w.hip): the same scaled weights as 32-column fp16 fragments (mlp_m.2: w2m_f16s) and as e4m3
-    // head / remainder fragments for the block-scaled correction product
-    hipLaunchKernelGGL(pack_frags_bf16<_Float16>, g, b, 0, st, x2_w, Wx, Wx, Wx, WxP, WxP, reinterpret_cast<_Float16*>(lp.w2x_f16s), s2 * kF16WScale);
-    if ((rc = pack_c8w_stream(x2_w, Wx, Wx, Wx, WxP, WxP, lp.w2x_c8w, s2 * kF16WScale, lp.c8_exp, reinterpret_cast<unsigned*>(lp.c8_exp + 4), st))) return rc;
-    if ((rc = pack_c8w_stream(m2_w, M, Wm, Wm, MP, WmP, lp.w2m_c8w, s2 * kF16WScale, lp.c8_exp + 2, reinterpret_cast<unsigned*>(lp.c8_exp + 5), st))) return rc;
-    hipLaunchKernelGGL(pack_frags_bf16_lo, g, b, 0, st, x2_w, Wx, Wx, Wx, WxP, WxP, reinterpret_cast<__bf16*>(lp.w2x_bf16s_lo), s2);
-    hipLaunchKernelGGL(pack_frags_bf16_lo, g, b, 0, st, m2_w, M, Wm, Wm, MP, WmP, reinterpret_cast<__bf16*>(lp.w2m_bf16s_lo), s2);
-    hipLaunchKernelGGL(pack_frags_bf16<__bf16>, g, b, 0, st, h0_w, Wh, H + M, H + M, WhP, c->K1Q, reinterpret_cast<__bf16*>(lp.w1h_bf16), 1.0f);
-    hipLaunchKernelGGL(pack_frags_bf16_accperm<__bf16>, g, b, 0, st, h2_w, H, Wh, Wh, HP, WhP, reinterpret_cast<__bf16*>(lp.w2h_bf16p), 1.0f);
-    if (H <= 48)   // hi/lo bf16 fragments of the scaled first-layer weights (node_pre_hilo_kernel)
-      hipLaunchKernelGGL(pack_w1_hilo, g, b, 0, st, lp.sc, H, TC, reinterpret_cast<__bf16*>(lp.w1hl_bf16));
-    // transposed packs for the backward dgrad: B[k = second-layer output][column = hidden unit]
-    hipLaunchKernelGGL(pack_frags_bf16_T, g, b, 0, st, x2_w, Wx, Wx, Wx, WxP, WxP, reinterpret_cast<__bf16*>(lp.w2xT_bf16));
-    hipLaunchKernelGGL(pack_frags_bf16_T, g, b, 0, st, m2_w, M, Wm, Wm, WmP, MP, reinterpret_cast<__bf16*>(lp.w2mT_bf16));
-  }
-  EGNN_HIP(hipGetLastError());
-  lp.packed = true;
   return EGNN_OK;
 }
 

@@ -1,5 +1,6 @@
 // Host-only logic of libegnn_amd (see host_logic.h).  Plain C++: no HIP call, no device code.
 #include "host_logic.h"
+#include "layer_pack.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -119,6 +120,69 @@ int dense_rows_args_check(int N, int K, int J, const void* in, const void* W, co
     return EGNN_EINVAL;
   }
   return EGNN_OK;
+}
+
+// The one statement of a layer's packed streams: field, element size in bytes, element count.  Offsets are integers, so the
+// measuring call (base == nullptr) does no pointer arithmetic.
+size_t carve_layer_pack(LayerPack& lp, const ModelDims& md, int H, int split_k, char* base) {
+  size_t off = 0;
+  auto put = [&](auto*& field, size_t elem, size_t count) {
+    field = base ? reinterpret_cast<decltype(+field)>(base + off) : nullptr;
+    off += (elem * count + kPackAlign - 1) / kPackAlign * kPackAlign;
+  };
+  const size_t TC = md.TC, WxP = md.WxP, WmP = md.WmP, MP = md.MP, WhP = md.WhP, HP = md.HP;
+  const size_t w2x = WxP * WxP, w2m = MP * WmP, w2h = HP * WhP;   // elements of the three second-layer weight matrices
+  put(lp.w1catT, 4, H * TC);
+  put(lp.b1cat, 4, TC);
+  put(lp.wdx, 4, WxP);
+  put(lp.wdm, 4, WmP);
+  put(lp.w2x_f32, 4, w2x);
+  put(lp.w2x_bf16, 2, w2x);
+  put(lp.b2x, 4, WxP);
+  put(lp.w3x, 4, WxP);
+  put(lp.w2m_f32, 4, w2m);
+  put(lp.w2m_bf16, 2, w2m);
+  put(lp.b2m, 4, MP);
+  put(lp.wa, 4, MP);
+  put(lp.scal, 4, 4);
+  put(lp.w1h_f32, 4, WhP * md.K1P);
+  put(lp.b1h, 4, WhP);
+  put(lp.w2h_f32, 4, w2h);
+  put(lp.b2h, 4, HP);
+  put(lp.w1catT_s, 4, H * TC);
+  put(lp.b1cat_s, 4, TC);
+  put(lp.wdx_s, 4, WxP);
+  put(lp.wdm_s, 4, WmP);
+  put(lp.b2x_s, 4, WxP);
+  put(lp.w3x_s, 4, WxP);
+  put(lp.b2m_s, 4, MP);
+  put(lp.wa_s, 4, MP);
+  put(lp.w1h_bf16, 2, WhP * md.K1Q);
+  put(lp.w2h_bf16p, 2, w2h);
+  put(lp.w2x_bf16s, 2, w2x);
+  put(lp.w2m_bf16s, 2, w2m);
+  put(lp.w2x_bf16s16, 2, w2x);
+  put(lp.w2x_bf16s_lo, 2, w2x);
+  put(lp.w2m_bf16s_lo, 2, w2m);
+  put(lp.w2xT_bf16, 2, w2x);
+  put(lp.w2mT_bf16, 2, w2m);
+  put(lp.w1hl_bf16, 2, (TC / 32) * 3 * 2 * 512);
+  put(lp.w2m_bf16s16, 2, w2m);
+  put(lp.w2m_f16s16, 2, w2m);
+  put(lp.w2x_f16s16, 2, w2x);
+  put(lp.w2m_f16s, 2, w2m);
+  put(lp.w2h_f16p, 2, w2h);
+  lp.w1h_f16k = lp.w1h_f16k_lo = lp.w2h_f16p_lo = nullptr;
+  if (md.HP <= 64 && H + md.MP > split_k / 2 && H + md.MP <= split_k) {   // shapes of the split-operand node MLP
+    put(lp.w1h_f16k, 2, WhP * split_k);
+    put(lp.w1h_f16k_lo, 2, WhP * split_k);
+    put(lp.w2h_f16p_lo, 2, w2h);
+  }
+  put(lp.w2x_f16s, 2, w2x);
+  put(lp.w2x_c8w, 1, 2 * w2x);   // e4m3 heads + remainders: 2 bytes per weight
+  put(lp.w2m_c8w, 1, 2 * w2m);
+  put(lp.c8_exp, 4, 8);          // [0..3] scale exponents {x: hi, lo, m: hi, lo}, [4..5] max |w| scratch
+  return off;
 }
 
 bool fork_candidate(int E, int WxP) {

@@ -68,6 +68,13 @@ __host__ __device__ inline size_t edge_a1_bytes(int R) {
 __host__ __device__ inline size_t edge_smem_bytes(int R, int MP) {
   return edge_smem_small(R) + 2 * edge_a1_bytes(R) + (size_t)R * (MP + 1) * 4;
 }
+// LDS of the fp32 node_post_kernel (egnn_forward.hip); egnn_set_model (pack.hip) checks it against the budget
+constexpr int kPostHC = 512;   // hidden columns kept in LDS at a time
+__host__ __device__ inline size_t post_smem_bytes(int K1P, int WhP) {
+  const int hc = WhP < kPostHC ? WhP : kPostHC;
+  size_t hs = (size_t)hc * 33 * 4, red = (size_t)4 * 16 * 64 * 4;
+  return (size_t)K1P * 33 * 4 + (hs > red ? hs : red);
+}
 
 
 // Sum of d^2 over the edges node n receives, as left by the v4 edge kernels in component 3 of the coordinate sums
@@ -318,7 +325,6 @@ bool node_post_bf16_supported(const PostParams& q);
 int init_node_bf16_attributes();
 
 bool edge_bf16_v3_supported(const EdgeParams& p);
-int edge_v3_rows();
 int launch_edge_bf16_v4_m(const EdgeParams& p, hipStream_t st);
 int launch_edge_bf16_v3_x(const EdgeParams& p, hipStream_t st);
 int launch_edge_bf16_v3_x_bwd(const EdgeParams& p, hipStream_t st);

@@ -197,7 +197,8 @@ int egcl_backward_scatter_geom(void* stream, int n_edges, int nparts, const int3
  *   g_a2x [n_edges, Wx], g_a2m [n_edges, M]  bf16 = dL/d(second-layer pre-activation) (what egcl_backward_heads leaves),
  *   g_diff [n_edges, 3] and the column sums ADDED to g_b2x, g_w3, g_b3, g_b2m, g_wa, g_ba, as egcl_backward_heads does.
  * g_sum_x [N,3] must already carry the 1/(G+1) factor; g_sum_m is [N, M].  egcl_backward_fused_supported = 1 if the
- * context's model takes this path. */
+ * context's model takes this path; it is asked on the packed streams of layer 0, so it answers 0 (and the entry points of this
+ * path report the path as unavailable) until egnn_pack_layer has packed that layer. */
 int egcl_backward_fused_supported(egnn_ctx* ctx);
 int egcl_backward_table(egnn_ctx* ctx, void* stream, int layer, const float* d_h);
 int egcl_backward_edge_recompute(egnn_ctx* ctx, void* stream, int layer, const float* d_x, const float* d_g_sum_x,

@@ -79,8 +79,8 @@ def geometry(x, dst, src, model=False):
 # ---------------------------------------------------------------------------------------------------------------------------
 def tables(h, W1, b1, H, model=False):
     """P = h W1[:, :H]^T + b1, Q = h W1[:, H:2H]^T, wd = W1[:, 2H] (egcl_backward_table; generic chain: autograd.py:_first_layer_operands).
-    model: the fast path's table -- weights and bias times -log2(e) rounded to fp32 (egnn_forward.hip:1626-1630 scale_copy),
-    entries clamped to +-32000 and rounded to fp16 (egnn_forward.hip:165 table_store); returns SCALED values."""
+    model: the fast path's table -- weights and bias times -log2(e) rounded to fp32 (pack.hip: egnn_pack_layer, scale_copy),
+    entries clamped to +-32000 and rounded to fp16 (egnn_forward.hip: table_store); returns SCALED values."""
     h, W1, b1 = d(h), d(W1), d(b1)
     if model:
         W1, b1 = f32(W1 * K_NEG_LOG2E), f32(b1 * K_NEG_LOG2E)
@@ -120,9 +120,9 @@ def l1_grad(g_s1, tab, d2, dst, src, model=False, store=None):
 def forward_kept(tab_x, tab_m, d2, dst, src, W2x, b2x, W2m, b2m, w3, b3, model=False, s1x=None, s1m=None):
     """What egcl_forward_save keeps (include/egnn_amd.h, egcl_forward_save): s1 = -log2(e) SiLU(a1), t2 = -log2(e) (W2 SiLU(a1) + b2)
     for both MLPs and s_e = w3 . SiLU(a2x + b2x) + b3.  s1x / s1m given: start from those stored activations instead.
-    model: s1 rounded to bf16 (the MFMA operand, kernels.h:256); W2 times -ln 2 rounded to bf16 (egnn_forward.hip:1635-1638);
-    fp32 accumulation; t2 = fma(acc, -log2 e, b2 * -log2 e) (edge_x_m16.hip:324, bias scaled at egnn_forward.hip:1631,1633) stored
-    as bf16 (edge_x_m16.hip:342); s_e from the UNROUNDED t2 with w3 * -ln 2 in fp32 (edge_x_m16.hip:379-385, egnn_forward.hip:1632)."""
+    model: s1 rounded to bf16 (the MFMA operand, kernels.h:256); W2 times -ln 2 rounded to bf16 (pack.hip: egnn_pack_layer);
+    fp32 accumulation; t2 = fma(acc, -log2 e, b2 * -log2 e) (edge_x_m16.hip:324, bias scaled in pack.hip: egnn_pack_layer) stored
+    as bf16 (edge_x_m16.hip:342); s_e from the UNROUNDED t2 with w3 * -ln 2 in fp32 (edge_x_m16.hip:379-385, pack.hip: egnn_pack_layer)."""
     out = NS()
     for name, tab, W2, b2, s1 in (("x", tab_x, W2x, b2x, s1x), ("m", tab_m, W2m, b2m, s1m)):
         W2, b2 = d(W2), d(b2)
@@ -163,7 +163,7 @@ def heads(t2x, t2m, diff, dst, g_sum_x, g_sum_m, s_e, w3, wa, ba, scaled=False, 
     (edge_bwd_heads.hip:9-12): t2 = second-layer pre-activations INCLUDING the bias (scaled: times -log2 e, as kept).
     Returns dL/da2x, dL/da2m, g_diff and the six sums g_b2x, g_w3, g_b3, g_b2m, g_wa, g_ba.
     model (heads_saved): w3 and wa arrive times -ln 2 and are multiplied back by -log2 e in fp32 (edge_bwd_heads.hip:66,114 on
-    egnn_forward.hip:1632,1634); dL/da2 stored as bf16 (edge_bwd_heads.hip:80,156) while the column sums take the unrounded
+    pack.hip: egnn_pack_layer); dL/da2 stored as bf16 (edge_bwd_heads.hip:80,156) while the column sums take the unrounded
     values (edge_bwd_heads.hip:78,154)."""
     t2x, t2m, diff, s_e = d(t2x), d(t2m), d(diff), d(s_e)
     gx, gm = d(g_sum_x)[dst], d(g_sum_m)[dst]
@@ -199,7 +199,7 @@ def heads(t2x, t2m, diff, dst, g_sum_x, g_sum_m, s_e, w3, wa, ba, scaled=False, 
 
 def dgrad(g_a2, W2, a1, scaled=False, model=False, form="chain"):
     """g1 = (g_a2 . W2) * SiLU'(a1) (egcl_backward_dgrad, egcl_backward_dgrad_reduce, or GEMM + egcl_backward_l1_grad).
-    model: W2 rounded to bf16 (pack_frags_bf16_T, egnn_forward.hip:1662-1663), fp32 accumulation;
+    model: W2 rounded to bf16 (pack.hip: pack_frags_bf16_T), fp32 accumulation;
       form "chain" (edge_bwd_dgrad.hip): the product is rounded to bf16 BEFORE SiLU' (:90) and g1 after it (:116-117);
       form "graph" (edge_bwd_dgrad_graph.hip): g1 stays fp32 (:294-297); the node sums take bf16(g1) (:308) -- see first_reduce."""
     g_a2, W2 = d(g_a2), d(W2)

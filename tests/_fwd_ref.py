@@ -125,13 +125,13 @@ def assert_features(b, R_):
 # ---- operand roundings ----------------------------------------------------------------------------------------------------------
 def fp16s(t):
     """fp16 as the kernels produce it: from the fp32 value, nearest even, saturating (MODE.FP16_OVFL, kernels.h:216-224; the packs
-    clamp explicitly, egnn_forward.hip:57)"""
+    clamp explicitly, pack.hip: to_operand)"""
     return fp16(t.clamp(-F16_MAX, F16_MAX))
 
 
 def split(t, rnd):
     """head + remainder of a split operand: hi = rnd(v), lo = rnd(v - hi) (edge_bf16x3.hip:35-38, node_bf16.hip:162-168,
-    egnn_forward.hip:58, :100)"""
+    pack.hip: to_operand, pack_frags_bf16_lo)"""
     t = f32(t)
     hi = rnd(t)
     return hi, rnd(t - hi)
@@ -155,7 +155,7 @@ def c8_shift(v):
 def second_layer(s1, W2, b2, prec, model):
     """a2 = W2 s1 + b2 of one edge MLP.  Exact: s1 = SiLU(a1), natural units.  model (every tiled path): s1 = silu_s(a1 scaled) =
     -log2(e) SiLU(a1) unrounded; the weights are W2 * -ln 2 [* 2^8] rounded to fp32 and then to the operand type
-    (egnn_forward.hip:1635-1642, :1652-1656, to_operand :55-60); fp32 accumulation; t2 = fma(acc, -log2(e) [/ 2^8], b2 * -log2(e))
+    (pack.hip: egnn_pack_layer, to_operand); fp32 accumulation; t2 = fma(acc, -log2(e) [/ 2^8], b2 * -log2(e))
     (edge_tile.h:188,228; edge_x_m16.hip:372; edge_small.hip:46) -- returned scaled and UNROUNDED (inference stores no t2).
       bf16    s1 and W2 rounded to bf16 (kernels.h:256)
       fp16    s1 and W2 2^8 rounded to fp16, saturating
@@ -167,7 +167,7 @@ def second_layer(s1, W2, b2, prec, model):
     W2, b2 = d(W2), d(b2)
     if not model:
         return NS(t2=s1 @ W2.t() + b2, abs_t2=s1.abs() @ W2.abs().t() + b2.abs(), Wabs=W2.abs(), scale=1.0, op=torch.zeros_like(s1))
-    if prec == "bf16g":   # generic edge_kernel<BF16>: natural units, s1 and W2 rounded to bf16 (egnn_forward.hip:486-487, :1610,1614)
+    if prec == "bf16g":   # generic edge_kernel<BF16>: natural units, s1 and W2 rounded to bf16 (egnn_forward.hip: gemm_bf16, pack.hip: egnn_pack_layer)
         A, Wo = bf16(s1), bf16(W2)
         return NS(t2=A @ Wo.t() + b2, abs_t2=A.abs() @ Wo.abs().t() + b2.abs(), Wabs=Wo.abs(), scale=1.0, op=R.ulp_bf16(f32(s1)))
     b2s = f32(b2 * K_NEG_LOG2E)
@@ -206,8 +206,8 @@ def second_layer(s1, W2, b2, prec, model):
 
 def table(h, W1, b1, H, kind):
     """first-layer table of one edge MLP.  kind "exact"; "f16s" = the half-precision paths' table (_bwd_ref.tables(model=True):
-    scaled, fp16); "f32s" = the fp32 table of bf16x3 / f16c8 on the scaled weights (egnn_forward.hip:1222,1235 use_scaled_pack,
-    :1627-1630 scale_copy; node_pre_mfma_kernel<float>: exact fp32 MFMA, no rounding modelled)"""
+    scaled, fp16); "f32s" = the fp32 table of bf16x3 / f16c8 on the scaled weights (egnn_forward.hip: plan_edge, set_edge_streams;
+    pack.hip: egnn_pack_layer, scale_copy; node_pre_mfma_kernel<float>: exact fp32 MFMA, no rounding modelled)"""
     if kind in ("exact", "f16s"):
         t = tables(h, W1, b1, H, kind == "f16s")
         t.half = kind == "f16s"
@@ -227,7 +227,7 @@ def silu_s(t):
 
 def edge_pass(p, H, h, x, dst, src, node_graph, N, B, scope, prec="fp32", model=False):
     """One edge pass.  p: the layer's parameters (keys mlp_x.0.weight ... attention.0.bias).  prec "fp32" with model=True is the
-    generic fp32 kernel: no operand rounding, natural units (egnn_forward.hip:661-767); "bf16g" is the generic kernel in bf16 (message
+    generic fp32 kernel: no operand rounding, natural units (egnn_forward.hip: edge_kernel); "bf16g" is the generic kernel in bf16 (message
     widths above 256, which no tiled kernel takes: fp32 table, bf16 operands); every other precision is its tiled path.
     -> NS(sum_m [N, M], sum_x [N, 3], sq [B] or [1], abs_sum_m, abs_sum_x, e = per-edge intermediates for the bounds)"""
     scaled = model and prec not in ("fp32", "bf16g")
@@ -245,7 +245,7 @@ def edge_pass(p, H, h, x, dst, src, node_graph, N, B, scope, prec="fp32", model=
         setattr(e, nm, NS(tab=tab, pq=pq, wd2=wd2, a1=a1, s1=s1, sl=sl, K=a1.shape[1]))
     w3, b3 = d(p["mlp_x.4.weight"]).reshape(-1), d(p["mlp_x.4.bias"]).reshape(())
     wa, ba = d(p["attention.0.weight"]).reshape(-1), d(p["attention.0.bias"]).reshape(())
-    if scaled:   # heads on the scaled values: w3 and wa arrive times -ln 2 (egnn_forward.hip:1632,1634), edge_tile.h:171-243
+    if scaled:   # heads on the scaled values: w3 and wa arrive times -ln 2 (pack.hip: egnn_pack_layer), edge_tile.h:171-243
         e.w3, e.wa = f32(w3 * K_NEG_LN2), f32(wa * K_NEG_LN2)
         e.sx, e.ms = silu_s(e.x.sl.t2), silu_s(e.m.sl.t2)
         e.c = K_NEG_LN2                                   # edge_tile.h:242: the gate also undoes the scale of mval
@@ -275,7 +275,7 @@ def edge_bounds(o, H, dst, src, N, deg, nsplit):
     """[2, ...] uncertainties of sum_m, sum_x of a MODEL-mode edge_pass o: index 0 = `acc` (fp32 arithmetic only), 1 = acc + `prop`
     (documented re-roundings of values the test cannot read back, each of which may flip by one spacing between device and model).
       a1     fp16 table: one fp16 ulp per entry and for their fp16 sum + the table product's own error (2^-15 for the split-operand
-             kernel H <= 48, egnn_forward.hip:278-282; (H + 2) 2^-24 else) -- prop, as tests/test_gpu_bwd_stages.py;
+             kernel H <= 48, egnn_forward.hip: node_pre_hilo_kernel; (H + 2) 2^-24 else) -- prop, as tests/test_gpu_bwd_stages.py;
              fp32 table: (H + 2) 2^-24 sum|terms| -- acc.  The fma and d2 = sqrtf(.)^2: 2^-24 (|P + Q| + 7 |wd d2|)
       s1     |SiLU'| <= 1.1, OPS operations (+ |a1| for __expf(-v) = exp2(-v log2 e), whose argument is rounded: generic kernel)
              + the operand rounding's spacing (second_layer.op) -- prop
@@ -317,7 +317,7 @@ def edge_bounds(o, H, dst, src, N, deg, nsplit):
 def node_update(p, H, h, x, sum_m, sum_x, sq, node_graph, scope, form="fp32", model=False):
     """h' = mlp_h([h | sum_m]) and x' = x + sum_x / (sqrt(sq) + 1) from GIVEN aggregates.  model, per node-kernel form:
       bf16   [h | sum_m], both weight matrices and the hidden activation rounded to bf16 (node_bf16.hip:162,197,354;
-             egnn_forward.hip:1657-1658), fp32 accumulation
+             pack.hip: egnn_pack_layer), fp32 accumulation
       split  every operand a fp16 head + fp16 remainder, weights times 2^8, lo.hi + hi.lo + hi.hi (node_bf16.hip:35-41,320-322,
              364-367), accumulators divided by 2^8 where the biases are added (:353,:388); K padded to SPLIT_K with zeros
       fp32   exact (node_post_kernel: v_mfma_f32_32x32x2f32)

@@ -12,7 +12,7 @@ the reference starts from the very same bf16 values), and compares ELEMENT-WISE.
              and v_rcp_f32 are 1-ulp instructions, the rest are correctly rounded), propagated with |SiLU'| <= 1.1, |SiLU''| <= 0.5;
       prop = the documented RE-ROUNDINGS of an input, which may flip between device and model because the value that is rounded
              differs by `acc`-sized amounts: one fp16 ulp per table entry and for their fp16 sum plus the perturbation of the table's
-             split-operand product (egnn_forward.hip:1097 "2^-16"), one ulp_bf16 of the dgrad product that edge_bwd_dgrad.hip:90
+             split-operand product (egnn_forward.hip: launch_node_pre_f16 "2^-16"), one ulp_bf16 of the dgrad product that edge_bwd_dgrad.hip:90
              rounds before SiLU', one ulp_bf16 of every g1 that edge_bwd_dgrad_graph.hip:308 rounds before the node sums.
     The worst |error| / bound is printed as "model"; FACTOR[stage] would multiply the bound (none is needed).
  2. asserted against the EXACT restatement: the norm-wise error (per row of an [edges, W] output, per tensor for sums) is at most
@@ -158,7 +158,7 @@ def _ref(c):
     H = c.H
     r.diff_m, r.d2_m = R.geometry(c.x, c.dst, c.src, True)
     r.diff_e, r.d2_e = R.geometry(c.x, c.dst, c.src, False)
-    # product of the table: bf16 head + remainder operands for H <= 48 (2^-16 each, egnn_forward.hip:1097), fp32 MFMA otherwise
+    # product of the table: bf16 head + remainder operands for H <= 48 (2^-16 each, egnn_forward.hip: launch_node_pre_f16), fp32 MFMA otherwise
     pert = 2.0 ** -15 if H <= 48 else (H + 2) * E24
     for name in ("x", "m"):
         W1, b1 = c.p[f"mlp_{name}.0.weight"], c.p[f"mlp_{name}.0.bias"]

@@ -62,7 +62,7 @@ def _expect(prec, Wx, Wm, Mo, H, Wh, N, E):
     R_, nsplit = (128, 1) if tiled else (64, 1)
     if tiled:
         nsplit = WxP // 256 if prec == "bf16x3" else max(WxP // 512, 1)
-    if half and ok2:                                                                          # small_tiles, egnn_forward.hip:1049-1054
+    if half and ok2:                                                                          # egnn_forward.hip: small_tiles
         R_ = 32 if E <= 2048 else (64 if E <= 6144 else 128)
     K1 = H + MP
     if tiled and prec != "bf16" and H <= 64 and F.SPLIT_K // 2 < K1 <= F.SPLIT_K:             # node_post_split_supported
@@ -157,7 +157,7 @@ def _inputs(graph, H):
 
 def _bind(net, b):
     """the network's context with graph b set.  A context that has once seen N > 1024 never splits the hidden units again
-    (egnn_forward.hip:944 allocates h_partial only then), so a network is used EITHER with batches above 1024 nodes OR below: the
+    (egnn_forward.hip: reserve allocates h_partial only then), so a network is used EITHER with batches above 1024 nodes OR below: the
     hidden split _expect predicts then does not depend on the order of the tests"""
     from diffusion_model_amd.egnn import _context
     big = b.N > 1024
@@ -271,7 +271,7 @@ def _refs(case):
     Mo = case[7] if len(case) > 7 else 256
     b = _graph(graph)
     ex = _expect(prec, Wx, Wm, Mo, H, Wh, b.N, b.E)
-    # a precision outside its tiling runs the generic kernel: bf16 as bf16, the others as the exact fp32 path (egnn_forward.hip:1209-1210,1234)
+    # a precision outside its tiling runs the generic kernel: bf16 as bf16, the others as the exact fp32 path (egnn_forward.hip: plan_edge)
     ran = prec if ex.tiled else ("bf16g" if prec == "bf16" else "fp32")
     return _edge_ref(H, Wx, Wm, Mo, Wh, graph, ran), _edge_ref(H, Wx, Wm, Mo, Wh, graph, None), ex
 
@@ -336,12 +336,12 @@ def test_node_update(case):
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])
 def test_layers_of_egnn_forward_equal_chained_single_layers(prec, L, H, scope):
     """egnn_forward defers the hidden-split finish of a layer (Wh = 1024, N <= 1024) to the next layer's begin -- fused into the
-    half-precision node_pre for H <= 48 (egnn_forward.hip:303-305,1286-1292: "adds them up in split order", what
+    half-precision node_pre for H <= 48 (egnn_forward.hip: node_pre_hilo_kernel, launch_layer_begin: "adds them up in split order", what
     node_post_finish_kernel does), a launch of node_post_finish_kernel for H = 63 -- and, in 'graph' scope, leaves the normaliser to
-    node_post (sq_from_agg, egnn_forward.hip:1373-1374).  Against the same layers chained through egcl_forward:
+    node_post (sq_from_agg, egnn_forward.hip: launch_layer_begin).  Against the same layers chained through egcl_forward:
       * h: bitwise, every node, in 'call' scope and after ONE layer in 'graph' scope;
       * x: bitwise where both paths add the d^2 sums in the same order: 'call' scope (both launch graph_sq_sums_kernel), graphs of
-        more than 64 nodes (node_bf16.hip:222-236 repeats graph_sq_sums_kernel's strided loop and tree, egnn_forward.hip:428-445)
+        more than 64 nodes (node_bf16.hip:222-236 repeats graph_sq_sums_kernel's strided loop and tree, egnn_forward.hip: graph_sq_sums_kernel)
         and graphs without edges.  Graphs of <= 64 nodes go through graph_sq_sum8 (kernels.h:89-118: 8 lanes x 8 nodes, then a
         3-step butterfly), another association of the same terms: after one layer x agrees within (terms 2^-24 sum d^2) taken
         through 1 / (sqrt(.) + 1); from the second layer on such a graph's h and x inherit that difference through d^2, so only the
@@ -355,10 +355,10 @@ def test_layers_of_egnn_forward_equal_chained_single_layers(prec, L, H, scope):
 @pytest.mark.parametrize("prec,Wh,H", [("bf16", 256, 36), ("fp16", 256, 36), ("bf16", 1024, 36), ("bf16", 256, 80), ("bf16x3", 256, 63)],
                          ids=["bf16-single-pass", "split-single-pass", "bf16-hidden-split", "fp32-node-kernel", "bf16x3-split"])
 def test_in_kernel_normaliser_on_128_edge_tiles(prec, Wh, H):
-    """the single-layer C ABI always asks for the d^2 sums (egnn_forward.hip:1711,1740), so only egnn_forward in 'graph' scope leaves
+    """the single-layer C ABI always asks for the d^2 sums (egnn_forward.hip: egcl_forward, egcl_forward_begin), so only egnn_forward in 'graph' scope leaves
     them to node_post (sq_from_agg): here one layer on the R = 128 irregular batch (a node whose d^2 partials span three tiles, graphs
     above and below 64 nodes, graphs without edges) through the single-pass bf16 and split-operand node kernels, the hidden-split
-    form, and the fp32 node kernel, for which launch_layer_end launches graph_sq_sums_kernel after all (egnn_forward.hip:1414-1418:
+    form, and the fp32 node kernel, for which launch_layer_end launches graph_sq_sums_kernel after all (egnn_forward.hip: launch_layer_end:
     x bitwise on every node)"""
     ex = _expect(prec, 512, 256, 256, H, Wh, 458, 7887)
     assert (ex.form, ex.hs, ex.R) == {("bf16", 256, 36): ("bf16", 1, 128), ("fp16", 256, 36): ("split", 1, 128), ("bf16", 1024, 36): ("bf16", 8, 128),
@@ -426,3 +426,76 @@ def test_case_list_reaches_every_node_form_and_tile_height():
     for R_ in (32, 64, 128):
         assert any(f[2] == R_ and f[3] for f in forms), R_
     assert any(not f[3] for f in forms)
+
+
+# ---- the packed parameters' arena: re-pack in place, release and re-carve ------------------------------------------------------------
+# name -> (H, Wx, Wm, Wh, M, atoms per graph), two fully connected graphs each.  By the selection rules restated in _expect:
+#   tiled    the smallest shape on which every precision but fp32 runs its 128-edge-tile kernels (2 x 64 x 63 = 8,064 edges is
+#            beyond the 64-edge small-tile limit of 6,144);
+#   padded   the padded widths of the goldens (WxP = 512, WmP = MP = 256, WhP = 256): fp32 on the generic kernel, bf16 / fp16 on
+#            32-edge tiles, bf16x3 / f16c8 on 128-edge tiles, every one with zero columns;
+#   generic  M = 300 (MP = 512) is outside every tiling: the generic kernel on its bf16 streams (bf16) and its fp32 ones (the rest).
+PACK_SHAPES = {"tiled": (36, 512, 256, 256, 256, 64), "padded": (3, 300, 7, 130, 5, 8), "generic": (36, 256, 256, 256, 300, 8)}
+
+
+@functools.lru_cache(maxsize=None)
+def _pack_graph(shape):
+    H, atoms = PACK_SHAPES[shape][0], PACK_SHAPES[shape][5]
+    b = F.fully_connected_batch((atoms, atoms))
+    plan = dma.GraphPlan(torch.stack((b.dst, b.src)).cuda(), b.N, sizes=b.sizes)
+    g = torch.Generator().manual_seed(23)
+    return b, plan, torch.randn(b.N, H, generator=g).cuda(), (torch.randn(b.N, 3, generator=g) * 1.5).cuda()
+
+
+def _pack_net(shape, seed):
+    H, Wx, Wm, Wh, Mo, _ = PACK_SHAPES[shape]
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        return dma.EquivariantGNN(2, **dims_for(H, Mo, Wm, Wx, Wh)).cuda()
+
+
+def _pack_forward(ctx, net, shape, prec):
+    """set_model (a no-op while the dimensions stay), set_graph, pack (a no-op while no parameter changed) and egnn_forward"""
+    from diffusion_model_amd import _lib
+    _, plan, hd, xd = _pack_graph(shape)
+    layers = list(net.egcl_list)
+    d = layers[0].dims
+    ctx.set_model(len(layers), d["H"], d["M"], d["Wm"], d["Wx"], d["Wh"])
+    ctx.set_graph(plan)
+    ctx.pack(layers)
+    ho, xo = torch.empty_like(hd), torch.empty_like(xd)
+    _lib.check(_lib.lib().egnn_forward(ctx.handle, _lib.stream_ptr(), _lib.PRECISIONS[prec], _lib.NORM_GRAPH, _lib.ptr(hd), _lib.ptr(xd),
+                                       _lib.ptr(ho), _lib.ptr(xo)))
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(ho).all()) and bool(torch.isfinite(xo).all())
+    return ho.cpu(), xo.cpu()
+
+
+@pytest.mark.parametrize("shape", list(PACK_SHAPES))
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "bf16x3", "fp16", "f16c8"])
+def test_repacked_and_recarved_context_equals_a_fresh_one(prec, shape):
+    """a layer's packed streams live in one arena (pack.hip: egnn_pack_layer, host_logic.cpp: carve_layer_pack).  A context that
+    re-packs changed parameters into the arena it has, and one whose arenas were released and carved again for other dimensions
+    and back (pack.hip: egnn_set_model, free_layer), must both compute, bit for bit, what a fresh context packed once computes:
+    a stream the re-pack misses, or one that overlaps its neighbour after the re-carve, changes the output"""
+    from diffusion_model_amd.egnn import _Context
+    H, Wx, Wm, Wh, Mo, _ = PACK_SHAPES[shape]
+    b = _pack_graph(shape)[0]
+    ex = _expect(prec, Wx, Wm, Mo, H, Wh, b.N, b.E)
+    small = 32 if prec in ("bf16", "fp16") else 128          # padded: 112 edges, the half-precision paths take 32-edge tiles
+    want = {"tiled": (prec != "fp32", 128), "padded": (prec != "fp32", small), "generic": (False, 64)}[shape]
+    assert (ex.tiled, ex.R) == (want[0], want[1] if want[0] else 64), (prec, shape, ex.tiled, ex.R)
+    dev = torch.device("cuda")
+    net, ctx = _pack_net(shape, 41), _Context(dev)
+    first = _pack_forward(ctx, net, shape, prec)
+    with torch.no_grad():
+        for p in net.parameters():          # every parameter, in place: the version counters make pack() run again
+            p.mul_(1.25).add_(0.01)
+    again = _pack_forward(ctx, net, shape, prec)
+    fresh = _pack_forward(_Context(dev), net, shape, prec)
+    assert not torch.equal(again[0], first[0]) and not torch.equal(again[1], first[1]), "the changed parameters were not packed"
+    assert torch.equal(again[0], fresh[0]) and torch.equal(again[1], fresh[1]), "re-packed context differs from a fresh one"
+    other = "padded" if shape != "padded" else "tiled"
+    _pack_forward(ctx, _pack_net(other, 43), other, prec)      # the arenas are released and carved for the other dimensions ...
+    back = _pack_forward(ctx, net, shape, prec)                # ... and again for these
+    assert torch.equal(back[0], fresh[0]) and torch.equal(back[1], fresh[1]), "re-carved context differs from a fresh one"

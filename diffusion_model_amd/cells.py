@@ -1,0 +1,320 @@
+"""Local environments of periodic cells: the constructor of the records everything else here consumes.
+
+Every record the reference trains on is the excited oxygen plus the atoms reachable from it in 2, 3 or 4 hops of the "closer than
+2.0 A" relation, cut out of a periodic cell (``make_dataset.py:79-142``: 3x3x3 supercell, full distance matrix,
+``return_index_within_2ang``, nested Python loops, ONE centre per cell).  Here the cut is made on the device, about every centre
+of a batch of cells (or every atom of one type, or any list of atoms), by ``csrc/cells/cell_env.hip``:
+
+* ``bond_list``          -- the periodic bond list (CSR of (neighbour atom, lattice shift) per atom);
+* ``local_environments`` -- the shell cluster about each centre, as one batch that goes straight into the model
+  (``.batch()``), the samplers and ``stats.compare_structures`` (``.to_data_list()``).
+
+The definitions (``csrc/cells/cell_math.h``) are those of the INFINITE lattice: a site is (atom, integer shift), a bond joins
+sites closer than the cutoff, an environment is what ``shells`` bonds reach.  Wherever the reference's search uses no bond that
+wraps round its 3x3x3 supercell the two site sets are identical; where it does, the reference aliases an image onto a site on the
+far side of the supercell (a position about three cell lengths away) and this module does not follow it (INTEGRATION.md,
+"Periodic cells").  Rows are ordered centre first, then by (atom index, shift): the reference's order is the iteration order of a
+Python ``set``.
+
+There is no CPU fallback: the functions need a ROCm device.
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from .data import Batch, GraphData, make_graph
+
+
+def lattice_from_parameters(a: float, b: float, c: float, alpha: float, beta: float, gamma: float) -> torch.Tensor:
+    """Lattice vectors (rows a, b, c; float64 [3, 3]) from lengths in Angstrom and angles in degrees, in the convention of
+    ``pymatgen.core.Lattice.from_parameters`` (what ``make_dataset.py:19,79`` calls): c along z, a in the xz-plane,
+    a = (a sin beta, 0, a cos beta), b = (-b sin alpha cos gamma*, b sin alpha sin gamma*, b cos alpha) with
+    cos gamma* = (cos alpha cos beta - cos gamma) / (sin alpha sin beta).  That library is not installed where this project is
+    built: the convention is pinned by its documentation only, not by execution."""
+    al, be, ga = (math.radians(float(v)) for v in (alpha, beta, gamma))
+    val = (math.cos(al) * math.cos(be) - math.cos(ga)) / (math.sin(al) * math.sin(be))
+    gs = math.acos(max(-1.0, min(1.0, val)))
+    va = [a * math.sin(be), 0.0, a * math.cos(be)]
+    vb = [-b * math.sin(al) * math.cos(gs), b * math.sin(al) * math.sin(gs), b * math.cos(al)]
+    vc = [0.0, 0.0, float(c)]
+    return torch.tensor([va, vb, vc], dtype=torch.float64)
+
+
+class PeriodicCell:
+    """One periodic cell: ``lattice`` float64 [3, 3] (rows a, b, c), ``frac`` float64 [n, 3] (any real value; wrapped to [0, 1)
+    when used), ``types`` int32 [n] in [0, num_types).  The species are given either as ``species_onehot`` [n, A] (the reference's
+    node feature: O = [1, 0], Si = [0, 1]) or as ``types`` (``num_types`` defaults to max + 1)."""
+
+    def __init__(self, lattice, frac_coords, species_onehot=None, types=None, id=None, num_types: Optional[int] = None):
+        self.lattice = torch.as_tensor(lattice, dtype=torch.float64).detach().cpu().reshape(3, 3).clone()
+        self.frac = torch.as_tensor(frac_coords, dtype=torch.float64).detach().cpu().reshape(-1, 3).clone()
+        n = self.frac.shape[0]
+        if (species_onehot is None) == (types is None):
+            raise ValueError("give species_onehot or types, not both")
+        if species_onehot is not None:
+            oh = torch.as_tensor(species_onehot).detach().cpu()
+            if oh.dim() != 2 or oh.shape[0] != n or oh.shape[1] < 1:
+                raise ValueError("species_onehot must be [n, A]")
+            if n and not bool((((oh == 0) | (oh == 1)).all(1) & (oh.sum(1) == 1)).all()):
+                raise ValueError("every row of species_onehot must be exactly one-hot")
+            self.num_types = int(oh.shape[1]) if num_types is None else int(num_types)
+            self.types = (oh.argmax(1) if n else torch.zeros(0, dtype=torch.long)).to(torch.int32)
+        else:
+            self.types = torch.as_tensor(types).detach().cpu().reshape(-1).to(torch.int32).clone()
+            if self.types.shape[0] != n:
+                raise ValueError("types must be [n]")
+            self.num_types = (int(self.types.max()) + 1 if n else 1) if num_types is None else int(num_types)
+        if n and (int(self.types.min()) < 0 or int(self.types.max()) >= self.num_types):
+            raise ValueError(f"types must lie in [0, {self.num_types})")
+        if not bool(torch.isfinite(self.frac).all()) or not bool(torch.isfinite(self.lattice).all()):
+            raise ValueError("lattice and coordinates must be finite")
+        self.id = id
+
+    @classmethod
+    def from_cartesian(cls, lattice, cart_coords, species_onehot=None, types=None, id=None, num_types=None) -> "PeriodicCell":
+        """the same cell from Cartesian coordinates in Angstrom: frac = cart L^-1 in float64"""
+        L = torch.as_tensor(lattice, dtype=torch.float64).detach().cpu().reshape(3, 3)
+        cart = torch.as_tensor(cart_coords, dtype=torch.float64).detach().cpu().reshape(-1, 3)
+        frac = torch.linalg.solve(L.T, cart.T).T if cart.shape[0] else cart
+        return cls(L, frac, species_onehot=species_onehot, types=types, id=id, num_types=num_types)
+
+    @property
+    def num_atoms(self) -> int:
+        return int(self.frac.shape[0])
+
+    def __repr__(self):
+        return f"PeriodicCell(n={self.num_atoms}, A={self.num_types}, id={self.id!r})"
+
+
+def _as_cells(cells) -> List[PeriodicCell]:
+    cells = [cells] if isinstance(cells, PeriodicCell) else list(cells)
+    if not cells or not all(isinstance(c, PeriodicCell) for c in cells):
+        raise ValueError("cells must be a PeriodicCell or a non-empty sequence of them")
+    return cells
+
+
+def _bond_tiles(sizes) -> np.ndarray:
+    """the work list of egnn_cell_bonds_count / _fill (include/egnn_amd.h): {cell, first centre} for every block of 64 centres"""
+    sz = np.asarray(sizes, dtype=np.int64)
+    per = -(-sz // _lib.CELL_CENTRE_BLOCK)
+    ci = np.repeat(np.arange(sz.size, dtype=np.int64), per)
+    t = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
+    return np.stack([ci, t * _lib.CELL_CENTRE_BLOCK], 1).astype(np.int32).reshape(-1, 2)
+
+
+class _CellBatch:
+    """a batch of cells on the device: host and device copies of cell_ptr and the lattices, device copies of the coordinates,
+    the types and the bond tiles"""
+
+    def __init__(self, cells, device):
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise RuntimeError("periodic-cell environments need an AMD GPU ('cuda' device); there is no CPU fallback")
+        self.cells, self.dev = cells, dev
+        self.sizes = [c.num_atoms for c in cells]
+        self.C, self.N = len(cells), sum(self.sizes)
+        self.A = max(c.num_types for c in cells)
+        self.cell_ptr_h = torch.zeros(self.C + 1, dtype=torch.int32)
+        self.cell_ptr_h[1:] = torch.cumsum(torch.tensor(self.sizes, dtype=torch.int64), 0).to(torch.int32)
+        self.lattice_h = torch.stack([c.lattice.reshape(9) for c in cells]).contiguous()
+        self.types_h = torch.cat([c.types for c in cells]).contiguous()
+        tiles = _bond_tiles(self.sizes)
+        self.n_tiles = len(tiles)
+        self.cell_ptr = self.cell_ptr_h.to(dev)
+        self.lattice = self.lattice_h.to(dev)
+        self.frac = torch.cat([c.frac for c in cells]).contiguous().to(dev)
+        self.types = self.types_h.to(dev)
+        self.tiles = torch.from_numpy(tiles).to(dev)
+
+
+class BondList:
+    """CSR of the periodic bonds of a batch of cells: ``row_ptr`` int32 [N+1]; ``atom`` int32 [E], the neighbour as an index into
+    the concatenated atoms of the batch; ``shift`` int32 [E, 3], the lattice shift of the neighbour's image relative to the wrapped
+    atoms; ``shift_code`` int32 [E] (csrc/cells/cell_math.h); ``cell_ptr`` int32 [C+1] (host).  Rows ascend by (atom, shift)."""
+
+    def __init__(self, row_ptr, atom, shift_code, cell_ptr):
+        self.row_ptr, self.atom, self.shift_code, self.cell_ptr = row_ptr, atom, shift_code, cell_ptr
+
+    @property
+    def shift(self) -> torch.Tensor:
+        return decode_shift(self.shift_code)
+
+    @property
+    def num_bonds(self) -> int:
+        return int(self.atom.shape[0])
+
+
+def decode_shift(code: torch.Tensor) -> torch.Tensor:
+    """shift codes ((sx + 4) 9 + (sy + 4)) 9 + (sz + 4) -> int32 [..., 3]"""
+    c = code.to(torch.int32)
+    return torch.stack((c // 81 - 4, c // 9 % 9 - 4, c % 9 - 4), -1)
+
+
+def _bond_args(cb: _CellBatch, cutoff: float):
+    return (_lib.stream_ptr(), cb.C, cb.N, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice),
+            _lib.ptr(cb.frac), float(cutoff), _lib.ptr(cb.tiles), cb.n_tiles)
+
+
+def _bonds_count(cb: _CellBatch, cutoff: float) -> torch.Tensor:
+    deg = torch.empty(cb.N, dtype=torch.int32, device=cb.dev)
+    _lib.check(_lib.lib().egnn_cell_bonds_count(*_bond_args(cb, cutoff), _lib.ptr(deg)))
+    return deg
+
+
+def _bonds_fill(cb: _CellBatch, cutoff: float, row_ptr: torch.Tensor, E: int):
+    atom = torch.empty(max(E, 1), dtype=torch.int32, device=cb.dev)[:E]
+    code = torch.empty(max(E, 1), dtype=torch.int32, device=cb.dev)[:E]
+    _lib.check(_lib.lib().egnn_cell_bonds_fill(*_bond_args(cb, cutoff), _lib.ptr(row_ptr), E, _lib.ptr(atom) if E else None,
+                                               _lib.ptr(code) if E else None))
+    return atom, code
+
+
+def _bond_list(cb: _CellBatch, cutoff: float) -> BondList:
+    deg = _bonds_count(cb, cutoff)
+    row_ptr = torch.zeros(cb.N + 1, dtype=torch.int32, device=cb.dev)
+    total = torch.cumsum(deg.long(), 0)
+    E = int(total[-1]) if cb.N else 0
+    if E >= 2 ** 31:
+        raise ValueError("more than 2^31 - 1 bonds")
+    row_ptr[1:] = total.to(torch.int32)
+    atom, code = _bonds_fill(cb, cutoff, row_ptr, E)
+    return BondList(row_ptr, atom, code, cb.cell_ptr_h)
+
+
+def _env_args(cb: _CellBatch, bonds: BondList, cc: torch.Tensor, shells: int, max_atoms: int):
+    """the arguments the two environment entries share after the cell arrays: the bond list, the centres ``cc`` int32 [2, M] =
+    (cell, atom) on the device, shells, max_atoms"""
+    E, M = bonds.num_bonds, int(cc.shape[1])
+    return (_lib.ptr(bonds.row_ptr), E, _lib.ptr(bonds.atom) if E else None, _lib.ptr(bonds.shift_code) if E else None, M,
+            _lib.ptr(cc[0]) if M else None, _lib.ptr(cc[1]) if M else None, int(shells), int(max_atoms))
+
+
+def _env_count(cb: _CellBatch, bonds: BondList, cc: torch.Tensor, shells: int, max_atoms: int) -> torch.Tensor:
+    M = int(cc.shape[1])
+    size = torch.empty(max(M, 1), dtype=torch.int32, device=cb.dev)[:M]
+    _lib.check(_lib.lib().egnn_cell_env_count(_lib.stream_ptr(), cb.C, cb.N, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.cell_ptr),
+                                              *_env_args(cb, bonds, cc, shells, max_atoms), _lib.ptr(size) if M else None))
+    return size
+
+
+def _env_fill(cb: _CellBatch, bonds: BondList, cc: torch.Tensor, shells: int, max_atoms: int, env_ptr: torch.Tensor, T: int):
+    """-> (atom, shift code, type: int32 [T]; pos float32 [T, 3])"""
+    e_atom, e_code, e_type = (torch.empty(max(T, 1), dtype=torch.int32, device=cb.dev)[:T] for _ in range(3))
+    pos = torch.empty(max(T, 1), 3, dtype=torch.float32, device=cb.dev)[:T]
+    _lib.check(_lib.lib().egnn_cell_env_fill(_lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h),
+                                             _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice), _lib.ptr(cb.frac), _lib.ptr(cb.types),
+                                             *_env_args(cb, bonds, cc, shells, max_atoms), _lib.ptr(env_ptr), T,
+                                             *((_lib.ptr(t) if T else None) for t in (e_atom, e_code, e_type, pos))))
+    return e_atom, e_code, e_type, pos
+
+
+def bond_list(cells: Union[PeriodicCell, Sequence[PeriodicCell]], cutoff: float = 2.0, device=None) -> BondList:
+    """The periodic bond list of every atom of a batch of cells (``return_index_within_2ang`` over the distance matrix of
+    ``make_dataset.py:50-57,99``, without the matrix): image (j, s), s in {-1, 0, 1}^3, of atom j is bonded to atom i iff it is
+    closer than ``cutoff`` in fp64 and is not i itself.  A cell with a perpendicular width below ``cutoff`` (27 images would not
+    hold every bond) or a singular lattice is refused (``EgnnError``, naming the cell)."""
+    return _bond_list(_CellBatch(_as_cells(cells), device), cutoff)
+
+
+def _centres(cb: _CellBatch, centres):
+    """-> (int64 [M] indices into the concatenated atoms, int64 [M] cells), on the host"""
+    if centres is None:
+        idx = torch.arange(cb.N, dtype=torch.int64)
+    elif isinstance(centres, (int, np.integer)) and not isinstance(centres, bool):
+        if not 0 <= int(centres) < cb.A:
+            raise ValueError(f"centre type {int(centres)} outside [0, {cb.A})")
+        idx = torch.nonzero(cb.types_h == int(centres)).reshape(-1)
+    else:
+        idx = torch.as_tensor(centres).detach().cpu().reshape(-1).to(torch.int64)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= cb.N):
+            raise ValueError(f"a centre lies outside the {cb.N} atoms of the batch")
+    cell = torch.searchsorted(cb.cell_ptr_h.long(), idx, right=True) - 1
+    return idx, cell
+
+
+class EnvironmentBatch:
+    """The environments of M centres, concatenated (T rows): ``pos`` float32 [T, 3] relative to the centre, ``x`` int64 [T, A]
+    one-hot species, ``exO`` float32 [T, 1] (1 for the centre, row 0 of every environment) on the device; ``sizes`` (list) and
+    ``ptr`` int64 [M+1] on the host; the provenance of every row, ``atom`` int64 [T] (index inside its cell) and ``shift`` int32
+    [T, 3] (lattice shift of the image, relative to the wrapped atoms; ``shift_code`` int32 [T] is its code), on the device; ``centre_cell`` / ``centre_atom`` int64 [M]
+    on the host; ``id`` (list of (cell id, atom)); ``bonds``, the ``BondList`` of the cells."""
+
+    def __init__(self, pos, x, exO, sizes, ptr, atom, shift, shift_code, centre_cell, centre_atom, id, bonds):
+        self.pos, self.x, self.exO, self.sizes, self.ptr = pos, x, exO, sizes, ptr
+        self.atom, self.shift, self.shift_code = atom, shift, shift_code
+        self.centre_cell, self.centre_atom, self.id, self.bonds = centre_cell, centre_atom, id, bonds
+
+    @property
+    def num_graphs(self) -> int:
+        return len(self.sizes)
+
+    def to_data_list(self) -> List[GraphData]:
+        """one ``GraphData`` per centre in ``make_graph``'s schema (make_dataset.py:121-142 without the spectrum)"""
+        x, pos = self.x.cpu(), self.pos.cpu()
+        out = []
+        for m in range(self.num_graphs):
+            lo, hi = int(self.ptr[m]), int(self.ptr[m + 1])
+            out.append(make_graph(x[lo:hi], pos[lo:hi], graph_id=self.id[m]))
+        return out
+
+    def batch(self) -> Batch:
+        """the fully connected ``data.Batch`` of these environments, its graph plan built on the device from the sizes: no edge
+        list is made on, or copied from, the host"""
+        from .graph import fully_connected_plan, plan_edge_index
+        if self.num_graphs == 0:
+            raise ValueError("no environment to batch")
+        dev = self.pos.device
+        out = Batch()
+        out.x, out.pos, out.exO = self.x, self.pos, self.exO
+        out.fully_connected = True
+        out._plan = fully_connected_plan(self.sizes, dev)
+        out.edge_index = plan_edge_index(out._plan)
+        out.batch = out._plan.batch
+        out.ptr, out.sizes, out.num_graphs, out.id = self.ptr.clone(), list(self.sizes), self.num_graphs, list(self.id)
+        return out
+
+
+def local_environments(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centres=None, shells: int = 2, cutoff: float = 2.0,
+                       max_atoms: int = 256, device=None) -> EnvironmentBatch:
+    """The environment of every requested centre: the centre plus the sites (atom, lattice shift) reachable from it in at most
+    ``shells`` (1..4) bonds of the infinite lattice -- ``make_dataset.py:101-107`` (2NN), ``:177-188`` (3NN), ``:258-272`` (4NN)
+    -- with positions ``float32((frac_j - frac_i + shift) L)`` relative to the centre (``:111``).
+
+    ``centres``: None = every atom of every cell; an int = every atom of that type index (0 = O in the reference's one-hot);
+    or an index tensor into the concatenated atoms of ``cells`` -- any order, duplicates allowed; the outputs follow its order.
+    A centre without a bond yields a one-atom environment (the reference's drivers skip those; filter on ``sizes``).  A centre
+    whose environment exceeds ``max_atoms`` (<= 1024) raises ValueError naming cell and atom."""
+    cb = _CellBatch(_as_cells(cells), device)
+    shells, max_atoms = int(shells), int(max_atoms)
+    bonds = _bond_list(cb, cutoff)
+    idx_h, cell_h = _centres(cb, centres)
+    M = int(idx_h.numel())
+    cc = torch.stack((cell_h, idx_h)).to(torch.int32).to(cb.dev)
+    size_h = _env_count(cb, bonds, cc, shells, max_atoms).cpu().long()
+    local_h = idx_h - cb.cell_ptr_h.long()[cell_h]
+    over = torch.nonzero(size_h > max_atoms).reshape(-1)
+    if over.numel():
+        m = int(over[0])
+        raise ValueError(f"cell {int(cell_h[m])}, atom {int(local_h[m])}: the environment of {shells} shells holds more than "
+                         f"max_atoms = {max_atoms} sites ({int(over.numel())} such centre(s)); raise max_atoms (at most "
+                         f"{_lib.CELL_MAX_ENV_ATOMS}) or lower shells / cutoff")
+    ptr_h = torch.zeros(M + 1, dtype=torch.int64)
+    ptr_h[1:] = torch.cumsum(size_h, 0)
+    T = int(ptr_h[-1])
+    if T >= 2 ** 31:
+        raise ValueError("more than 2^31 - 1 rows")
+    env_ptr = ptr_h.to(torch.int32).to(cb.dev)
+    e_atom, e_code, e_type, pos = _env_fill(cb, bonds, cc, shells, max_atoms, env_ptr, T)
+    row_cell = torch.repeat_interleave(cell_h.to(cb.dev), size_h.to(cb.dev), output_size=T)
+    exO = torch.zeros(T, 1, dtype=torch.float32, device=cb.dev)
+    if M:
+        exO[ptr_h[:-1].to(cb.dev)] = 1.0
+    ids = [(cb.cells[c].id, a) for c, a in zip(cell_h.tolist(), local_h.tolist())]
+    return EnvironmentBatch(pos=pos, x=torch.nn.functional.one_hot(e_type.long(), cb.A), exO=exO, sizes=size_h.tolist(), ptr=ptr_h,
+                            atom=e_atom.long() - cb.cell_ptr.long()[row_cell], shift=decode_shift(e_code), shift_code=e_code,
+                            centre_cell=cell_h, centre_atom=local_h, id=ids, bonds=bonds)

@@ -503,6 +503,59 @@ int egnn_struct_counts_host(int B, int A, const float* pos, const int32_t* type,
                             float cutoff, double dtheta, int max_cn, int32_t* counts, int32_t* cn, int32_t* angles,
                             int32_t* overflow);
 
+/* ---- local environments of periodic cells (csrc/cells/cell_env.hip; definitions in csrc/cells/cell_math.h) ---------------
+ * Every record of the reference is a local environment cut out of a periodic cell: make_dataset.py:79-142 builds the 3x3x3
+ * supercell (:79-92), its full distance matrix (:99), takes the sites closer than 2.0 A to the excited oxygen
+ * (return_index_within_2ang, :50-57, :101) and theirs in nested loops to 2NN / 3NN / 4NN (:103-107), and stores positions
+ * relative to the centre (:111), for ONE centre per cell.  These entries make the same cut about ANY set of centres of a batch of
+ * cells, on the infinite lattice (where the reference's search wraps round its supercell it aliases an image onto a far site;
+ * INTEGRATION.md, "Periodic cells").
+ *   cells    cell_ptr int32 [C+1] over N atoms, lattice double [C, 9] (rows a, b, c), frac double [N, 3] (any real value; wrapped
+ *            to [0, 1) as f - floor(f), all shifts refer to the wrapped atoms), type int32 [N] in [0, A), A <= 4.  cell_ptr and
+ *            lattice are given twice: HOST copies for the checks (sizes, a singular lattice, a perpendicular width below the
+ *            cutoff -- with every width >= cutoff the 27 images s in {-1,0,1}^3 hold every bond) and device copies for the kernels.
+ *   bond     site (j, s) != (i, 0) is bonded to atom i iff |(frac_j - frac_i + s) L|^2 < cutoff^2 in fp64, one fixed order.
+ *   shift    code ((s_x + 4) 9 + (s_y + 4)) 9 + (s_z + 4) in [0, 729); 364 is no shift.
+ *   tiles    d_tiles int32 [n_tiles, 2] = {cell, first centre}: 64 centres of a cell (local index, every multiple of 64 below
+ *            its size once), one workgroup each, built by the caller; a kernel checks every entry.
+ * Atom indices in every list count over the whole batch (0 .. N-1).  Bad arguments return EGNN_EINVAL, naming the cell where
+ * one is at fault, before anything is launched.  Results are bitwise reproducible.
+ *
+ * egnn_cell_bonds_count / _fill replace the distance matrix of make_dataset.py:99 and return_index_within_2ang (:50-57) for every
+ * atom: d_degree int32 [N] = bonds of each atom; the caller takes the exclusive prefix sum d_row_ptr int32 [N+1]; the fill pass
+ * writes d_bond_atom / d_bond_shift int32 [n_bonds], every row ascending by (atom, shift code). */
+int egnn_cell_bonds_count(void* stream, int C, int N, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                          const double* d_lattice, const double* d_frac, double cutoff, const int32_t* d_tiles, int n_tiles,
+                          int32_t* d_degree);
+int egnn_cell_bonds_fill(void* stream, int C, int N, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                         const double* d_lattice, const double* d_frac, double cutoff, const int32_t* d_tiles, int n_tiles,
+                         const int32_t* d_row_ptr, int n_bonds, int32_t* d_bond_atom, int32_t* d_bond_shift);
+/* egnn_cell_env_count / _fill replace the nested neighbour loops of make_dataset.py:101-107 (2NN), :177-188 (3NN) and :258-272
+ * (4NN), and the positions of :111: for centre m (atom d_centre[m] of cell d_centre_cell[m]; any order, duplicates allowed)
+ * the sites reachable in at most `shells` (1..4) bonds, the centre first, the others ascending by (atom, shift code).  One
+ * wavefront per centre; at most max_atoms (1..1024) sites each.  The count pass writes d_size int32 [M]; a centre whose
+ * environment exceeds max_atoms gets the sentinel max_atoms + 1, and a centre outside its cell 0.  The caller takes the prefix sum
+ * d_env_ptr int32 [M+1] (sentinels counted as 0) and the fill pass writes, for every centre whose size equals its share of
+ * d_env_ptr, d_env_atom, d_env_shift, d_env_type int32 [n_sites] and d_env_pos float [n_sites, 3] =
+ * float((frac_j - frac_i + s) L), rounded once from fp64; other centres write nothing. */
+int egnn_cell_env_count(void* stream, int C, int N, const int32_t* cell_ptr, const int32_t* d_cell_ptr, const int32_t* d_row_ptr,
+                        int n_bonds, const int32_t* d_bond_atom, const int32_t* d_bond_shift, int M, const int32_t* d_centre_cell,
+                        const int32_t* d_centre, int shells, int max_atoms, int32_t* d_size);
+int egnn_cell_env_fill(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                       const double* d_lattice, const double* d_frac, const int32_t* d_type, const int32_t* d_row_ptr, int n_bonds,
+                       const int32_t* d_bond_atom, const int32_t* d_bond_shift, int M, const int32_t* d_centre_cell,
+                       const int32_t* d_centre, int shells, int max_atoms, const int32_t* d_env_ptr, int n_sites, int32_t* d_env_atom,
+                       int32_t* d_env_shift, int32_t* d_env_type, float* d_env_pos);
+/* Host statement of the four entries above (make_dataset.py:79-111 about every requested centre): HOST pointers, no GPU, no
+ * tiles, the same definitions in plain C++.  bond_ptr int32 [N+1] and env_size int32 [M] are always written; the lists are written
+ * where their pointers are given and bond_cap / env_cap hold them (call once with capacities 0 to learn the sizes).  An
+ * environment above max_atoms has size max_atoms + 1 and no rows.  Also EGNN_EINVAL: a type outside [0, A), a coordinate that is
+ * not finite, a centre outside its cell. */
+int egnn_cell_env_host(int C, int A, const int32_t* cell_ptr, const double* lattice, const double* frac, const int32_t* type,
+                       double cutoff, int M, const int32_t* centre_cell, const int32_t* centre, int shells, int max_atoms,
+                       int32_t* bond_ptr, int64_t bond_cap, int32_t* bond_atom, int32_t* bond_shift, int32_t* env_size,
+                       int64_t env_cap, int32_t* env_atom, int32_t* env_shift, int32_t* env_type, float* env_pos);
+
 /* ---- the two small networks at the edge of the path ---------------------------------------------------
  * gamma_tilde(t_i) = l1(t_i) + l3(sigmoid(l2(l1(t_i)))) of GammaNetwork (SNR.py:50-52) with PositiveLinear's softplus weights
  * (:5-22) for n time points; d_l1_w [1], d_l2_w [hidden], d_l3_w [hidden] are the RAW parameters (l1.weight, l2.weight,

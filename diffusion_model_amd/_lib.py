@@ -59,8 +59,9 @@ def edge_kernel_sources_sha256() -> str:
 
 def forward_sources_sha256() -> str:
     """Fingerprint of every source an inference forward of any precision runs through (edge kernels of all precisions, node
-    kernels, packing): what a measured error table (tools/prec_errors.py) is valid for."""
-    return _sources_sha256(("egnn_forward.hip", "pack.hip", "edge_x_m16.hip", "edge_bf16_v4.hip", "edge_bf16_v3.hip", "edge_small.hip",
+    kernels, packing, and the dispatch: plan_forward in host_logic.cpp): what a measured error table (tools/prec_errors.py) is
+    valid for."""
+    return _sources_sha256(("egnn_forward.hip", "host_logic.h", "host_logic.cpp", "pack.hip", "edge_x_m16.hip", "edge_bf16_v4.hip", "edge_bf16_v3.hip", "edge_small.hip",
                             "edge_bf16x3.hip", "edge_f16c8w.hip", "edge_f16c8w_mphase2.inc", "edge_f16c8w_mphasek.inc", "node_bf16.hip",
                             "edge_tile.h", "kernels.h", "common.h", "layer_pack.h", "diag.h"))
 

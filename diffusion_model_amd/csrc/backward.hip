@@ -459,12 +459,12 @@ using namespace egnn;
 extern "C" {
 
 int egcl_read_aggregates(egnn_ctx* c, void* stream, int norm_scope, float* sum_m, float* sum_x, float* sq_sums) {
-  if (!c || c->N == 0 || c->last_R <= 0) { set_error("egcl_read_aggregates: no layer has been run on this context"); return EGNN_ESTATE; }
+  if (!c || c->N == 0 || c->plan.R <= 0) { set_error("egcl_read_aggregates: no layer has been run on this context"); return EGNN_ESTATE; }
   if (!sum_m || !sum_x || !sq_sums) { set_error("bad egcl_read_aggregates arguments"); return EGNN_EINVAL; }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t agg_x_stride = (size_t)c->cap_nodes * 4, part_x_stride = (c->cap_tiles + 1) * 2 * 4;
-  hipLaunchKernelGGL(agg_export_kernel, dim3(c->N), dim3(kThreads), 0, st, c->N, c->M, c->MP, c->last_R,
-                     c->last_nsplit_x, c->row_ptr, c->agg_m, c->part_m, c->agg_x, c->part_x, agg_x_stride,
+  hipLaunchKernelGGL(agg_export_kernel, dim3(c->N), dim3(kThreads), 0, st, c->N, c->M, c->MP, c->plan.R,
+                     c->plan.nsplit_x, c->row_ptr, c->agg_m, c->part_m, c->agg_x, c->part_x, agg_x_stride,
                      part_x_stride, sum_m, sum_x);
   EGNN_HIP(hipGetLastError());
   EGNN_HIP(hipMemcpyAsync(sq_sums, c->gscale, sizeof(float) * (norm_scope == EGNN_NORM_GRAPH ? c->B : 1),

@@ -47,14 +47,13 @@ inline int dev_alloc(T** p, size_t count) {
   return EGNN_OK;
 }
 
-// edge path of a layer's forward pass, chosen by launch_layer_begin (egnn_forward.hip: plan_edge) and read by launch_layer_end
-enum class EdgePath {
-  kGeneric,   // the 64-edge-tile kernel edge_kernel<PREC> (fp32, and every shape / switch the tiled kernels do not take)
-  kBf16,      // precision bf16: edge_x_m16.hip or edge_bf16_v3.hip + edge_bf16_v4.hip (fp16 table), or edge_small.hip
-  kBf16x3,    // precision bf16x3: edge_bf16x3.hip
-  kF16,       // precision fp16: the bf16 path's kernels on fp16 operands
-  kF16c8,     // precision f16c8: edge_f16c8w.hip
+// egcl_forward_save: where a layer's edge kernels leave what the backward needs
+struct SaveBuffers {
+  void *s1x, *s1m, *t2x, *t2m;
+  float* s;   // [nsplit][E] column-split shares of s_e
 };
+
+struct CachedSupport { bool known = false; KernelSupport sup; };   // egnn_ctx::support
 
 constexpr int kGraphSteps = 8;   // reverse steps captured per hipGraph
 struct Sampler {
@@ -98,9 +97,12 @@ struct egnn_ctx {
   float* part_x = nullptr;   // [tiles][2][4]
   float* node_d2 = nullptr;  // [N]
   float* gscale = nullptr;   // [B] sum of d^2 per graph (G^2); node_post applies 1/(G+1)
-  int last_R = 64, last_nsplit_x = 1;
-  egnn::EdgePath last_path = egnn::EdgePath::kGeneric;   // edge path chosen by the last launch_layer_begin
-  bool sq_from_agg = false;             // node_post takes the d^2 sums from the coordinate sums' component 3
+  egnn::ForwardPlan plan;               // how the last launch_layer_begin ran (host_logic.h: plan_forward); launch_layer_end reads it
+  int ncu = 256;                        // compute units of the device (egnn_create)
+  // answers of the kernels' *_supported predicates per (layer, precision): they depend on the model, the packed streams and N
+  // only, so they are asked once and forgotten by egnn_set_model / egnn_pack_layer / egnn_set_graph (forget_support)
+  std::vector<egnn::CachedSupport> support;
+  void forget_support() { support.clear(); }
   bool small_ok = false;                // the partial slots were sized for 32-edge tiles (E <= 65536): edge_small.hip may run
   // A layer's hidden-split node_post leaves its 8 partial h' in h_partial; inside a multi-layer call the NEXT layer's node_pre
   // adds them up (and writes h') instead of a launch of its own (small graphs: every launch is a serial link of the step)
@@ -108,9 +110,6 @@ struct egnn_ctx {
   float* h_partial = nullptr;  // [8][N][H] partial node-MLP outputs (hidden-split node_post at small N)
   float* bwd_s = nullptr;    // [nsplit][chunk edges] column-split shares of s_e (backward recompute)
   size_t cap_bwd_s = 0;
-  // egcl_forward_save: where the running layer's edge kernels leave what the backward needs (null = plain forward)
-  void *save_s1x = nullptr, *save_s1m = nullptr, *save_t2x = nullptr, *save_t2m = nullptr;
-  float* save_s = nullptr;   // [nsplit][E] column-split shares of s_e
   unsigned long long* stamps = nullptr;  // [2 kernels][8 waves][32 chunks][4] diagnostic time stamps
   float* h_tmp[2] = {nullptr, nullptr};  // [N][H] ping-pong between layers
   float* x_tmp[2] = {nullptr, nullptr};  // [N][3]
@@ -126,8 +125,11 @@ struct egnn_ctx {
 
 namespace egnn {
 int reserve(egnn_ctx* c);
-int launch_layer(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_scope, const float* h,
-                 const float* x, float* h_out, float* x_out, bool need_gscale = false, bool defer_finish = false);
+// save: a training forward's buffers, null = plain forward
+int launch_layer(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_scope, const float* h, const float* x, float* h_out,
+                 float* x_out, bool need_gscale = false, bool defer_finish = false, const SaveBuffers* save = nullptr);
+// all L layers from (h, x) to (h_out, x_out), ping-ponging through c->h_tmp / c->x_tmp
+int launch_stack(egnn_ctx* c, hipStream_t st, int prec, int norm_scope, const float* h, const float* x, float* h_out, float* x_out);
 void free_layer(LayerPack& lp);   // pack.hip
 // backward recompute on the forward's bf16 edge kernels (egcl_backward_edge_recompute)
 int backward_recompute_supported(egnn_ctx* c);

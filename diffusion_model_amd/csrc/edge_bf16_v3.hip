@@ -27,6 +27,7 @@ namespace {
 
 constexpr int kT3 = 512;
 constexpr int kR3 = 128, kRB3 = 4, kRPAD3 = kR3 + 1;
+static_assert(kR3 == kTileRows, "plan_forward (host_logic.cpp) plans 128-edge tiles");
 constexpr int kKC3 = 64;
 constexpr size_t kA1_3 = (size_t)8 * kRPAD3 * 16;  // one activation chunk [8 k-groups][129][8 bf16]
 using namespace tile128;
@@ -406,9 +407,11 @@ bool edge_bf16_v3_supported(const EdgeParams& p) {
 // forward coordinate kernel for hidden width 256 (one 256-column workgroup per tile); wider coordinate MLPs run on
 // edge_x_m16.hip (v_mfma_f32_16x16x32_bf16: 5-6 % faster by wall at the same workgroup tile, profiles/r03c_ab_xm16.log --
 // the 512-column forward / training-forward instantiations of this 32x32x16 kernel were retired for it)
-int launch_edge_bf16_v3_x(const EdgeParams& p, hipStream_t st) {
+// save: the training forward (p.s1_out / p.g_a2_out / p.s_half_out receive what the backward needs)
+int launch_edge_v3_x(const EdgeParams& p, hipStream_t st, bool save) {
   const int tiles = (p.E + kR3 - 1) / kR3;
-  if (p.WxP != 256) { set_error("edge_bf16_v3: forward kernel kept for WxP = 256 only"); return EGNN_EINVAL; }
+  if (p.WxP != 256) { set_error("edge_bf16_v3: forward kernels kept for WxP = 256 only"); return EGNN_EINVAL; }
+  if (save) return launch_v3<1, false, false, true>(p, tiles, v3_smem_bytes(p.WxP, p.MP, false), st);
   return launch_v3<1, false>(p, tiles, v3_smem_bytes(p.WxP, p.MP, false, false), st);   // (the plain forward stages nothing)
 }
 
@@ -418,13 +421,6 @@ int launch_edge_bf16_v3_x_bwd(const EdgeParams& p, hipStream_t st) {
   const int tiles = (p.E + kR3 - 1) / kR3;
   if (p.WxP >= 512) return launch_v3<2, false, true>(p, tiles * (p.WxP / 512), v3_smem_bytes(p.WxP, p.MP, false), st);
   return launch_v3<1, false, true>(p, tiles, v3_smem_bytes(p.WxP, p.MP, false), st);
-}
-
-// training forward of the coordinate branch for WxP = 256 (wider: edge_x_m16.hip)
-int launch_edge_bf16_v3_x_save(const EdgeParams& p, hipStream_t st) {
-  const int tiles = (p.E + kR3 - 1) / kR3;
-  if (p.WxP != 256) { set_error("edge_bf16_v3: training-forward kernel kept for WxP = 256 only"); return EGNN_EINVAL; }
-  return launch_v3<1, false, false, true>(p, tiles, v3_smem_bytes(p.WxP, p.MP, false), st);
 }
 
 }  // namespace egnn

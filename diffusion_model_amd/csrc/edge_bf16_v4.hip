@@ -402,7 +402,7 @@ int init_edge_bf16_v4_attributes() {
   return EGNN_OK;
 }
 
-int edge_v4_rows() { return kR3; }
+static_assert(kR3 == kTileRows, "plan_forward (host_logic.cpp) plans 128-edge tiles");
 
 bool edge_bf16_v4_supported(const EdgeParams& p) {
   return (p.WxP == 256 || p.WxP == 512 || p.WxP == 1024) && p.MP == 256 && p.WmP % 64 == 0 && p.WmP >= 192 && p.w2m &&   // >= 3 chunks: the K loop has a steady-state iteration (segment modes are stored there)
@@ -417,22 +417,15 @@ int launch_edge_bf16_v4_m_bwd(const EdgeParams& p, hipStream_t st) {
   return launch_v4<1, true, true>(p, tiles, v4_smem_bytes(p.WmP, p.MP, true), st);
 }
 
-// training forward of the message branch: p.s1_out / p.g_a2_out receive the activations and the scaled pre-activations
-int launch_edge_bf16_v4_m_save(const EdgeParams& p, hipStream_t st) {
+// message kernel only; f16: p.w2m = the fp16 fragment stream (scaled by -2^8 / log2(e)); save (bf16 only): the training forward,
+// p.s1_out / p.g_a2_out receive the activations and the scaled pre-activations
+int launch_edge_v4_m(const EdgeParams& p, hipStream_t st, bool f16, bool save) {
   const int tiles = (p.E + kR3 - 1) / kR3;
-  return launch_v4<1, true, false, true>(p, tiles, v4_smem_bytes(p.WmP, p.MP, true), st);
-}
-
-// message kernel, precision fp16: p.w2m = the fp16 fragment stream (scaled by -2^8 / log2(e))
-int launch_edge_f16_v4_m(const EdgeParams& p, hipStream_t st) {
-  const int tiles = (p.E + kR3 - 1) / kR3;
-  return launch_v4<1, true, false, false, f16x8>(p, tiles, v4_smem_bytes(p.WmP, p.MP, true), st);
-}
-
-// message kernel only
-int launch_edge_bf16_v4_m(const EdgeParams& p, hipStream_t st) {
-  const int tiles = (p.E + kR3 - 1) / kR3;
-  return launch_v4<1, true>(p, tiles, v4_smem_bytes(p.WmP, p.MP, true), st);
+  const size_t sm = v4_smem_bytes(p.WmP, p.MP, true);
+  if (save && f16) { set_error("edge_bf16_v4: the training forward runs on bf16 operands"); return EGNN_EINVAL; }
+  if (save) return launch_v4<1, true, false, true>(p, tiles, sm, st);
+  if (f16) return launch_v4<1, true, false, false, f16x8>(p, tiles, sm, st);
+  return launch_v4<1, true>(p, tiles, sm, st);
 }
 
 }  // namespace egnn

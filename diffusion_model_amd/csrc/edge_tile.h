@@ -9,6 +9,7 @@ namespace egnn {
 namespace tile128 {
 
 constexpr int kR = 128;         // edges per tile
+static_assert(kR == kTileRows, "plan_forward (host_logic.cpp) plans 128-edge tiles");
 constexpr int kSegFast = 8;     // segments (receiving nodes) per tile handled by the register path
 // LDS carve (bytes) of the per-tile arrays; the kernel's own K-loop buffers start at kOffLoop
 constexpr size_t kOffDst = 0;                                  // int[R]

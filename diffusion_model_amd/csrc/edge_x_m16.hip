@@ -438,55 +438,33 @@ int init_edge_x_m16_attributes() {
   return EGNN_OK;
 }
 
-// grid of the persistent form: one workgroup per CU when there are more than two units per CU, else 0 (EGNN_X_PERSIST=0: A/B switch,
-// read per launch so that a test can compare the two forms bit for bit in one process)
-static int persistent_grid(int units) {
-  const char* e = getenv("EGNN_X_PERSIST");
-  static int ncu = 0;
-  if (e && atoi(e) == 0) return 0;
-  if (ncu == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    ncu = n;
-  }
-  return units > 2 * ncu ? ncu : 0;
-}
-
 bool edge_x_m16_supported(const EdgeParams& p) {
   return (p.WxP == 512 || p.WxP == 1024) && p.w2x16 != nullptr && x16_smem_bytes(p.WxP) <= 160 * 1024 &&
          (size_t)p.N * p.TC * 2 < ((size_t)1 << 32);
 }
 
-// coordinate kernel only; p.w2x16 = mlp_x.2 packed by pack_frags_bf16_n16 (scaled by -1/log2(e))
-int launch_edge_x_m16(const EdgeParams& p, hipStream_t st) {
-  const int tiles = (p.E + kR - 1) / kR;
+// coordinate kernel only; p.w2x16 = mlp_x.2 as 16-column fragments of the operand type: bf16 (pack_frags_bf16_n16, scaled by
+// -1/log2(e)) or fp16 (pack_frags_n16<_Float16>, scaled by -2^8 / log2(e)).  kSave: the training forward, p.s1_out / p.g_a2_out /
+// p.s_half_out receive what the backward needs (see the kernel's SAVE mode; instantiated for bf16 only)
+int launch_edge_x_m16(const EdgeParams& p, hipStream_t st, bool f16, XForm form, int grid) {
+  const int units = (p.E + kR - 1) / kR * (p.WxP / 512);
+  const size_t sm = x16_smem_bytes(p.WxP);
   EdgeParams q = p;
   q.w2x = p.w2x16;
-  const int units = tiles * (p.WxP / 512), pg = persistent_grid(units);
-  if (pg > 0) hipLaunchKernelGGL((edge_x_m16_kernel<false, bf16x8, true>), dim3(pg), dim3(kT), x16_smem_bytes(p.WxP), st, q);
-  else hipLaunchKernelGGL(edge_x_m16_kernel<false>, dim3(units), dim3(kT), x16_smem_bytes(p.WxP), st, q);
-  EGNN_HIP(hipGetLastError());
-  return EGNN_OK;
-}
-
-// precision fp16: p.w2x16 = the fp16 fragment stream (pack_frags_n16<_Float16>, scaled by -2^8 / log2(e))
-int launch_edge_x_m16_f16(const EdgeParams& p, hipStream_t st) {
-  const int tiles = (p.E + kR - 1) / kR;
-  EdgeParams q = p;
-  q.w2x = p.w2x16;
-  const int units = tiles * (p.WxP / 512), pg = persistent_grid(units);
-  if (pg > 0) hipLaunchKernelGGL((edge_x_m16_kernel<false, f16x8, true>), dim3(pg), dim3(kT), x16_smem_bytes(p.WxP), st, q);
-  else hipLaunchKernelGGL((edge_x_m16_kernel<false, f16x8>), dim3(units), dim3(kT), x16_smem_bytes(p.WxP), st, q);
-  EGNN_HIP(hipGetLastError());
-  return EGNN_OK;
-}
-
-// training forward: p.s1_out / p.g_a2_out / p.s_half_out receive what the backward needs (see the kernel's SAVE mode)
-int launch_edge_x_m16_save(const EdgeParams& p, hipStream_t st) {
-  const int tiles = (p.E + kR - 1) / kR;
-  EdgeParams q = p;
-  q.w2x = p.w2x16;
-  hipLaunchKernelGGL(edge_x_m16_kernel<true>, dim3(tiles * (p.WxP / 512)), dim3(kT), x16_smem_bytes(p.WxP), st, q);
+  switch (form) {
+    case XForm::kSave:
+      if (f16) { set_error("edge_x_m16: the training forward runs on bf16 operands"); return EGNN_EINVAL; }
+      hipLaunchKernelGGL(edge_x_m16_kernel<true>, dim3(units), dim3(kT), sm, st, q);
+      break;
+    case XForm::kPersistent:
+      if (f16) hipLaunchKernelGGL((edge_x_m16_kernel<false, f16x8, true>), dim3(grid), dim3(kT), sm, st, q);
+      else hipLaunchKernelGGL((edge_x_m16_kernel<false, bf16x8, true>), dim3(grid), dim3(kT), sm, st, q);
+      break;
+    case XForm::kPerUnit:
+      if (f16) hipLaunchKernelGGL((edge_x_m16_kernel<false, f16x8>), dim3(units), dim3(kT), sm, st, q);
+      else hipLaunchKernelGGL(edge_x_m16_kernel<false>, dim3(units), dim3(kT), sm, st, q);
+      break;
+  }
   EGNN_HIP(hipGetLastError());
   return EGNN_OK;
 }

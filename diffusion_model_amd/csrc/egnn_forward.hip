@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kThreads) void node_pre_mfma_kernel(const float* __
 
 // workgroup = 32 nodes x (4 waves x NBW column blocks): NBW = 8 (1024 columns) to amortise the h tile at large N,
 // NBW = 2 (256 columns) when the whole launch is a handful of workgroups and their serial length is the layer's latency
-constexpr int kPre3Nodes = 32;
+constexpr int kPre3Nodes = kHiloNodes;   // (host_logic.h: node_pre_form counts the workgroups)
 // fin_hs > 0: h is not there yet -- the previous layer's hidden-split node_post left fin_hs partial sums in fin_partial
 // [fin_hs][N][H]; this kernel adds them up in split order (+ the bias fin_b2h: what node_post_finish_kernel does) and the
 // workgroups of column block 0 write h' to h_write (the next node_post and the caller read it there).
@@ -759,11 +759,9 @@ __global__ __launch_bounds__(kThreads, 1) void node_post_kernel(const PostParams
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-constexpr int kEdgeRows = 64;   // edges per tile of the generic kernel (edge_kernel<PREC, 2>)
-
 int reserve(egnn_ctx* c) {
   if (c->L == 0 || c->N == 0) { set_error("model and graph must be set first"); return EGNN_ESTATE; }
-  const int R = kEdgeRows;
+  const int R = kGenericRows;   // edges per tile of the generic kernel (edge_kernel<PREC, 2>)
   // partial slots per tile: 64-row tiles are the smallest, except for small graphs, which may run on 32-row tiles
   c->small_ok = c->E <= (1 << 16);
   const size_t tiles = c->small_ok ? (size_t)(c->E + 31) / 32 : (size_t)(c->E + R - 1) / R;
@@ -829,7 +827,7 @@ static void prof_end(egnn_ctx* c, hipStream_t st) {
 // CU), the message kernel goes to the side stream and runs in that shadow: one 64-atom graph 64 of 256 CUs busy, five graphs
 // (generate()'s default gen_num_per_spectrum) 316 coordinate workgroups = 1.23 rounds -> 0.49 -> 0.42 ms per reverse step.
 // Full rounds (16 graphs and more: measured equal eager, 2-8 % slower in graph replay) keep the single stream.
-// (the decision itself: fork_candidate() in host_logic.cpp)
+// (the decision itself: plan_forward() in host_logic.cpp)
 
 int fork_streams(egnn_ctx* c) {   // fork / join events for a context whose caller provided a side stream
   if (!c->side || c->ev_fork) return EGNN_OK;
@@ -872,18 +870,22 @@ static int launch_edge(const EdgeParams& p, int tiles, size_t smem, hipStream_t 
   return EGNN_OK;
 }
 
-// 32-edge tiles (edge_small.hip) for graphs of up to ~2 k edges (a 20-40-atom molecule, the toy graphs of configs[0]): measured
-// (profiles/r04e_latency_small_tiles.log, hipGraph replay, ms per reverse step) 20-atom cell 0.289 -> 0.277, 4 x 2-atom graphs
-// 0.258 -> 0.223; but one 64-atom cell (4,032 edges) 0.313 -> 0.343 and five 0.41 -> 0.70: a layer's weight traffic through L2
-// is (E / tile rows) x 2.5 MB whatever the column split, 315 MB at 32 rows for ONE 64-atom graph, and the chip's L2 delivers
-// ~7 TB/s to 256 streaming CUs, not the 34 TB/s of 64 B/clk/CU -- 128-row tiles are within 3x of that floor already.
-// EGNN_SMALL_EDGES overrides the edge-count limit (0 = never): measurement switch.
-// -> edges per tile (32 / 64) or 0 = the 128-edge-tile kernels.  EGNN_SMALL64_EDGES: limit of the 64-row form (one 64-atom graph).
-static int small_tiles(const egnn_ctx* c, const EdgeParams& p) {
-  static const long limit = getenv("EGNN_SMALL_EDGES") ? atol(getenv("EGNN_SMALL_EDGES")) : 2048;
-  static const long limit64 = getenv("EGNN_SMALL64_EDGES") ? atol(getenv("EGNN_SMALL64_EDGES")) : 6144;
-  if (c->E <= 0 || !c->small_ok || !edge_small_supported(p)) return 0;
-  return (long)c->E <= limit ? 32 : ((long)c->E <= limit64 ? 64 : 0);
+// The environment switches of the forward dispatch, read here and nowhere else.  EGNN_X_PERSIST is read per call (a test compares
+// the two forms of the coordinate kernel bit for bit in one process), but only for shapes that can reach the persistent form.
+static ForwardSwitches forward_switches(bool persistent_possible) {
+  static const ForwardSwitches fixed = [] {
+    ForwardSwitches s;
+    if (const char* e = getenv("EGNN_EDGE")) s.edge = atoi(e);
+    if (const char* e = getenv("EGNN_SMALL_EDGES")) s.small_edges = atol(e);
+    if (const char* e = getenv("EGNN_SMALL64_EDGES")) s.small64_edges = atol(e);
+    return s;
+  }();
+  ForwardSwitches s = fixed;
+  if (persistent_possible) {
+    const char* e = getenv("EGNN_X_PERSIST");
+    s.x_persist = !(e && atoi(e) == 0);
+  }
+  return s;
 }
 
 // EdgeParams over the graph set on the context: dimensions, graph and scratch; every parameter stream is left null
@@ -941,37 +943,49 @@ static void set_edge_streams(const LayerPack& lp, EdgePath path, int prec, EdgeP
       break;
   }
 }
-// first-layer table of the v3 / v4 kernels (fp16, pre-scaled) for node features h
-static int launch_node_pre_f16(egnn_ctx* c, hipStream_t st, int layer, const float* h, const float* w1catT,
-                               const float* b1cat) {
+// first-layer table for node features h: fp16 (pre-scaled; the half-precision paths) or exact fp32, in the form the plan names
+static int launch_node_pre(egnn_ctx* c, hipStream_t st, int layer, NodePre form, bool half_table, const float* h, const float* w1catT,
+                           const float* b1cat) {
   const int N = c->N;
-  if (c->H <= 48) {   // bf16 hi/lo MFMA (2^-16), else exact f32 MFMA, else the VALU kernel
-    const int ntile = (N + kPre3Nodes - 1) / kPre3Nodes;
-    const size_t sm = (size_t)48 * 33 * 4 + (size_t)4 * 32 * (128 + 8) * 2;
-    const bf16x8* w1hl = reinterpret_cast<const bf16x8*>(c->layers[layer].w1hl_bf16);
-    _Float16* tab = reinterpret_cast<_Float16*>(c->table);
-    // a pending hidden-split finish of the previous layer (c->pend) rides in this launch
-    const bool fin = c->pend.active && c->pend.h_out == h;
-    const int fhs = fin ? c->pend.hs : 0;
-    const float* fb = fin ? c->pend.b2h : nullptr;
-    float* fw = fin ? c->pend.h_out : nullptr;
-    if (fin) c->pend.active = false;
-    if (ntile * (c->TC / 1024) >= 256)
-      hipLaunchKernelGGL(node_pre_hilo_kernel<8>, dim3(ntile, (c->TC + 1023) / 1024), dim3(kThreads), sm, st, h, N, c->H, w1hl,
-                         b1cat, c->TC, tab, fhs, c->h_partial, fb, fw);
-    else
-      hipLaunchKernelGGL(node_pre_hilo_kernel<2>, dim3(ntile, (c->TC + 255) / 256), dim3(kThreads), sm, st, h, N, c->H, w1hl,
-                         b1cat, c->TC, tab, fhs, c->h_partial, fb, fw);
-  } else if (c->H <= 64) {
-    dim3 grid((N + kPre2Nodes - 1) / kPre2Nodes, (c->TC + kPre2Cols - 1) / kPre2Cols);
-    const size_t sm = (size_t)((c->H + 1) & ~1) * 33 * sizeof(float);
-    const size_t sm16 = (size_t)kPre2Nodes * (kPre2Cols + 8) * 2;   // output staging tile of the fp16 variant
-    hipLaunchKernelGGL(node_pre_mfma_kernel<_Float16>, grid, dim3(kThreads), sm > sm16 ? sm : sm16, st, h, N, c->H,
-                       w1catT, b1cat, c->TC, reinterpret_cast<_Float16*>(c->table));
-  } else {
-    dim3 grid((N + kPreNodes - 1) / kPreNodes, (c->TC + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL(node_pre_kernel<_Float16>, grid, dim3(kThreads), (size_t)kPreNodes * c->H * sizeof(float), st, h, N,
-                       c->H, w1catT, b1cat, c->TC, reinterpret_cast<_Float16*>(c->table));
+  _Float16* tab16 = reinterpret_cast<_Float16*>(c->table);
+  switch (form) {
+    case NodePre::kHilo8:
+    case NodePre::kHilo2: {   // bf16 hi/lo MFMA (2^-16), half-precision table and H <= 48 only
+      const int ntile = (N + kPre3Nodes - 1) / kPre3Nodes;
+      const size_t sm = (size_t)48 * 33 * 4 + (size_t)4 * 32 * (128 + 8) * 2;
+      const bf16x8* w1hl = reinterpret_cast<const bf16x8*>(c->layers[layer].w1hl_bf16);
+      // a pending hidden-split finish of the previous layer (c->pend) rides in this launch
+      const bool fin = c->pend.active && c->pend.h_out == h;
+      const int fhs = fin ? c->pend.hs : 0;
+      const float* fb = fin ? c->pend.b2h : nullptr;
+      float* fw = fin ? c->pend.h_out : nullptr;
+      if (fin) c->pend.active = false;
+      if (form == NodePre::kHilo8)
+        hipLaunchKernelGGL(node_pre_hilo_kernel<8>, dim3(ntile, (c->TC + 1023) / 1024), dim3(kThreads), sm, st, h, N, c->H, w1hl,
+                           b1cat, c->TC, tab16, fhs, c->h_partial, fb, fw);
+      else
+        hipLaunchKernelGGL(node_pre_hilo_kernel<2>, dim3(ntile, (c->TC + 255) / 256), dim3(kThreads), sm, st, h, N, c->H, w1hl,
+                           b1cat, c->TC, tab16, fhs, c->h_partial, fb, fw);
+      break;
+    }
+    case NodePre::kMfma: {   // exact f32 MFMA, H <= 64
+      dim3 grid((N + kPre2Nodes - 1) / kPre2Nodes, (c->TC + kPre2Cols - 1) / kPre2Cols);
+      const size_t sm = (size_t)((c->H + 1) & ~1) * 33 * sizeof(float);
+      const size_t sm16 = (size_t)kPre2Nodes * (kPre2Cols + 8) * 2;   // output staging tile of the fp16 variant
+      if (half_table)
+        hipLaunchKernelGGL(node_pre_mfma_kernel<_Float16>, grid, dim3(kThreads), sm > sm16 ? sm : sm16, st, h, N, c->H, w1catT, b1cat,
+                           c->TC, tab16);
+      else
+        hipLaunchKernelGGL(node_pre_mfma_kernel<float>, grid, dim3(kThreads), sm, st, h, N, c->H, w1catT, b1cat, c->TC, c->table);
+      break;
+    }
+    case NodePre::kValu: {
+      dim3 grid((N + kPreNodes - 1) / kPreNodes, (c->TC + kThreads - 1) / kThreads);
+      const size_t sm = (size_t)kPreNodes * c->H * sizeof(float);
+      if (half_table) hipLaunchKernelGGL(node_pre_kernel<_Float16>, grid, dim3(kThreads), sm, st, h, N, c->H, w1catT, b1cat, c->TC, tab16);
+      else hipLaunchKernelGGL(node_pre_kernel<float>, grid, dim3(kThreads), sm, st, h, N, c->H, w1catT, b1cat, c->TC, c->table);
+      break;
+    }
   }
   EGNN_HIP(hipGetLastError());
   return EGNN_OK;
@@ -987,7 +1001,7 @@ int backward_recompute_supported(egnn_ctx* c) {
 }
 int backward_table(egnn_ctx* c, hipStream_t st, int layer, const float* h) {
   const LayerPack& lp = c->layers[layer];
-  return launch_node_pre_f16(c, st, layer, h, lp.w1catT_s, lp.b1cat_s);
+  return launch_node_pre(c, st, layer, node_pre_form(true, c->N, c->H, c->TC), true, h, lp.w1catT_s, lp.b1cat_s);
 }
 int backward_recompute(egnn_ctx* c, hipStream_t st, int layer, const float* x, const float* g_sum_x, const float* g_sum_m,
                        int e_first, int n_edges, void* s1x, void* s1m, void* g_a2x, void* g_a2m, float* s_halves,
@@ -1043,50 +1057,19 @@ int backward_dgrad_graph(egnn_ctx* c, hipStream_t st, int layer, const float* x,
                                  gd2_part + (size_t)(c->WxP / 256) * n_edges, st);
 }
 
-// Edge path of a layer and its EdgeParams (streams: set_edge_streams).  The candidate of a precision:
-//   bf16    edge_x_m16.hip (hidden width 512 / 1024) or edge_bf16_v3.hip (256) + edge_bf16_v4.hip, fp16 table
-//   bf16x3  edge_bf16x3.hip (head / remainder operands, fp32 table)
-//   fp16    the bf16 path's kernels on fp16 operands (hidden width 512 / 1024)
-//   f16c8   edge_f16c8w.hip (fp16 heads + e4m3 corrections, fp32 table)
-// Its kernels are asked on the very EdgeParams they would be launched with.  A precision whose tiled kernels do not take the
-// shape runs the generic kernel: bf16 as bf16, the others as the exact fp32 path (prec is set to EGNN_PREC_F32).  EGNN_EDGE=1
-// forces the generic kernel (the one switch kept: the fallback kernels' own parity test runs the reference widths on them).
-static EdgePath plan_edge(egnn_ctx* c, int layer, int& prec, const float* x, EdgeParams& p, const float*& w1catT,
-                          const float*& b1cat) {
-  static const int edge_sel = getenv("EGNN_EDGE") ? atoi(getenv("EGNN_EDGE")) : 4;
-  const LayerPack& lp = c->layers[layer];
-  fill_edge_params(c, x, p);
-  const EdgePath want = prec == EGNN_PREC_BF16 ? EdgePath::kBf16 : prec == EGNN_PREC_BF16X3 ? EdgePath::kBf16x3
-                      : prec == EGNN_PREC_F16 ? EdgePath::kF16 : prec == EGNN_PREC_F16C8 ? EdgePath::kF16c8 : EdgePath::kGeneric;
-  if (edge_sel >= 4 && want != EdgePath::kGeneric) {
-    set_edge_streams(lp, want, prec, p, w1catT, b1cat);
-    bool ok = false;
-    switch (want) {
-      case EdgePath::kBf16: ok = edge_bf16_v4_supported(p) && edge_bf16_v3_supported(p); break;
-      case EdgePath::kBf16x3: ok = edge_bf16x3_supported(p); break;
-      case EdgePath::kF16: ok = !c->save_s1x && edge_bf16_v4_supported(p) && edge_x_m16_supported(p); break;
-      case EdgePath::kF16c8: ok = !c->save_s1x && edge_f16c8w_supported(p); break;
-      default: break;
-    }
-    if (ok) return want;
-  }
-  if (prec != EGNN_PREC_BF16) prec = EGNN_PREC_F32;
-  set_edge_streams(lp, EdgePath::kGeneric, prec, p, w1catT, b1cat);
-  return EdgePath::kGeneric;
-}
-
-// fp32 first-layer table (exact: the generic path, and the fp32 table of bf16x3 / f16c8)
-static void launch_node_pre_f32(egnn_ctx* c, hipStream_t st, const float* h, const float* w1catT, const float* b1cat) {
-  const int N = c->N;
-  if (c->H <= 64) {
-    dim3 grid((N + kPre2Nodes - 1) / kPre2Nodes, (c->TC + kPre2Cols - 1) / kPre2Cols);
-    const size_t sm = (size_t)((c->H + 1) & ~1) * 33 * sizeof(float);
-    hipLaunchKernelGGL(node_pre_mfma_kernel<float>, grid, dim3(kThreads), sm, st, h, N, c->H, w1catT, b1cat, c->TC, c->table);
-  } else {
-    dim3 grid((N + kPreNodes - 1) / kPreNodes, (c->TC + kThreads - 1) / kThreads);
-    const size_t sm = (size_t)kPreNodes * c->H * sizeof(float);
-    hipLaunchKernelGGL(node_pre_kernel<float>, grid, dim3(kThreads), sm, st, h, N, c->H, w1catT, b1cat, c->TC, c->table);
-  }
+// node_post arguments that depend on the model and the context only (the node MLP's streams: split = the head / remainder fp16
+// streams of the split-operand form); launch_layer_end adds the call's tensors and what the plan says
+static PostParams post_params(const egnn_ctx* c, const LayerPack& lp, bool split) {
+  PostParams q{};
+  q.N = c->N; q.H = c->H; q.MP = c->MP; q.K1P = c->K1P; q.WhP = c->WhP; q.HP = c->HP; q.K1Q = c->K1Q;
+  q.row_ptr = c->row_ptr; q.node_graph = c->node_graph; q.graph_ptr = c->graph_ptr;
+  q.agg_m = c->agg_m; q.agg_x = c->agg_x; q.part_m = c->part_m; q.part_x = c->part_x; q.gscale = c->gscale;
+  q.agg_x_stride = (size_t)c->cap_nodes * 4; q.part_x_stride = (c->cap_tiles + 1) * 2 * 4;
+  q.w1h = reinterpret_cast<const f32x4*>(lp.w1h_f32); q.w2h = reinterpret_cast<const f32x4*>(lp.w2h_f32);
+  q.b1h = lp.b1h; q.b2h = lp.b2h; q.h_partial = c->h_partial;
+  q.w1h_bf16 = split ? lp.w1h_f16k : lp.w1h_bf16; q.w2h_bf16p = split ? lp.w2h_f16p : lp.w2h_bf16p;
+  if (split) { q.w1h_lo = lp.w1h_f16k_lo; q.w2h_lo = lp.w2h_f16p_lo; }
+  return q;
 }
 
 // A layer's coordinate and message kernel: with `fork`, the message kernel goes to the caller's side stream between two events
@@ -1107,36 +1090,60 @@ static int launch_edge_pair(egnn_ctx* c, hipStream_t st, bool fork, LaunchX laun
   return rc;
 }
 
+static int launch_graph_sq_sums(egnn_ctx* c, hipStream_t st, int R, int per_graph) {
+  hipLaunchKernelGGL(graph_sq_sums_kernel, dim3(per_graph ? c->B : 1), dim3(kThreads), 0, st, c->row_ptr, R, c->agg_x, c->part_x,
+                     c->graph_ptr, c->N, per_graph, c->gscale);
+  EGNN_HIP(hipGetLastError());
+  return EGNN_OK;
+}
+
 // Stage 1 of a layer: node_pre, squared-distance sums and the fused edge pass.  gsum (c->gscale) then holds the
-// sum of d^2 over the edges THIS context received, per graph (or per call).
-int launch_layer_begin(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_scope, const float* h,
-                       const float* x, bool need_gscale) {
+// sum of d^2 over the edges THIS context received, per graph (or per call).  Every decision is plan_forward's
+// (host_logic.cpp); the plan stays in c->plan for launch_layer_end and egcl_read_aggregates.
+int launch_layer_begin(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_scope, const float* h, const float* x,
+                       bool need_gscale, const SaveBuffers* save = nullptr) {
   const LayerPack& lp = c->layers[layer];
   if (!lp.packed) { set_error("layer %d has no packed parameters", layer); return EGNN_ESTATE; }
-  const int N = c->N, E = c->E;
-  const int per_graph = norm_scope == EGNN_NORM_GRAPH;
+  const int N = c->N, per_graph = norm_scope == EGNN_NORM_GRAPH;
+
+  // the params the precision's own path would be launched with, and its kernels' answers on them (asked once per layer and
+  // precision, until the model, the pack or the graph changes)
   EdgeParams p;
   const float *w1catT, *b1cat;
-  const EdgePath path = plan_edge(c, layer, prec, x, p, w1catT, b1cat);
-  if (c->save_s1x && path != EdgePath::kBf16) { set_error("egcl_forward_save needs the 128-edge-tile bf16 kernels"); return EGNN_EINVAL; }
-  const bool tiled = path != EdgePath::kGeneric;            // the 128-edge-tile kernels sum d^2 per receiving node themselves
-  const bool half_table = path == EdgePath::kBf16 || path == EdgePath::kF16;   // fp16 table (launch_node_pre_f16)
+  fill_edge_params(c, x, p);
+  set_edge_streams(lp, path_of_precision(prec), prec, p, w1catT, b1cat);
+  ForwardAsk a;
+  a.N = N; a.E = c->E; a.B = c->B; a.H = c->H;
+  a.md = {c->WxP, c->WmP, c->MP, c->WhP, c->HP, c->K1P, c->K1Q, c->TC, c->cbx, c->cbm};
+  a.small_ok = c->small_ok; a.prec = prec; a.norm_scope = norm_scope; a.save = save != nullptr; a.need_gscale = need_gscale;
+  a.side_ok = st != nullptr && c->side != nullptr && c->ev_fork != nullptr; a.prof = c->prof; a.ncu = c->ncu;
+  a.sw = forward_switches(persistent_possible(c->E, c->WxP, c->ncu));
+  const size_t slot = (size_t)layer * 5 + prec;   // (five precisions: egnn_amd.h)
+  if (c->support.empty()) c->support.resize((size_t)c->L * 5);
+  if (!c->support[slot].known) {
+    KernelSupport& s = c->support[slot].sup;
+    s.v3 = edge_bf16_v3_supported(p); s.v4 = edge_bf16_v4_supported(p); s.x_m16 = edge_x_m16_supported(p);
+    s.small = edge_small_supported(p); s.bf16x3 = edge_bf16x3_supported(p); s.f16c8w = edge_f16c8w_supported(p);
+    s.post_split = node_post_split_supported(post_params(c, lp, true));
+    s.post_bf16 = node_post_bf16_supported(post_params(c, lp, false));
+    c->support[slot].known = true;
+  }
+  a.sup = c->support[slot].sup;
+  ForwardPlan pl;
+  int rc = plan_forward(a, &pl);
+  if (rc) return rc;
+  if (pl.path == EdgePath::kGeneric) set_edge_streams(lp, pl.path, pl.frag_bf16 ? EGNN_PREC_BF16 : EGNN_PREC_F32, p, w1catT, b1cat);
 
-  // a pending hidden-split finish (previous layer of a multi-layer call) is fused into the half-precision node_pre for H <= 48;
-  // every other case runs the finish launch now
-  if (c->pend.active && !(half_table && c->H <= 48 && c->pend.h_out == h)) {
-    int rc = launch_node_post_finish(N, c->H, c->pend.hs, c->h_partial, c->pend.b2h, c->pend.h_out, st);
+  // a pending hidden-split finish (previous layer of a multi-layer call) rides in a node_pre that can absorb it; every other
+  // case runs the finish launch now
+  if (c->pend.active && !(pl.absorbs_finish && c->pend.h_out == h)) {
+    rc = launch_node_post_finish(N, c->H, c->pend.hs, c->h_partial, c->pend.b2h, c->pend.h_out, st);
     c->pend.active = false;
     if (rc) return rc;
   }
   prof_begin(c, st, 1);
-  if (half_table) {
-    int rc = launch_node_pre_f16(c, st, layer, h, w1catT, b1cat);
-    if (rc) return rc;
-  } else {
-    launch_node_pre_f32(c, st, h, w1catT, b1cat);
-  }
-  if (!tiled) {
+  if ((rc = launch_node_pre(c, st, layer, pl.node_pre, pl.half_table, h, w1catT, b1cat))) return rc;
+  if (pl.sq == SqSource::kNodeD2) {
     hipLaunchKernelGGL(node_d2_kernel, dim3((N + 255) / 256), dim3(256), 0, st, x, c->row_ptr, c->edge_src, N, c->node_d2);
     hipLaunchKernelGGL(graph_sum_kernel, dim3(per_graph ? c->B : 1), dim3(kThreads), 0, st, c->node_d2, c->graph_ptr, N, per_graph,
                        c->gscale);
@@ -1144,132 +1151,96 @@ int launch_layer_begin(egnn_ctx* c, hipStream_t st, int layer, int prec, int nor
   prof_end(c, st);
   EGNN_HIP(hipGetLastError());
 
-  int R = kEdgeRows, nsplit_x = 1;
-  if (E > 0) {
+  if (pl.form != EdgeForm::kNone) {
     prof_begin(c, st, 0);
-    // fork_candidate(): whether the message kernel fits the shadow of the coordinate kernel's last round (small-tile kernels:
-    // always fork when the caller gave a side stream)
-    const bool can_fork = !c->prof && st != nullptr && c->side != nullptr && c->ev_fork != nullptr;
-    const bool fork = can_fork && fork_candidate(E, p.WxP);
-    const int small = half_table && !c->save_s1x ? small_tiles(c, p) : 0;
-    int rc;
-    if (path == EdgePath::kBf16x3) {
-      R = 128;
-      nsplit_x = p.WxP / 256;
-      rc = launch_edge_bf16x3(p, st);
-    } else if (path == EdgePath::kF16c8) {   // fp16 32-column streams + e4m3 correction streams
-      R = 128;
-      nsplit_x = p.WxP / 512;
-      rc = launch_edge_pair(c, st, fork, [&](hipStream_t s) { return launch_edge_f16c8w_x(p, s); },
-                            [&](hipStream_t s) { return launch_edge_f16c8w_m(p, s); });
-    } else if (small != 0) {
-      // small graphs (the reference's per-call workload): 32-edge tiles, weight-stream-bound workgroups (edge_small.hip)
-      const bool f16 = path == EdgePath::kF16;
-      R = small;
-      nsplit_x = p.WxP / 512;
-      rc = launch_edge_pair(c, st, can_fork, [&](hipStream_t s) { return launch_edge_small_x(p, s, f16, R); },
-                            [&](hipStream_t s) { return launch_edge_small_m(p, s, f16, R); });
-    } else if (path == EdgePath::kF16) {   // the bf16 path's kernels on fp16 operands (same tiles, same launch structure)
-      R = edge_v4_rows();
-      nsplit_x = p.WxP / 512;
-      rc = launch_edge_pair(c, st, fork, [&](hipStream_t s) { return launch_edge_x_m16_f16(p, s); },
-                            [&](hipStream_t s) { return launch_edge_f16_v4_m(p, s); });
-    } else if (path == EdgePath::kBf16) {
-      R = edge_v4_rows();
-      const bool xm16 = edge_x_m16_supported(p);   // hidden width 512 / 1024: v_mfma_f32_16x16x32_bf16 (512 columns per workgroup)
-      nsplit_x = xm16 ? p.WxP / 512 : 1;
-      if (c->save_s1x) {   // training forward (egcl_forward_save): the same kernels, which also store what the backward needs
-        p.s1_out = c->save_s1x; p.g_a2_out = c->save_t2x; p.s_half_out = c->save_s;
-        rc = xm16 ? launch_edge_x_m16_save(p, st) : launch_edge_bf16_v3_x_save(p, st);
-        p.s1_out = c->save_s1m; p.g_a2_out = c->save_t2m; p.s_half_out = nullptr;
-        if (!rc) rc = launch_edge_bf16_v4_m_save(p, st);
-      } else {
-        rc = launch_edge_pair(c, st, fork, [&](hipStream_t s) { return xm16 ? launch_edge_x_m16(p, s) : launch_edge_bf16_v3_x(p, s); },
-                              [&](hipStream_t s) { return launch_edge_bf16_v4_m(p, s); });
+    switch (pl.form) {
+      case EdgeForm::kNone: break;
+      case EdgeForm::kGeneric64: {
+        const int tiles = (c->E + pl.R - 1) / pl.R;
+        const size_t smem = edge_smem_bytes(pl.R, c->MP);
+        rc = pl.frag_bf16 ? launch_edge<EGNN_PREC_BF16, 2>(p, tiles, smem, st) : launch_edge<EGNN_PREC_F32, 2>(p, tiles, smem, st);
+        break;
       }
-    } else {
-      const int tiles = (E + R - 1) / R;
-      const size_t smem = edge_smem_bytes(R, c->MP);
-      rc = prec == EGNN_PREC_BF16 ? launch_edge<EGNN_PREC_BF16, 2>(p, tiles, smem, st) : launch_edge<EGNN_PREC_F32, 2>(p, tiles, smem, st);
+      case EdgeForm::kBf16x3: rc = launch_edge_bf16x3(p, st); break;
+      case EdgeForm::kF16c8:   // fp16 32-column streams + e4m3 correction streams
+        rc = launch_edge_pair(c, st, pl.fork, [&](hipStream_t s) { return launch_edge_f16c8w_x(p, s); },
+                              [&](hipStream_t s) { return launch_edge_f16c8w_m(p, s); });
+        break;
+      case EdgeForm::kSmall:   // small graphs (the reference's per-call workload): weight-stream-bound workgroups (edge_small.hip)
+        rc = launch_edge_pair(c, st, pl.fork, [&](hipStream_t s) { return launch_edge_small_x(p, s, pl.f16, pl.R); },
+                              [&](hipStream_t s) { return launch_edge_small_m(p, s, pl.f16, pl.R); });
+        break;
+      case EdgeForm::kTile128: {
+        EdgeParams pm = p;
+        if (save) {   // training forward: the same kernels, which also store what the backward needs
+          p.s1_out = save->s1x; p.g_a2_out = save->t2x; p.s_half_out = save->s;
+          pm.s1_out = save->s1m; pm.g_a2_out = save->t2m;
+        }
+        rc = launch_edge_pair(c, st, pl.fork,
+                              [&](hipStream_t s) {
+                                if (pl.coord == CoordKernel::kV3) return launch_edge_v3_x(p, s, pl.save);
+                                const XForm form = pl.save ? XForm::kSave : pl.coord == CoordKernel::kXm16Persistent ? XForm::kPersistent : XForm::kPerUnit;
+                                return launch_edge_x_m16(p, s, pl.f16, form, pl.persist_grid);
+                              },
+                              [&](hipStream_t s) { return launch_edge_v4_m(pm, s, pl.f16, pl.save); });
+        break;
+      }
     }
     prof_end(c, st);
     if (rc) return rc;
   }
 
-  c->last_R = R; c->last_nsplit_x = nsplit_x; c->last_path = path;
-  c->sq_from_agg = false;
-  if (tiled) {
-    if (E == 0) {
-      EGNN_HIP(hipMemsetAsync(c->gscale, 0, sizeof(float) * (per_graph ? c->B : 1), st));
-    } else if (!per_graph || need_gscale) {
-      hipLaunchKernelGGL(graph_sq_sums_kernel, dim3(per_graph ? c->B : 1), dim3(kThreads), 0, st, c->row_ptr, R, c->agg_x,
-                         c->part_x, c->graph_ptr, N, per_graph, c->gscale);
-      EGNN_HIP(hipGetLastError());
-    } else {
-      c->sq_from_agg = true;   // node_post adds the per-graph sums up itself: no launch
-    }
-  }
+  c->plan = pl;   // (only once the edge pass is enqueued: launch_layer_end and egcl_read_aggregates read the sums with its R / nsplit_x)
+  if (pl.sq == SqSource::kMemset) EGNN_HIP(hipMemsetAsync(c->gscale, 0, sizeof(float) * (per_graph ? c->B : 1), st));
+  else if (pl.sq == SqSource::kLaunch) return launch_graph_sq_sums(c, st, pl.R, per_graph);
   return EGNN_OK;
 }
 
-// Stage 2: node_post with the normaliser sums in c->gscale (possibly replaced by a cross-rank total).
-int launch_layer_end(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_scope, const float* h, const float* x,
-                     float* h_out, float* x_out, bool defer_finish = false) {
+// Stage 2: node_post with the normaliser sums in c->gscale (possibly replaced by a cross-rank total), as c->plan says.
+int launch_layer_end(egnn_ctx* c, hipStream_t st, int layer, int norm_scope, const float* h, const float* x, float* h_out,
+                     float* x_out, bool defer_finish = false) {
   const LayerPack& lp = c->layers[layer];
-  const int N = c->N, R = c->last_R, nsplit_x = c->last_nsplit_x;
-  const size_t agg_x_stride = (size_t)c->cap_nodes * 4, part_x_stride = (c->cap_tiles + 1) * 2 * 4;
-  const int per_graph = norm_scope == EGNN_NORM_GRAPH;
-  (void)prec;
-  {
-    PostParams q;
-    q.N = N; q.H = c->H; q.MP = c->MP; q.K1P = c->K1P; q.WhP = c->WhP; q.HP = c->HP; q.R = R;
-    q.h = h; q.x = x; q.row_ptr = c->row_ptr; q.node_graph = c->node_graph;
-    q.agg_m = c->agg_m; q.agg_x = c->agg_x; q.part_m = c->part_m; q.part_x = c->part_x;
-    q.gscale = c->gscale; q.per_graph = per_graph;
-    q.graph_ptr = c->graph_ptr; q.sq_from_agg = c->sq_from_agg ? 1 : 0;
-    q.agg_x_stride = agg_x_stride; q.part_x_stride = part_x_stride; q.nsplit_x = nsplit_x;
-    q.w1h = reinterpret_cast<const f32x4*>(lp.w1h_f32); q.w2h = reinterpret_cast<const f32x4*>(lp.w2h_f32);
-    q.b1h = lp.b1h; q.b2h = lp.b2h; q.h_out = h_out; q.x_out = x_out;
-    q.w1h_bf16 = lp.w1h_bf16; q.w2h_bf16p = lp.w2h_bf16p; q.K1Q = c->K1Q;
-    q.h_partial = c->h_partial;
-    prof_begin(c, st, 1);
-    // node MLP of precisions fp16, bf16x3 and f16c8 on their 128-edge-tile paths: split-operand fp16 products (22 significant
-    // bits, node_bf16.hip) where the shape allows, else the exact fp32 kernel
-    PostParams qs = q;
-    qs.w1h_bf16 = lp.w1h_f16k; qs.w2h_bf16p = lp.w2h_f16p; qs.w1h_lo = lp.w1h_f16k_lo; qs.w2h_lo = lp.w2h_f16p_lo;
-    const bool split_path = c->last_path == EdgePath::kF16 || c->last_path == EdgePath::kBf16x3 || c->last_path == EdgePath::kF16c8;
-    int hs_used = 1;
-    if (split_path && node_post_split_supported(qs)) {
-      int rc = launch_node_post_bf16(qs, st, true, defer_finish, &hs_used);
-      if (rc) return rc;
-    } else if (prec == EGNN_PREC_BF16 && node_post_bf16_supported(q)) {
-      int rc = launch_node_post_bf16(q, st, false, defer_finish, &hs_used);
-      if (rc) return rc;
-    } else {
-      if (q.sq_from_agg) {   // the fp32 node kernel reads gscale
-        hipLaunchKernelGGL(graph_sq_sums_kernel, dim3(per_graph ? c->B : 1), dim3(kThreads), 0, st, c->row_ptr, R, c->agg_x,
-                           c->part_x, c->graph_ptr, N, per_graph, c->gscale);
-        q.sq_from_agg = 0;
-      }
-      hipLaunchKernelGGL(node_post_kernel, dim3((N + kPostNodes - 1) / kPostNodes), dim3(kThreads),
-                         post_smem_bytes(c->K1P, c->WhP), st, q);
-    }
-    if (defer_finish && hs_used > 1) {   // the next layer's node_pre (or launch_layer_begin's flush) adds the partials up
-      c->pend.active = true; c->pend.hs = hs_used; c->pend.b2h = lp.b2h; c->pend.h_out = h_out;
-    }
-    prof_end(c, st);
-    EGNN_HIP(hipGetLastError());
+  const ForwardPlan& pl = c->plan;
+  PostParams q = post_params(c, lp, pl.node_post == NodePost::kSplit);
+  q.R = pl.R; q.nsplit_x = pl.nsplit_x; q.sq_from_agg = pl.sq == SqSource::kNodePost ? 1 : 0;
+  q.per_graph = norm_scope == EGNN_NORM_GRAPH;
+  q.h = h; q.x = x; q.h_out = h_out; q.x_out = x_out;
+  prof_begin(c, st, 1);
+  int hs_used = 1;
+  if (pl.node_post == NodePost::kF32) {
+    hipLaunchKernelGGL(node_post_kernel, dim3((c->N + kPostNodes - 1) / kPostNodes), dim3(kThreads), post_smem_bytes(c->K1P, c->WhP),
+                       st, q);
+  } else {
+    const int rc = launch_node_post_bf16(q, st, pl.node_post == NodePost::kSplit, defer_finish, &hs_used);
+    if (rc) return rc;
   }
+  if (defer_finish && hs_used > 1) {   // the next layer's node_pre (or launch_layer_begin's flush) adds the partials up
+    c->pend.active = true; c->pend.hs = hs_used; c->pend.b2h = lp.b2h; c->pend.h_out = h_out;
+  }
+  prof_end(c, st);
+  EGNN_HIP(hipGetLastError());
   return EGNN_OK;
 }
 
-// defer_finish: only from a loop that launches the NEXT layer on h_out right away (egnn_forward, the sampler's step)
-int launch_layer(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_scope, const float* h,
-                 const float* x, float* h_out, float* x_out, bool need_gscale, bool defer_finish) {
+// defer_finish: only from a loop that launches the NEXT layer on h_out right away (launch_stack)
+int launch_layer(egnn_ctx* c, hipStream_t st, int layer, int prec, int norm_scope, const float* h, const float* x, float* h_out,
+                 float* x_out, bool need_gscale, bool defer_finish, const SaveBuffers* save) {
   if (layer == 0) c->pend.active = false;   // (a call that failed half-way leaves nothing behind)
-  int rc = launch_layer_begin(c, st, layer, prec, norm_scope, h, x, need_gscale);
+  int rc = launch_layer_begin(c, st, layer, prec, norm_scope, h, x, need_gscale, save);
   if (rc) return rc;
-  return launch_layer_end(c, st, layer, prec, norm_scope, h, x, h_out, x_out, defer_finish);
+  return launch_layer_end(c, st, layer, norm_scope, h, x, h_out, x_out, defer_finish);
+}
+
+int launch_stack(egnn_ctx* c, hipStream_t st, int prec, int norm_scope, const float* h, const float* x, float* h_out, float* x_out) {
+  for (int l = 0; l < c->L; ++l) {
+    const bool last = l == c->L - 1;
+    float* ho = last ? h_out : c->h_tmp[l & 1];
+    float* xo = last ? x_out : c->x_tmp[l & 1];
+    const int rc = launch_layer(c, st, l, prec, norm_scope, h, x, ho, xo, false, !last);
+    if (rc) return rc;
+    h = ho; x = xo;
+  }
+  return EGNN_OK;
 }
 
 }  // namespace egnn
@@ -1295,6 +1266,8 @@ int egnn_create(egnn_ctx** out, int device) {
   }
   egnn_ctx* c = new egnn_ctx();
   c->device = device;
+  int ncu = 0;   // the persistent coordinate kernel runs one workgroup per CU (plan_forward)
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->ncu = ncu;
   *out = c;
   return EGNN_OK;
 }
@@ -1343,6 +1316,7 @@ int egnn_set_graph(egnn_ctx* c, int N, int E, int B, const int32_t* edge_dst, co
   c->N = N; c->E = E; c->B = B;
   c->edge_dst = edge_dst; c->edge_src = edge_src; c->row_ptr = row_ptr; c->graph_ptr = graph_ptr;
   c->node_graph = node_graph;
+  c->forget_support();
   c->smp.ready = false;
   return reserve(c);
 }
@@ -1377,10 +1351,8 @@ int egcl_forward_save(egnn_ctx* c, void* stream, int layer, int norm_scope, cons
     set_error("egcl_forward_save: E x Wx x 2 bytes must stay below 4 GiB (%d edges); train on smaller batches or use the recompute path", c->E);
     return EGNN_EINVAL;
   }
-  c->save_s1x = s1x; c->save_s1m = s1m; c->save_t2x = t2x; c->save_t2m = t2m; c->save_s = s_shares;
-  rc = launch_layer(c, reinterpret_cast<hipStream_t>(stream), layer, EGNN_PREC_BF16, norm_scope, h, x, h_out, x_out, true);
-  c->save_s1x = c->save_s1m = c->save_t2x = c->save_t2m = nullptr; c->save_s = nullptr;
-  return rc;
+  const SaveBuffers save = {s1x, s1m, t2x, t2m, s_shares};
+  return launch_layer(c, reinterpret_cast<hipStream_t>(stream), layer, EGNN_PREC_BF16, norm_scope, h, x, h_out, x_out, true, false, &save);
 }
 
 int egcl_forward_begin(egnn_ctx* c, void* stream, int layer, int prec, int norm_scope, const float* h, const float* x,
@@ -1408,8 +1380,8 @@ int egcl_forward_end(egnn_ctx* c, void* stream, int layer, int prec, int norm_sc
   if (d_sq_sums)
     EGNN_HIP(hipMemcpyAsync(c->gscale, d_sq_sums, sizeof(float) * (norm_scope == EGNN_NORM_GRAPH ? c->B : 1),
                             hipMemcpyDeviceToDevice, st));
-  c->sq_from_agg = false;
-  return launch_layer_end(c, st, layer, prec, norm_scope, h, x, h_out, x_out);
+  if (c->plan.sq == SqSource::kNodePost) c->plan.sq = SqSource::kLaunch;   // node_post reads gscale: the caller's sums, or what it holds
+  return launch_layer_end(c, st, layer, norm_scope, h, x, h_out, x_out);
 }
 
 int egnn_forward(egnn_ctx* c, void* stream, int prec, int norm_scope, const float* h, const float* x, float* h_out,
@@ -1417,15 +1389,7 @@ int egnn_forward(egnn_ctx* c, void* stream, int prec, int norm_scope, const floa
   int rc = check_ready(c, prec, norm_scope);
   if (rc) return rc;
   if (!h || !x || !h_out || !x_out || h == h_out || x == x_out) { set_error("bad egnn_forward arguments"); return EGNN_EINVAL; }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const float *hc = h, *xc = x;
-  for (int l = 0; l < c->L; ++l) {
-    float* ho = (l == c->L - 1) ? h_out : c->h_tmp[l & 1];
-    float* xo = (l == c->L - 1) ? x_out : c->x_tmp[l & 1];
-    if ((rc = launch_layer(c, st, l, prec, norm_scope, hc, xc, ho, xo, false, l + 1 < c->L))) return rc;
-    hc = ho; xc = xo;
-  }
-  return EGNN_OK;
+  return launch_stack(c, reinterpret_cast<hipStream_t>(stream), prec, norm_scope, h, x, h_out, x_out);
 }
 
 int egnn_debug_stamps(egnn_ctx* c, unsigned long long* host_out) {

@@ -191,6 +191,76 @@ bool fork_candidate(int E, int WxP) {
   return E > 0 && idle >= (tiles + 1) / 2;
 }
 
+EdgePath path_of_precision(int prec) {
+  return prec == EGNN_PREC_BF16 ? EdgePath::kBf16 : prec == EGNN_PREC_BF16X3 ? EdgePath::kBf16x3
+       : prec == EGNN_PREC_F16 ? EdgePath::kF16 : prec == EGNN_PREC_F16C8 ? EdgePath::kF16c8 : EdgePath::kGeneric;
+}
+
+// half-precision table: bf16 hi/lo MFMA for H <= 48 (1024-column workgroups once they fill the chip, else 256-column ones),
+// else exact f32 MFMA for H <= 64, else the VALU kernel; the fp32 table has the last two only
+NodePre node_pre_form(bool half_table, int N, int H, int TC) {
+  if (half_table && H <= 48) return (long)((N + kHiloNodes - 1) / kHiloNodes) * (TC / 1024) >= 256 ? NodePre::kHilo8 : NodePre::kHilo2;
+  return H <= 64 ? NodePre::kMfma : NodePre::kValu;
+}
+
+int plan_forward(const ForwardAsk& a, ForwardPlan* out) {
+  ForwardPlan pl;
+  const KernelSupport& sup = a.sup;
+  const int WxP = a.md.WxP;
+  const EdgePath want = path_of_precision(a.prec);
+  const bool takes = want == EdgePath::kBf16 ? sup.v4 && sup.v3 : want == EdgePath::kBf16x3 ? sup.bf16x3
+                   : want == EdgePath::kF16 ? sup.v4 && sup.x_m16 : want == EdgePath::kF16c8 ? sup.f16c8w : false;
+  pl.path = a.sw.edge >= 4 && takes ? want : EdgePath::kGeneric;
+  if (a.save && pl.path != EdgePath::kBf16) { set_error("egcl_forward_save needs the 128-edge-tile bf16 kernels"); return EGNN_EINVAL; }
+  const bool tiled = pl.path != EdgePath::kGeneric;   // the tiled kernels sum d^2 per receiving node themselves
+  pl.frag_bf16 = !tiled && a.prec == EGNN_PREC_BF16;
+  pl.half_table = pl.path == EdgePath::kBf16 || pl.path == EdgePath::kF16;
+  pl.node_pre = node_pre_form(pl.half_table, a.N, a.H, a.md.TC);
+  pl.absorbs_finish = pl.half_table && a.H <= 48;
+  pl.save = a.save;
+
+  if (a.E > 0) {
+    // fork_candidate(): whether the message kernel fits the shadow of the coordinate kernel's last round; the small-tile
+    // kernels fork whenever there is a side stream; a training forward and the one-launch bf16x3 pair never do
+    const bool can_fork = a.side_ok && !a.prof, fork = can_fork && fork_candidate(a.E, WxP);
+    // 32- / 64-edge tiles (edge_small.hip) up to 2,048 / 6,144 edges (profiles/r04e_latency_small_tiles.log, ms per replayed
+    // reverse step: 20-atom cell 0.289 -> 0.277, but one 64-atom cell on 32 rows 0.313 -> 0.343 and five 0.41 -> 0.70): a layer's
+    // weight traffic through L2 is (E / tile rows) x 2.5 MB whatever the column split, and L2 delivers ~7 TB/s to 256 streaming CUs
+    const bool small_ok = pl.half_table && !a.save && a.small_ok && sup.small;
+    const int small = !small_ok ? 0 : a.E <= a.sw.small_edges ? 32 : a.E <= a.sw.small64_edges ? 64 : 0;
+    switch (pl.path) {
+      case EdgePath::kGeneric: pl.form = EdgeForm::kGeneric64; break;
+      case EdgePath::kBf16x3: pl.form = EdgeForm::kBf16x3; pl.R = kTileRows; pl.nsplit_x = WxP / 256; break;
+      case EdgePath::kF16c8: pl.form = EdgeForm::kF16c8; pl.R = kTileRows; pl.nsplit_x = WxP / 512; pl.fork = fork; break;
+      case EdgePath::kBf16:
+      case EdgePath::kF16:
+        pl.f16 = pl.path == EdgePath::kF16;
+        if (small) { pl.form = EdgeForm::kSmall; pl.R = small; pl.nsplit_x = WxP / 512; pl.fork = can_fork; break; }
+        pl.form = EdgeForm::kTile128; pl.R = kTileRows; pl.fork = fork && !a.save;
+        if (!sup.x_m16) { pl.coord = CoordKernel::kV3; break; }   // hidden width 256
+        pl.nsplit_x = WxP / 512;
+        // one persistent workgroup per CU once there are more than two 512-column units per CU
+        if (!a.save && a.sw.x_persist && persistent_possible(a.E, WxP, a.ncu)) {
+          pl.coord = CoordKernel::kXm16Persistent; pl.persist_grid = a.ncu;
+        } else pl.coord = CoordKernel::kXm16;
+        break;
+    }
+  }
+
+  // node MLP of fp16, bf16x3 and f16c8 on their tiled paths: split-operand fp16 products where the shape allows; bf16: the bf16
+  // kernel; else the exact fp32 kernel
+  const bool split_path = pl.path == EdgePath::kF16 || pl.path == EdgePath::kBf16x3 || pl.path == EdgePath::kF16c8;
+  pl.node_post = split_path && sup.post_split ? NodePost::kSplit
+               : a.prec == EGNN_PREC_BF16 && sup.post_bf16 ? NodePost::kBf16 : NodePost::kF32;
+
+  // the per-graph sums need no launch when only node_post reads them and it can add them up itself (not the fp32 kernel)
+  const bool per_graph = a.norm_scope == EGNN_NORM_GRAPH;
+  pl.sq = !tiled ? SqSource::kNodeD2 : a.E == 0 ? SqSource::kMemset
+        : !per_graph || a.need_gscale || pl.node_post == NodePost::kF32 ? SqSource::kLaunch : SqSource::kNodePost;
+  *out = pl;
+  return EGNN_OK;
+}
+
 }  // namespace egnn
 
 using namespace egnn;

@@ -324,22 +324,21 @@ int node_post_split_k();
 bool node_post_bf16_supported(const PostParams& q);
 int init_node_bf16_attributes();
 
+// One launch function per kernel family, the variant as an argument (f16: fp16 operands, else bf16; save: the training forward of
+// egcl_forward_save, bf16 only).  The _bwd launchers are the backward's recompute.
 bool edge_bf16_v3_supported(const EdgeParams& p);
-int launch_edge_bf16_v4_m(const EdgeParams& p, hipStream_t st);
-int launch_edge_bf16_v3_x(const EdgeParams& p, hipStream_t st);
+int launch_edge_v3_x(const EdgeParams& p, hipStream_t st, bool save);   // coordinate kernel for hidden width 256
 int launch_edge_bf16_v3_x_bwd(const EdgeParams& p, hipStream_t st);
-int launch_edge_bf16_v4_m_bwd(const EdgeParams& p, hipStream_t st);
-int launch_edge_bf16_v3_x_save(const EdgeParams& p, hipStream_t st);
-int launch_edge_bf16_v4_m_save(const EdgeParams& p, hipStream_t st);
-bool edge_bf16_v4_supported(const EdgeParams& p);
-int edge_v4_rows();
-int init_edge_bf16_v4_attributes();
 int init_edge_bf16_v3_attributes();
-int launch_edge_x_m16(const EdgeParams& p, hipStream_t st);   // coordinate kernel on v_mfma_f32_16x16x32_bf16
-int launch_edge_x_m16_save(const EdgeParams& p, hipStream_t st);
-int launch_edge_x_m16_f16(const EdgeParams& p, hipStream_t st);   // precision fp16: v_mfma_f32_16x16x32_f16 (p.w2x16 = fp16 fragments)
-int launch_edge_f16_v4_m(const EdgeParams& p, hipStream_t st);    // precision fp16 message kernel (p.w2m = fp16 fragments)
+bool edge_bf16_v4_supported(const EdgeParams& p);
+int launch_edge_v4_m(const EdgeParams& p, hipStream_t st, bool f16, bool save);   // message kernel (p.w2m = fragments of the operand type)
+int launch_edge_bf16_v4_m_bwd(const EdgeParams& p, hipStream_t st);
+int init_edge_bf16_v4_attributes();
+// coordinate kernel for hidden width 512 / 1024 on v_mfma_f32_16x16x32 (p.w2x16 = fragments of the operand type): one workgroup
+// per unit (tile x 512 columns), `grid` persistent workgroups, or the per-unit training forward (bf16 only)
+enum class XForm { kPerUnit, kPersistent, kSave };
 bool edge_x_m16_supported(const EdgeParams& p);
+int launch_edge_x_m16(const EdgeParams& p, hipStream_t st, bool f16, XForm form, int grid = 0);
 int init_edge_x_m16_attributes();
 // 32-edge tiles for small graphs (edge_small.hip): p.w2x16 / p.w2m16 = 16-column fragment streams of the operand type
 int launch_edge_small_x(const EdgeParams& p, hipStream_t st, bool f16, int rows);   // rows = 32 or 64 edges per tile

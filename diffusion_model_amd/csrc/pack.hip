@@ -171,6 +171,7 @@ int egnn_set_model(egnn_ctx* c, int L, int H, int M, int Wm, int Wx, int Wh) {
   (void)hipDeviceSynchronize();
   for (auto& lp : c->layers) free_layer(lp);
   c->layers.assign(L, LayerPack());
+  c->forget_support();
   c->L = L; c->H = H; c->M = M; c->Wm = Wm; c->Wx = Wx; c->Wh = Wh;
   c->WxP = md.WxP; c->WmP = md.WmP; c->MP = md.MP; c->cbx = md.cbx; c->cbm = md.cbm;
   c->WhP = md.WhP; c->HP = md.HP; c->K1P = md.K1P; c->K1Q = md.K1Q; c->TC = md.TC;
@@ -192,6 +193,7 @@ int egnn_pack_layer(egnn_ctx* c, void* stream, int l, const float* m0_w, const f
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   EGNN_HIP(hipSetDevice(c->device));
   LayerPack& lp = c->layers[l];
+  c->forget_support();
   const int H = c->H, M = c->M, Wm = c->Wm, Wx = c->Wx, Wh = c->Wh;
   const int WxP = c->WxP, WmP = c->WmP, MP = c->MP, WhP = c->WhP, HP = c->HP, K1P = c->K1P, TC = c->TC;
   int rc;

@@ -294,14 +294,8 @@ static StepParams make_params(egnn_ctx* c) {
 
 static int enqueue_step(egnn_ctx* c, hipStream_t st, int prec, int norm_scope, const float* npos, const float* nh) {
   Sampler& s = c->smp;
-  int rc;
-  const float *hc = s.h, *xc = s.pos;
-  for (int l = 0; l < c->L; ++l) {
-    float* ho = (l == c->L - 1) ? s.h_out : c->h_tmp[l & 1];
-    float* xo = (l == c->L - 1) ? s.x_out : c->x_tmp[l & 1];
-    if ((rc = launch_layer(c, st, l, prec, norm_scope, hc, xc, ho, xo, false, l + 1 < c->L))) return rc;
-    hc = ho; xc = xo;
-  }
+  const int rc = launch_stack(c, st, prec, norm_scope, s.h, s.pos, s.h_out, s.x_out);
+  if (rc) return rc;
   StepParams p = make_params(c);
   p.noise_pos = npos; p.noise_h = nh;
   hipLaunchKernelGGL(sampler_step_kernel, dim3(c->B), dim3(kThreads), 0, st, p);
@@ -535,14 +529,8 @@ int egnn_sampler_final(egnn_ctx* c, void* stream, int prec, int norm_scope, cons
   if (s.x_only) { set_error("the x-only loop (test.py:253-279) has no t = 0 decode: read egnn_sampler_state"); return EGNN_ESTATE; }
   if (!d_pos_out || !d_hc_out || !d_onehot_out) { set_error("null output"); return EGNN_EINVAL; }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int rc;
-  const float *hc = s.h, *xc = s.pos;
-  for (int l = 0; l < c->L; ++l) {
-    float* ho = (l == c->L - 1) ? s.h_out : c->h_tmp[l & 1];
-    float* xo = (l == c->L - 1) ? s.x_out : c->x_tmp[l & 1];
-    if ((rc = launch_layer(c, st, l, prec, norm_scope, hc, xc, ho, xo, false, l + 1 < c->L))) return rc;
-    hc = ho; xc = xo;
-  }
+  const int rc = launch_stack(c, st, prec, norm_scope, s.h, s.pos, s.h_out, s.x_out);
+  if (rc) return rc;
   StepParams p = make_params(c);
   hipLaunchKernelGGL(sampler_final_kernel, dim3(c->B), dim3(kThreads), 0, st, p, d_noise_pos, d_noise_h, d_pos_out,
                      d_hc_out, d_onehot_out);

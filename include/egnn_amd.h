@@ -110,7 +110,8 @@ int egcl_forward(egnn_ctx* ctx, void* stream, int layer, int prec, int norm_scop
  * _begin runs node_pre + the fused edge pass and returns this rank's sums of d^2 (float[B], or [1] in 'call'
  * scope); the caller all-reduces them (the coordinate normaliser of :64 spans all edges) and passes the
  * totals to _end, which runs node_post; rows of nodes the rank does not own are meaningless and the caller
- * all-gathers the owned rows.  d_sq_sums may be NULL (single rank: use the local sums). */
+ * all-gathers the owned rows.  d_sq_sums may be NULL (single rank: use the local sums).  _end finishes the layer the last
+ * _begin on this context started: its layer and prec must be that call's (the node kernel was chosen there). */
 int egcl_forward_begin(egnn_ctx* ctx, void* stream, int layer, int prec, int norm_scope,
                        const float* d_h, const float* d_x, float* d_sq_sums);
 int egcl_forward_end(egnn_ctx* ctx, void* stream, int layer, int prec, int norm_scope,

@@ -196,8 +196,8 @@ def _aggregates(c):
     return sm, sx, sq
 
 
-# edge counts up to which egcl_forward in bf16 takes the 32 / 64-edge-tile kernels at hidden width 512 / 1024 (egnn_forward.hip
-# small_tiles); the training forward always takes the 128-edge tiles
+# edge counts up to which egcl_forward in bf16 takes the 32 / 64-edge-tile kernels at hidden width 512 / 1024 (host_logic.cpp:
+# plan_forward); the training forward always takes the 128-edge tiles
 SMALL_TILE_EDGES = int(os.environ.get("EGNN_SMALL64_EDGES", 6144))   # (the library's own measurement switch moves the limit)
 
 

@@ -271,7 +271,7 @@ def _refs(case):
     Mo = case[7] if len(case) > 7 else 256
     b = _graph(graph)
     ex = _expect(prec, Wx, Wm, Mo, H, Wh, b.N, b.E)
-    # a precision outside its tiling runs the generic kernel: bf16 as bf16, the others as the exact fp32 path (egnn_forward.hip: plan_edge)
+    # a precision outside its tiling runs the generic kernel: bf16 as bf16, the others as the exact fp32 path (host_logic.cpp: plan_forward)
     ran = prec if ex.tiled else ("bf16g" if prec == "bf16" else "fp32")
     return _edge_ref(H, Wx, Wm, Mo, Wh, graph, ran), _edge_ref(H, Wx, Wm, Mo, Wh, graph, None), ex
 

@@ -601,3 +601,150 @@ def compare_structures(original_graph_list, generated_graph_list, sigma=5, R=5.0
                 total=dict(rdf=_curve_metrics(o.partial_rdf.double().sum(0), g.partial_rdf.double().sum(0)),
                            angles=_curve_metrics(o.angles.sum(0), g.angles.sum(0))),
                 cn_original=o.cn, cn_generated=g.cn, original=o, generated=g)
+
+
+# ---- topological fingerprint (csrc/eval/topo.hip) ------------------------------------------------------------------
+COVALENT_RADII = (0.66, 1.11)   # (O, Si), Cordero et al. 2008, in the order of the one-hot columns ([1, 0] is O)
+
+
+def _host_ptr(a):
+    import ctypes
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+class _TopoInput:
+    """positions, type indices, graph_ptr and the bond lists of a batch on the device (egnn_topo_bonds: three launches)"""
+
+    def __init__(self, pos, onehot, sizes, radii, scale, what):
+        if not pos.is_cuda:
+            raise RuntimeError(f"{what} needs CUDA(ROCm) tensors; there is no CPU fallback")
+        sizes = [int(s) for s in sizes]
+        self.sizes, self.B, self.N = sizes, len(sizes), sum(sizes)
+        if self.B < 1 or min(sizes) < 0 or self.N < 1:
+            raise ValueError(f"{what} needs at least one graph, at least one atom and no negative size")
+        if pos.shape != (self.N, 3):
+            raise ValueError("position must be [sum(sizes), 3]")
+        oh = onehot.detach().to(pos.device)
+        if oh.dim() != 2 or oh.shape[0] != self.N or oh.shape[1] < 1:
+            raise ValueError("onehot must be [sum(sizes), A]")
+        self.A = int(oh.shape[1])
+        if not bool((((oh == 0) | (oh == 1)).all(1) & (oh.sum(1) == 1)).all()):
+            raise ValueError("every row of onehot must be exactly one-hot")
+        radii = np.asarray(radii, dtype=np.float64).reshape(-1)
+        if radii.size != self.A:
+            raise ValueError(f"{radii.size} radii for {self.A} atom types")
+        self.thr = np.ascontiguousarray(float(scale) * (radii[:, None] + radii[None, :]))   # fp64, once per type pair
+        self.dev = pos.device
+        self.pos = pos.detach().to(torch.float32).contiguous()
+        self.type = oh.argmax(1).to(torch.int32).contiguous()
+        self.max_atoms = max(sizes)
+        sz = np.asarray(sizes, dtype=np.int64)
+        head = np.concatenate([[0], np.cumsum(sz), [0], np.cumsum(sz * sz)])   # graph_ptr [B+1], then dist_ptr [B+1]
+        blob = torch.from_numpy(head).to(self.dev)                              # one upload
+        self.gp = blob[:self.B + 1].to(torch.int32)
+        self.dist_ptr = blob[self.B + 1:].contiguous()
+        self.n_dist = int(head[-1])
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=self.dev)
+        self.row_ptr, self.neighbours, self.degree, self.overflow = i32(self.N + 1), i32(_lib.TOPO_MAX_DEGREE * self.N), i32(self.N), i32(self.B)
+        _lib.check(_lib.lib().egnn_topo_bonds(_lib.stream_ptr(), self.B, self.N, self.A, _lib.ptr(self.pos), _lib.ptr(self.type),
+                                              _lib.ptr(self.gp), self.max_atoms, _host_ptr(self.thr), _lib.ptr(self.row_ptr),
+                                              _lib.ptr(self.neighbours), _lib.ptr(self.degree), _lib.ptr(self.overflow)))
+
+    def paths(self, max_length, dist=False, component=False, fp=True):
+        """egnn_topo_paths -> (dist [sum n^2], the uint16 values in an int16 tensor | None, component | None, fragments | None, fp int32 [B, K] | None)"""
+        L = int(max_length)
+        Cn = _lib.TOPO_BRANCH_MODULUS * self.A
+        d = torch.empty(self.n_dist, dtype=torch.int16, device=self.dev) if dist else None
+        c = torch.empty(self.N, dtype=torch.int32, device=self.dev) if component else None
+        f = torch.empty(self.B, dtype=torch.int32, device=self.dev) if component else None
+        k = torch.empty(self.B, Cn * (Cn + 1) // 2 * max(L, 1), dtype=torch.int32, device=self.dev) if fp else None
+        _lib.check(_lib.lib().egnn_topo_paths(_lib.stream_ptr(), self.B, self.N, self.A, _lib.ptr(self.type), _lib.ptr(self.gp), self.max_atoms,
+                                              _lib.ptr(self.row_ptr), _lib.ptr(self.neighbours), _lib.ptr(self.degree), _lib.ptr(self.overflow),
+                                              L, _lib.ptr(d), _lib.ptr(self.dist_ptr), _lib.ptr(c), _lib.ptr(f), _lib.ptr(k)))
+        return d, c, f, k
+
+
+def _raise_on_topo_overflow(over, side=""):
+    """``side`` names the list a graph belongs to where a call looks at two ('original' / 'generated')"""
+    bad = torch.nonzero(over > 0)
+    if bad.numel():
+        g = int(bad[0])
+        raise RuntimeError(f"{side + ' ' if side else ''}graph {g}: {int(over[g])} atom(s) with more than 32 bonds; the graph has no "
+                           "bond list, distances or fingerprint (lower the scale or the radii)")
+
+
+def bond_graph(pos: torch.Tensor, onehot: torch.Tensor, sizes: Sequence[int], radii=COVALENT_RADII, scale=1.2):
+    """The bond graph guess_bonds draws (evaluate_fingerprint.py:49-84), for a ragged batch: atoms i != j of one graph are bonded
+    iff |p_i - p_j| < scale * (radii[type i] + radii[type j]), the distance in fp64 from the float32 positions.
+    -> (row_ptr int64 [N+1], neighbours int64 [n_bonds], degree int64 [N]): a CSR list over the atoms of the whole batch, every row
+    ascending, atom indices counting over the batch.  ``onehot`` [N, A] exactly one-hot, A <= 4 = len(radii); graphs of at most
+    1024 atoms.  Raises RuntimeError, naming the first such graph, if an atom has more than 32 bonds."""
+    inp = _TopoInput(pos, onehot, sizes, radii, scale, "bond_graph")
+    _raise_on_topo_overflow(inp.overflow)
+    row_ptr = inp.row_ptr.long()
+    return row_ptr, inp.neighbours[:int(row_ptr[-1])].long(), inp.degree.long()
+
+
+def topological_distances(pos: torch.Tensor, onehot: torch.Tensor, sizes: Sequence[int], radii=COVALENT_RADII, scale=1.2):
+    """Hop distances on the bond graph of bond_graph: -> (list of int64 [n, n], one per graph, the number of bonds on a shortest
+    path and -1 where there is none; fragments int64 [B], the connected components of each graph; component int64 [N], the lowest
+    atom index -- counted over the batch -- reachable from each atom)."""
+    inp = _TopoInput(pos, onehot, sizes, radii, scale, "topological_distances")
+    _raise_on_topo_overflow(inp.overflow)
+    d, comp, frag, _ = inp.paths(1, dist=True, component=True, fp=False)
+    d = d.long() & 0xFFFF
+    d = torch.where(d == 0xFFFF, torch.full_like(d, -1), d)
+    return [b.view(n, n) for b, n in zip(d.split([n * n for n in inp.sizes]), inp.sizes)], frag.long(), comp.long()
+
+
+def atom_pair_fingerprint(pos: torch.Tensor, onehot: torch.Tensor, sizes: Sequence[int], radii=COVALENT_RADII, scale=1.2, max_length=30):
+    """The atom-pair count vector of every graph's bond graph (AllChem.GetAtomPairFingerprint, evaluate_fingerprint.py:109-110,
+    restated): int32 [B, K], K = C (C + 1) / 2 * max_length with C = 7 A.  Every pair of atoms i < j joined by a shortest path of
+    1 <= d <= max_length bonds counts once under the key (class lo, class hi, d), class = type * 7 + degree % 7:
+    fp[g, (c_lo C - c_lo (c_lo - 1) / 2 + c_hi - c_lo) * max_length + d - 1]."""
+    inp = _TopoInput(pos, onehot, sizes, radii, scale, "atom_pair_fingerprint")
+    _raise_on_topo_overflow(inp.overflow)
+    return inp.paths(max_length)[3]
+
+
+def _tanimoto(fp_a, fp_b):
+    n, K = fp_a.shape
+    sim = torch.empty(n, dtype=torch.float64, device=fp_a.device)
+    sa, sb = torch.empty(n, dtype=torch.int64, device=fp_a.device), torch.empty(n, dtype=torch.int64, device=fp_a.device)
+    _lib.check(_lib.lib().egnn_topo_tanimoto(_lib.stream_ptr(), n, K, _lib.ptr(fp_a), n, _lib.ptr(fp_b), n, None, _lib.ptr(sim),
+                                             _lib.ptr(sa), _lib.ptr(sb)))
+    return sim, sa, sb
+
+
+def tanimoto(fp_a: torch.Tensor, fp_b: torch.Tensor):
+    """Tanimoto similarity of count vectors, row by row (DataStructs.TanimotoSimilarity, evaluate_fingerprint.py:96-97):
+    -> (sim float64 [B], sa int64 [B], sb int64 [B]); sim = sum min(a, b) / (sa + sb - sum min(a, b)), integer sums and one fp64
+    division; 0.0 where both rows are empty (sa = sb = 0 tells)."""
+    if not fp_a.is_cuda or not fp_b.is_cuda:
+        raise RuntimeError("tanimoto needs CUDA(ROCm) tensors; there is no CPU fallback")
+    if fp_a.dim() != 2 or fp_a.shape != fp_b.shape or fp_a.shape[0] < 1 or fp_a.shape[1] < 1:
+        raise ValueError("fp_a and fp_b must be [B, K] of one shape")
+    return _tanimoto(fp_a.to(torch.int32).contiguous(), fp_b.to(torch.int32).contiguous())
+
+
+def fingerprint_similarity(original_graph_list, generated_graph_list, radii=COVALENT_RADII, scale=1.2, max_length=30):
+    """The loop of evaluate_fingerprint.py:127-134 on what generate() returns (the list conventions of evaluate_by_rmsd): for every
+    original and the LAST element of its generated entry, guess the bonds, take the atom-pair fingerprints and their Tanimoto
+    similarity; one-atom graphs are skipped.  Both sides are collated once; two fingerprint passes, one Tanimoto launch, one
+    download.  -> (similarities: list of float in list order, one per graph that was not skipped; skipped: list of the indices
+    that were).  Raises RuntimeError naming the side ('original' / 'generated') and the first graph with an atom above 32 bonds."""
+    col = _collate_pairs(original_graph_list, generated_graph_list, True)
+    if col is None:
+        return [], []
+    sizes, _, po, pg, xo, xg = col
+    if xo.shape[1:] != xg.shape[1:]:
+        raise ValueError("originals and samples differ in the number of atom types")
+    a = _TopoInput(po, xo, sizes, radii, scale, "fingerprint_similarity")
+    b = _TopoInput(pg, xg, sizes, radii, scale, "fingerprint_similarity")
+    sim, _, _ = _tanimoto(a.paths(max_length)[3], b.paths(max_length)[3])
+    out = torch.cat([sim, a.overflow.double(), b.overflow.double()]).cpu()   # ONE download
+    B = len(sizes)
+    _raise_on_topo_overflow(out[B:2 * B], "original")      # (such a graph's fingerprint is zero: the launches above were harmless)
+    _raise_on_topo_overflow(out[2 * B:], "generated")
+    skipped = [i for i, n in enumerate(sizes) if n == 1]
+    return [float(out[i]) for i, n in enumerate(sizes) if n != 1], skipped

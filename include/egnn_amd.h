@@ -504,6 +504,51 @@ int egnn_struct_counts_host(int B, int A, const float* pos, const int32_t* type,
                             float cutoff, double dtheta, int max_cn, int32_t* counts, int32_t* cn, int32_t* angles,
                             int32_t* overflow);
 
+/* ---- topological fingerprint (csrc/eval/topo.hip; definitions in csrc/eval/topo_math.h) ------------------------------------
+ * evaluate_fingerprint.py:99-114 scores a sample by its bonding network: bonds guessed from distances (guess_bonds, :49-84),
+ * RDKit's atom-pair fingerprint of the bond graph, Tanimoto similarity.  These entries restate it for a ragged batch without ASE
+ * or RDKit.  Atoms carry a type index d_type int32 [N] in [0, A), A <= 4; graphs through d_graph_ptr int32 [B+1] over N atoms;
+ * max_atoms is the size of the largest graph, at most 1024 (EGNN_ASSIGN_MAX_ATOMS).  Atom indices in every list count over the
+ * whole batch (0 .. N-1).  All sums are integers: the outputs are bitwise reproducible and equal to egnn_topo_host's.  Bad
+ * arguments (A > 4, max_atoms > 1024, L outside [1, 64], a threshold that is not positive and finite, a required pointer NULL)
+ * return EGNN_EINVAL before anything is launched; a kernel ignores a type outside [0, A) (the atom bonds to nothing).
+ *
+ * egnn_topo_bonds: i != j of one graph are bonded iff d < thr[type i][type j], d = sqrt((dx*dx + dy*dy) + dz*dz) in fp64 from the
+ * float32 positions; thr is a HOST table double [A][A] (scale * (radius_a + radius_b), computed once by the caller).
+ *   d_degree int32 [N]:      bonds of each atom, all of them;
+ *   d_row_ptr int32 [N+1]:   exclusive prefix sum of min(degree, 32);
+ *   d_neighbours int32:      the caller allocates 32 N entries; row i holds the first min(degree, 32) neighbours, ascending;
+ *   d_overflow int32 [B]:    atoms of the graph with more than 32 bonds.  Such a graph has no distances and no fingerprint.
+ * d_row_ptr is one workgroup's prefix sum, ceil(N / 1024) degrees per thread: meant for evaluation batches (tens of thousands of
+ * atoms); N up to 2^26 is accepted and correct, but that sum then runs on one CU. */
+int egnn_topo_bonds(void* stream, int B, int N, int A, const float* d_pos, const int32_t* d_type, const int32_t* d_graph_ptr,
+                    int max_atoms, const double* thr, int32_t* d_row_ptr, int32_t* d_neighbours, int32_t* d_degree,
+                    int32_t* d_overflow);
+/* egnn_topo_paths: one breadth-first search per atom over the lists of egnn_topo_bonds, one workgroup per graph.  Each output may
+ * be NULL:
+ *   d_dist uint16:           graph g's [n, n] hop distances (bonds on a shortest path, never capped) from element d_dist_ptr[g]
+ *                            on (int64 [B], the caller's prefix sum of n^2); 0xFFFF = unreachable;
+ *   d_component int32 [N]:   the lowest atom index reachable from i;   d_fragments int32 [B]: connected components;
+ *   d_fp int32 [B, K]:       atom-pair counts, K = C (C+1)/2 * L with C = 7 A: for i < j with 1 <= d <= L,
+ *                            ++fp[(c_lo C - c_lo (c_lo-1)/2 + c_hi - c_lo) L + d - 1], class = type * 7 + degree % 7.  Zeroed by the call.
+ * A graph with d_overflow[g] != 0 gets distances 0xFFFF, components -1, fragments -1 and a zero fingerprint; a graph of no atoms
+ * gets fragments 0 and a zero fingerprint. */
+int egnn_topo_paths(void* stream, int B, int N, int A, const int32_t* d_type, const int32_t* d_graph_ptr, int max_atoms,
+                    const int32_t* d_row_ptr, const int32_t* d_neighbours, const int32_t* d_degree, const int32_t* d_overflow, int L,
+                    uint16_t* d_dist, const int64_t* d_dist_ptr, int32_t* d_component, int32_t* d_fragments, int32_t* d_fp);
+/* egnn_topo_tanimoto: pair p compares row d_pairs[2p] of d_fp_a [rows_a, K] with row d_pairs[2p+1] of d_fp_b [rows_b, K]
+ * (d_pairs int32 [n_pairs, 2]; NULL = row p with row p): both = sum min, sa = sum a, sb = sum b in int64,
+ * d_sim double [n_pairs] = both / (sa + sb - both) as one fp64 division, 0.0 where the denominator is 0; d_sa, d_sb int64 [n_pairs].
+ * A pair that names no row gets sim 0, sa = sb = -1. */
+int egnn_topo_tanimoto(void* stream, int n_pairs, int K, const int32_t* d_fp_a, int rows_a, const int32_t* d_fp_b, int rows_b,
+                       const int32_t* d_pairs, double* d_sim, int64_t* d_sa, int64_t* d_sb);
+/* Host statement of the three entries above: HOST pointers, no GPU, the same definitions in plain C++.  dist is contiguous (graph
+ * g's block follows graph g-1's); dist, component, fragments and fp may be NULL; the n_pairs pairs name rows of fp itself.
+ * Types outside [0, A) and graphs above 1024 atoms are EGNN_EINVAL. */
+int egnn_topo_host(int B, int A, const float* pos, const int32_t* type, const int32_t* graph_ptr, const double* thr, int L,
+                   int32_t* row_ptr, int32_t* neighbours, int32_t* degree, int32_t* overflow, uint16_t* dist, int32_t* component,
+                   int32_t* fragments, int32_t* fp, int n_pairs, const int32_t* pairs, double* sim, int64_t* sa, int64_t* sb);
+
 /* ---- local environments of periodic cells (csrc/cells/cell_env.hip; definitions in csrc/cells/cell_math.h) ---------------
  * Every record of the reference is a local environment cut out of a periodic cell: make_dataset.py:79-142 builds the 3x3x3
  * supercell (:79-92), its full distance matrix (:99), takes the sites closer than 2.0 A to the excited oxygen

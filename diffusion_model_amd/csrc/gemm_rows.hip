@@ -179,7 +179,8 @@ int egnn_gemm_rows_bf16(void* stream, int E, const void* d_A0, int lda0, int K0,
   {
     const int rc = gemm_rows_args_check(E, d_A0, lda0, K0, d_W0, d_A1, lda1, K1, d_W1, d_out, ldo);   // host_logic.cpp
     if (rc) return rc;
-    if (n_chunks < 1 || n_chunks > 65535 || ldo < 128 * n_chunks) { set_error("egnn_gemm_rows_bf16: %d column chunks need ldo >= %d", n_chunks, 128 * n_chunks); return EGNN_EINVAL; }
+    const int rc_out = gemm_rows_out_check(d_out, ldo, out_f32, n_chunks);
+    if (rc_out) return rc_out;
   }
   GemmRowsParams p;
   p.A[0] = d_A0; p.lda[0] = lda0; p.K[0] = K0; p.W[0] = d_W0;

@@ -74,12 +74,18 @@ void plan_gemm_tn(int E, int M, int N, int& BN, int& tiles_n, int& S, int& steps
 }
 
 static bool gemm_tn_shape_ok(int E, int M, int N) { return !(E < 1 || M < 256 || M % 256 != 0 || N < 128 || N % 128 != 0); }
+// the LDS-DMA loads fetch 16-byte pieces at base + row * ld * 2 + 16 * piece (ld % 8 == 0): the base must be aligned too
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
 int gemm_tn_args_check(int E, int M, int N, const void* A, int lda, const void* B, int ldb, const void* C, int ldc, int rows,
                        int cols, const void* workspace, size_t workspace_bytes) {
   if (!gemm_tn_shape_ok(E, M, N) || lda < M || ldb < N || lda % 8 != 0 || ldb % 8 != 0 || !A || !B || !C || rows < 1 || rows > M ||
       cols < 1 || cols > N || ldc < cols) {
     set_error("egnn_gemm_tn_bf16: unsupported shape E=%d M=%d N=%d lda=%d ldb=%d", E, M, N, lda, ldb);
+    return EGNN_EINVAL;
+  }
+  if (misaligned16(A) || misaligned16(B)) {
+    set_error("egnn_gemm_tn_bf16: the operands must be 16-byte aligned");
     return EGNN_EINVAL;
   }
   // The kernel forms 32-bit byte offsets for the rows of its LAST k-step too (up to kGemmBK - 1 rows past E, answered with
@@ -105,10 +111,26 @@ int gemm_rows_args_check(int E, const void* A0, int lda0, int K0, const void* W0
     set_error("egnn_gemm_rows_bf16: unsupported shape E=%d K0=%d K1=%d", E, K0, K1);
     return EGNN_EINVAL;
   }
+  if (misaligned16(A0) || misaligned16(W0) || (A1 && (misaligned16(A1) || misaligned16(W1)))) {
+    set_error("egnn_gemm_rows_bf16: the operands and the fragment packs must be 16-byte aligned");
+    return EGNN_EINVAL;
+  }
   // a workgroup covers 256 rows: the offsets of the rows past E in the last workgroup must not wrap (see gemm_tn_args_check)
   const size_t lim = (size_t)1 << 32;
   if ((size_t)(E + 255) * lda0 * 2 >= lim || (A1 && (size_t)(E + 255) * lda1 * 2 >= lim)) {
     set_error("egnn_gemm_rows_bf16: operand larger than 4 GiB (cut the rows into chunks)");
+    return EGNN_EINVAL;
+  }
+  return EGNN_OK;
+}
+
+int gemm_rows_out_check(const void* out, int ldo, int out_f32, int n_chunks) {
+  if (n_chunks < 1 || n_chunks > 65535 || ldo < 128 * n_chunks) {
+    set_error("egnn_gemm_rows_bf16: %d column chunks need ldo >= %d", n_chunks, 128 * n_chunks);
+    return EGNN_EINVAL;
+  }
+  if (!out_f32 && (ldo % 8 != 0 || misaligned16(out))) {
+    set_error("egnn_gemm_rows_bf16: a bf16 output is stored in 16-byte pieces: ldo %% 8 == 0 and a 16-byte aligned base (ldo=%d)", ldo);
     return EGNN_EINVAL;
   }
   return EGNN_OK;

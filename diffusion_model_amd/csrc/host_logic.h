@@ -34,6 +34,9 @@ int gemm_tn_args_check(int E, int M, int N, const void* A, int lda, const void* 
                        int cols, const void* workspace, size_t workspace_bytes);
 int gemm_rows_args_check(int E, const void* A0, int lda0, int K0, const void* W0, const void* A1, int lda1, int K1, const void* W1,
                          const void* out, int ldo);
+// the output side of egnn_gemm_rows_bf16: n_chunks column chunks inside ldo; a bf16 output is stored in 16-byte pieces, so its
+// base must be 16-byte aligned and its row stride a multiple of 8 (an fp32 output is stored element by element: ldo % 4)
+int gemm_rows_out_check(const void* out, int ldo, int out_f32, int n_chunks);
 int dense_rows_args_check(int N, int K, int J, const void* in, const void* W, const void* b, const void* out);
 
 // the message edge kernel goes to the caller's side stream when the coordinate kernel's last round of workgroups leaves

@@ -256,7 +256,12 @@ int egcl_backward_dgrad_reduce(egnn_ctx* ctx, void* stream, int layer, const flo
  * leave them: dL/da2 and the activations s1; dL/da1 and the gathered inputs), C fp32 with leading dimension ldc.  M and N are
  * the operand widths the kernel reads (M % 256 == 0, N % 128 == 0, M <= lda, N <= ldb; columns beyond rows / cols are
  * computed and dropped), split over slices of E whose fp32 partial tiles go through d_workspace
- * (egnn_gemm_tn_workspace_bytes) and are added in slice order: deterministic.  Replaces torch.mm / bmm (round 2). */
+ * (egnn_gemm_tn_workspace_bytes) and are added in slice order: deterministic.  Replaces torch.mm / bmm (round 2).
+ * Reads and writes: d_A and d_B are 16-byte aligned, lda and ldb multiples of 8.  Rows at and past E of a taller buffer are
+ * never read, nor are columns at and past M / N.  Columns rows..M-1 of A and cols..N-1 of B (the padding inside the operand
+ * width) are read and may hold anything, NaN included: column m of A only ever meets row m of C.  Of C exactly the elements
+ * [0, rows) x [0, cols) are written (ldc >= cols; everything else in a wider or taller C is left alone), and of the
+ * workspace only its first egnn_gemm_tn_workspace_bytes(E, M, N) bytes. */
 size_t egnn_gemm_tn_workspace_bytes(int E, int M, int N);
 int egnn_gemm_tn_bf16(void* stream, int E, int M, int N, const void* d_A, int lda, const void* d_B, int ldb, float scale,
                       float* d_C, int ldc, int rows, int cols, int accumulate, void* d_workspace, size_t workspace_bytes);
@@ -267,7 +272,13 @@ int egnn_gemm_tn_bf16(void* stream, int E, int M, int N, const void* d_A, int ld
  * W0 / W1 are fragment packs made by egnn_gemm_rows_pack from fp32 [K, ldw] matrices whose first ncols columns are used:
  * K * 128 bf16 per chunk of 128 columns, chunk after chunk (ceil(ncols / 128) chunks).  K % 64 == 0.  n_chunks column chunks
  * run in ONE launch (out columns 128 j .. 128 j + 127 from chunk j of both packs; ldo >= 128 n_chunks): the node MLP's
- * backward products are 8 chunks wide over only N / 256 row blocks.  Replaces torch.mm + addmm_ (round 2). */
+ * backward products are 8 chunks wide over only N / 256 row blocks.  Replaces torch.mm + addmm_ (round 2).
+ * Reads and writes: A0, A1 and the packs are 16-byte aligned, lda0 and lda1 multiples of 8.  Rows at and past E and columns at
+ * and past K0 / K1 of the operands are never read.  Of out, rows [0, E) x columns [0, 128 n_chunks) are written, ALL of them
+ * (columns ncols..128 n_chunks-1 receive the zeros of the pack's padding), nothing else.  A bf16 out is stored in 16-byte
+ * pieces: 16-byte aligned base and ldo % 8 == 0; an fp32 out element by element: ldo % 4 == 0.
+ * egnn_gemm_rows_pack reads the first ncols columns of its K rows of d_W only (ldw >= ncols; the rest may hold anything) and
+ * writes K * 128 * ceil(ncols / 128) bf16. */
 int egnn_gemm_rows_pack(void* stream, int K, int ncols, const float* d_W, int ldw, void* d_frags_out);
 int egnn_gemm_rows_bf16(void* stream, int E, const void* d_A0, int lda0, int K0, const void* d_W0, const void* d_A1, int lda1,
                         int K1, const void* d_W1, void* d_out, int ldo, int out_f32 /* fp32 [E, ldo] output */, int n_chunks);

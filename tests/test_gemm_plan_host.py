@@ -1,0 +1,64 @@
+"""The host side of the training GEMMs (csrc/host_logic.cpp: plan_gemm_tn, gemm_tn_args_check, gemm_rows_args_check,
+gemm_rows_out_check) as a stand-alone program under AddressSanitizer + UBSan (no GPU): tests/host/gemm_plan_main.cpp has its own
+main and links its own sanitizer runtime statically, so nothing is preloaded.  The program reads the cases of
+tests/_gemm_cases.py, checks that the argument checks accept each of them and refuse the bad variants (a bf16 output stride
+that is no multiple of 8, a base pointer inside a 16-byte piece, a short workspace ...), sweeps E = 1 .. 40000 over the (M, N)
+of the cases for the invariants of the split-K plan, and prints each case's plan, which is compared with the Python
+restatement here and in tests/test_gemm_cases_cpu.py."""
+import atexit
+import functools
+import os
+import shutil
+import subprocess
+import tempfile
+
+from tests import _gemm_cases as GC
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@functools.lru_cache(maxsize=None)
+def host_program_run():
+    """build and run the program once per session -> (return code, stdout, stderr)"""
+    tmp = tempfile.mkdtemp(prefix="gemm_plan_")
+    atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+    exe, cases = os.path.join(tmp, "gemm_plan_main"), os.path.join(tmp, "cases.txt")
+    with open(cases, "w") as f:
+        f.write(GC.host_case_lines())
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "host", "gemm_plan_main.cpp"),
+           os.path.join(ROOT, "diffusion_model_amd", "csrc", "host_logic.cpp"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-4000:]
+    env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    r = subprocess.run([exe, cases], env=env, capture_output=True, text=True, timeout=120)
+    return r.returncode, r.stdout, r.stderr
+
+
+def host_plans():
+    """{(E, M, N): (BN, tiles_n, S, steps_per_slice)} as the host code planned the cases"""
+    _, out, _ = host_program_run()
+    plans = {}
+    for line in out.splitlines():
+        w = line.split()
+        if w and w[0] == "PLAN":
+            v = [int(x) for x in w[1:]]
+            plans[tuple(v[:3])] = tuple(v[3:])
+    return plans
+
+
+def test_gemm_plan_and_checks_under_sanitizers():
+    rc, out, err = host_program_run()
+    assert rc == 0 and "GEMM-PLAN-OK" in out, f"rc={rc}\nstdout:\n{out[-6000:]}\nstderr:\n{err[-4000:]}"
+    assert "ERROR: AddressSanitizer" not in err and "runtime error" not in err, err[-4000:]
+    assert f"cases: {len(GC.TN_CASES)} tn, {len(GC.ROWS_CASES)} rows" in out
+    swept = {tuple(int(x) for x in line.split()[1:]) for line in out.splitlines() if line.startswith("SWEEP")}
+    assert swept == {(c.M, c.N) for c in GC.TN_CASES}
+
+
+def test_host_plan_equals_the_restatement():
+    plans = host_plans()
+    assert len(plans) == len({(c.E, c.M, c.N) for c in GC.TN_CASES})
+    for c in GC.TN_CASES:
+        p = GC.plan_gemm_tn(c.E, c.M, c.N)
+        assert plans[(c.E, c.M, c.N)] == (p.BN, p.tiles_n, p.S, p.steps_per_slice), c

@@ -620,7 +620,8 @@ int egnn_cell_env_host(int C, int A, const int32_t* cell_ptr, const double* latt
 int egnn_gamma_tilde(void* stream, int n, int hidden, const float* d_t, const float* d_l1_w, const float* d_l2_w,
                      const float* d_l3_w, float* d_out);
 /* One Linear (+ ReLU) over node rows: out [N, J] = act(in [N, K] . W^T + b), W in nn.Linear layout [J, K]
- * (SpectrumCompressor, DataPreprocessor.py:10-19, layer by layer). */
+ * (SpectrumCompressor, DataPreprocessor.py:10-19, layer by layer).  1 <= K <= 2048: a workgroup stages 16 rows of K floats in
+ * LDS, 128 KiB at the limit; a larger K returns EGNN_EINVAL before anything is launched. */
 int egnn_dense_rows(void* stream, int N, int K, int J, const float* d_in, const float* d_W, const float* d_b, int relu,
                     float* d_out);
 

@@ -10,7 +10,8 @@
 // fp32 geometry, SiLU / sigmoid and segment sums, fp32 node MLP.  The tile, the phase-opposed K loop and the operand
 // pipeline are those of edge_bf16_v3.hip at ONE 32-column block per wave (256 columns per workgroup: the coordinate
 // branch runs as WxP / 256 column shares whose coordinate sums node_post adds; s_ij is linear in the column shares);
-// prologue, heads and segment sums are the shared ones of edge_tile.h.
+// prologue, build-thread setup, operand-read helpers, heads and segment sums are the shared ones of edge_tile.h.  Two kernels: the
+// coordinate branch (edge_x3_kernel<false>) and the message branch (edge_x3_kernel<true>).
 #include "edge_tile.h"
 
 namespace egnn {
@@ -18,11 +19,10 @@ namespace egnn {
 namespace {
 
 using namespace tile128;
-constexpr int kT = 512;
-constexpr int kRPAD = kR + 1;
-constexpr int kKC = 64;
-constexpr size_t kImg = (size_t)8 * kRPAD * 16;   // one activation image [8 k-groups][129][8 bf16] (head or remainder)
-__host__ __device__ inline size_t x3_smem_bytes(int KP) { return kOffLoop + 4 * kImg + (size_t)KP * 4; }
+constexpr size_t kImg = kChunkBytes;   // one activation image (head or remainder) of a chunk
+__host__ __device__ constexpr size_t x3_smem_bytes(int KP) { return kOffLoop + 4 * kImg + (size_t)KP * 4; }
+static_assert(x3_smem_bytes(256) == 81472 && x3_smem_bytes(512) == 82496 && x3_smem_bytes(1024) == 84544,
+              "LDS allocation of the bf16x3 kernels");
 
 // SiLU + head / remainder split of one build unit (8 columns of one row): table, wd pre-scaled by -log2(e)
 __device__ __forceinline__ void unit_finish_hilo(const Unit& u, const float* wd, float d2, char* slot_hi, char* slot_lo) {
@@ -42,7 +42,7 @@ __device__ __forceinline__ void unit_finish_hilo(const Unit& u, const float* wd,
 }
 
 template <bool IS_M>
-__global__ __launch_bounds__(kT, 2) void edge_x3_kernel(const EdgeParams p) {
+__global__ __launch_bounds__(kTileThreads, 2) void edge_x3_kernel(const EdgeParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const Lds L(smem);
   char* s_a1 = smem + kOffLoop;                       // [2 buffers][head image | remainder image]
@@ -61,22 +61,15 @@ __global__ __launch_bounds__(kT, 2) void edge_x3_kernel(const EdgeParams p) {
   const int S = prologue(p, L, e0, nvalid, IS_M ? p.wdm : p.wdx, KP, s_wd, tid, lane, wave);
 
   // ---- K loop ----
-  const int NC = KP / kKC, KS = KP / 16;
-  const int brow = tid >> 3, kg = tid & 7;   // this thread builds rows brow and brow + 64, columns 8 kg .. 8 kg + 7 of a chunk
-  const rsrc_t rs_tab = make_rsrc(p.table, (unsigned)min((size_t)p.N * p.TC * 4, (size_t)0xFFFFFFFFu));
+  const int NC = KP / kChunkK, KS = KP / 16;
+  const BuildRows<4> b(p, L, tid, IS_M, (unsigned)min((size_t)p.N * p.TC * 4, (size_t)0xFFFFFFFFu));   // fp32 table
   const size_t wbytes = (size_t)(IS_M ? p.MP : p.WxP) * KP * 2;
   const rsrc_t rs_wh = make_rsrc(IS_M ? p.w2m : p.w2x, (unsigned)wbytes);
   const rsrc_t rs_wl = make_rsrc(IS_M ? p.w2m_lo : p.w2x_lo, (unsigned)wbytes);
-  const unsigned vdst0 = (unsigned)L.dst[brow] * (unsigned)p.TC * 4u + (unsigned)kg * 32u;
-  const unsigned vsrc0 = (unsigned)L.src[brow] * (unsigned)p.TC * 4u + (unsigned)kg * 32u;
-  const unsigned vdst1 = (unsigned)L.dst[brow + 64] * (unsigned)p.TC * 4u + (unsigned)kg * 32u;
-  const unsigned vsrc1 = (unsigned)L.src[brow + 64] * (unsigned)p.TC * 4u + (unsigned)kg * 32u;
-  const float d2r0 = L.d2[brow], d2r1 = L.d2[brow + 64];
-  const unsigned offP = (IS_M ? 2u * p.WxP : 0u) * 4u, offQ = (IS_M ? 2u * p.WxP + p.WmP : (unsigned)p.WxP) * 4u;   // fp32 table
-  char* slot0 = s_a1 + ((size_t)kg * kRPAD + brow) * 16;
+  char* slot0 = s_a1 + ((size_t)b.kg * kRowPad + b.brow) * 16;
   char* slot1 = slot0 + 64 * 16;
   const unsigned lane16 = lane * 16u;
-  const unsigned lds_a1 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)(s_a1 + ((size_t)hh * kRPAD + r) * 16);
+  const unsigned lds_a1 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)(s_a1 + ((size_t)hh * kRowPad + r) * 16);
   const int colblk0 = half * 8 + wave;   // this wave's 32-column block
   const unsigned w0 = (unsigned)colblk0 * KS * 1024u;
 
@@ -88,10 +81,10 @@ __global__ __launch_bounds__(kT, 2) void edge_x3_kernel(const EdgeParams p) {
 
   {  // chunk 0
     Unit u;
-    unit_load(u, rs_tab, vdst0, vsrc0, offP, offQ);
-    unit_finish_hilo(u, s_wd + kg * 8, d2r0, slot0, slot0 + kImg);
-    unit_load(u, rs_tab, vdst1, vsrc1, offP, offQ);
-    unit_finish_hilo(u, s_wd + kg * 8, d2r1, slot1, slot1 + kImg);
+    unit_load(u, b.tab, b.vdst0, b.vsrc0, b.offP, b.offQ);
+    unit_finish_hilo(u, s_wd + b.kg * 8, b.d2r0, slot0, slot0 + kImg);
+    unit_load(u, b.tab, b.vdst1, b.vsrc1, b.offP, b.offQ);
+    unit_finish_hilo(u, s_wd + b.kg * 8, b.d2r1, slot1, slot1 + kImg);
   }
   bf16x8 bh[4], bl[4];   // head / remainder weight fragments of the 4 k-steps of the current chunk
 #pragma unroll
@@ -107,18 +100,16 @@ __global__ __launch_bounds__(kT, 2) void edge_x3_kernel(const EdgeParams p) {
   auto mphase = [&](const int c, const bool last) {
     const unsigned abase = lds_a1 + (unsigned)(c & 1) * (unsigned)(2 * kImg);
     bf16x8 ah[4], al[4];
-#define LDS_RD(dst, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(abase), "n"(off))
-#define LDS_RD2(rb, off) LDS_RD(ah[rb], off); LDS_RD(al[rb], (off) + (int)kImg)
-#define LDS_WAIT(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
+#define LDS_RD2(rb, off) TILE_LDS_RD(ah[rb], abase, off); TILE_LDS_RD(al[rb], abase, (off) + (int)kImg)
     LDS_RD2(0, 0); LDS_RD2(1, 512); LDS_RD2(2, 1024); LDS_RD2(3, 1536);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
 #pragma unroll
       for (int rb = 0; rb < 4; ++rb) {
-        if (s < 3 || rb == 0) LDS_WAIT(6);
-        else if (rb == 1) LDS_WAIT(4);
-        else if (rb == 2) LDS_WAIT(2);
-        else LDS_WAIT(0);
+        if (s < 3 || rb == 0) TILE_LDS_WAIT(6);
+        else if (rb == 1) TILE_LDS_WAIT(4);
+        else if (rb == 2) TILE_LDS_WAIT(2);
+        else TILE_LDS_WAIT(0);
         asm volatile("" : "+v"(ah[rb]), "+v"(al[rb]));   // uses stay below the wait
         acc[rb][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[rb], bh[s], acc[rb][0], 0, 0, 0);
         acc[rb][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[rb], bl[s], acc[rb][0], 0, 0, 0);
@@ -134,25 +125,25 @@ __global__ __launch_bounds__(kT, 2) void edge_x3_kernel(const EdgeParams p) {
         bl[s] = ldbuf_bf16x8(rs_wl, lane16, w0 + ksn);
       }
     }
-#undef LDS_WAIT
 #undef LDS_RD2
-#undef LDS_RD
   };
   Unit ua0, ua1;
   auto vload = [&](const int cq) {   // fp32 table rows for the activations of chunk cq (clamped: a harmless repeat at the end)
     const int c = cq < NC ? cq : NC - 1;
-    const unsigned kb = (unsigned)c * kKC * 4u;
-    unit_load(ua0, rs_tab, vdst0, vsrc0, offP + kb, offQ + kb);
-    unit_load(ua1, rs_tab, vdst1, vsrc1, offP + kb, offQ + kb);
+    const unsigned kb = (unsigned)c * kChunkK * 4u;
+    unit_load(ua0, b.tab, b.vdst0, b.vsrc0, b.offP + kb, b.offQ + kb);
+    unit_load(ua1, b.tab, b.vdst1, b.vsrc1, b.offP + kb, b.offQ + kb);
   };
   auto vfinish = [&](const int c) {
     const size_t nbuf = (size_t)(c & 1) * (2 * kImg);
     __builtin_amdgcn_s_setprio(3);
-    unit_finish_hilo(ua0, s_wd + c * kKC + kg * 8, d2r0, slot0 + nbuf, slot0 + nbuf + kImg);
-    unit_finish_hilo(ua1, s_wd + c * kKC + kg * 8, d2r1, slot1 + nbuf, slot1 + nbuf + kImg);
+    unit_finish_hilo(ua0, s_wd + c * kChunkK + b.kg * 8, b.d2r0, slot0 + nbuf, slot0 + nbuf + kImg);
+    unit_finish_hilo(ua1, s_wd + c * kChunkK + b.kg * 8, b.d2r1, slot1 + nbuf, slot1 + nbuf + kImg);
     __builtin_amdgcn_s_setprio(0);
   };
-  // SIMD partners (waves w and w + 4) in opposite phase, one barrier per chunk (edge_bf16_v3.hip)
+  // SIMD partners (waves w and w + 4) in opposite phase, one barrier per chunk: phase_opposed_k_loop of edge_tile.h with the
+  // first request and the last matrix phase outside the wave branch -- through the shared form (each arm in full) hipcc
+  // schedules these kernels on 20 fewer registers and a step takes 0.4 % longer (profiles/edge_tile_refactor_ab.txt)
   vload(1);
   if (wave < 4) {
     for (int i = 0; i < NC - 1; ++i) {
@@ -199,8 +190,8 @@ bool edge_bf16x3_supported(const EdgeParams& p) {
 // coordinate kernel (WxP / 256 column shares per tile), then the message kernel
 int launch_edge_bf16x3(const EdgeParams& p, hipStream_t st) {
   const int tiles = (p.E + kR - 1) / kR;
-  hipLaunchKernelGGL(edge_x3_kernel<false>, dim3(tiles * (p.WxP / 256)), dim3(kT), x3_smem_bytes(p.WxP), st, p);
-  hipLaunchKernelGGL(edge_x3_kernel<true>, dim3(tiles), dim3(kT), x3_smem_bytes(p.WmP), st, p);
+  hipLaunchKernelGGL(edge_x3_kernel<false>, dim3(tiles * (p.WxP / 256)), dim3(kTileThreads), x3_smem_bytes(p.WxP), st, p);
+  hipLaunchKernelGGL(edge_x3_kernel<true>, dim3(tiles), dim3(kTileThreads), x3_smem_bytes(p.WmP), st, p);
   EGNN_HIP(hipGetLastError());
   return EGNN_OK;
 }

@@ -1,7 +1,9 @@
 // Bookkeeping shared by the 128-edge-tile bf16 edge kernels (gfx950): the LDS carve of the per-tile arrays, the tile
 // prologue (edge rows, geometry of EquivariantGraphNeuralNetwork.py:56, segment = receiving-node structure of the CSR
 // tile) and the coordinate branch's segment sums (:62-65, aggregate 'sum' of :70).  One implementation for every kernel
-// that works on such a tile; the K loops and the accumulator-layout-specific row reductions stay in the kernels.
+// that works on such a tile.  Also what the K loops of these kernels have in common: the chunk and thread constants, the
+// operand-read helpers, the build-thread setup (BuildRows), the phase-opposed chunk loop and the staged row-major store of
+// the training kernels.  The matrix phases and the accumulator-layout-specific row reductions stay in the kernels.
 #pragma once
 #include "kernels.h"
 
@@ -11,6 +13,11 @@ namespace tile128 {
 constexpr int kR = 128;         // edges per tile
 static_assert(kR == kTileRows, "plan_forward (host_logic.cpp) plans 128-edge tiles");
 constexpr int kSegFast = 8;     // segments (receiving nodes) per tile handled by the register path
+constexpr int kTileThreads = 512;   // 8 wave64 per workgroup
+constexpr int kChunkK = 64;         // depth of one activation chunk
+constexpr int kRowPad = kR + 1;     // rows of a k-group in the padded activation image
+constexpr size_t kChunkBytes = (size_t)8 * kRowPad * 16;   // one activation image [8 k-groups][129 rows][8 x 16-bit]
+constexpr size_t kStageBytes = (size_t)8 * 32 * 72 * 2;    // store staging (stage_store_rows): 8 waves x [32][72] bf16
 // LDS carve (bytes) of the per-tile arrays; the kernel's own K-loop buffers start at kOffLoop
 constexpr size_t kOffDst = 0;                                  // int[R]
 constexpr size_t kOffSrc = kOffDst + kR * 4;                   // int[R]
@@ -26,6 +33,11 @@ constexpr size_t kOffSegMode = kOffSegRe + kR * 4;             // int[R]
 constexpr size_t kOffMisc = kOffSegMode + kR * 4;              // int[16]
 constexpr size_t kOffGseg = kOffMisc + 64;                     // float[kSegFast][R]
 constexpr size_t kOffLoop = kOffGseg + kSegFast * kR * 4;
+
+// Operand reads of the matrix phases by inline asm, so that hipcc cannot sink them to their use.  LDS operations of a wave
+// return in order: lgkmcnt(n) before a use means "all but the n younger reads have landed".
+#define TILE_LDS_RD(dst, base, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(base), "n"(off))
+#define TILE_LDS_WAIT(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
 
 struct Lds {
   int *dst, *src, *seg_of_row, *seg_node, *seg_rs, *seg_re, *seg_mode, *misc;
@@ -113,6 +125,89 @@ __device__ __forceinline__ int prologue(const EdgeParams& p, const Lds& L, int e
   return prologue_segments(p, L, e0, nvalid, tid, lane, wave);
 }
 
+// What a build thread knows about its share of every activation chunk: it builds columns [8 kg, 8 kg + 8) of rows brow and
+// brow + 64.  v*: byte offsets of the two rows' receiving / sending node in the first-layer table at those columns, offP /
+// offQ: byte offsets of the branch's P and Q blocks in a table row {Px | Qx | Pm | Qm}, d2r*: the rows' squared distances,
+// tab: the table's descriptor.  ESZ = bytes per table element (2: fp16 table, 4: fp32 table).  The LDS slots stay with the
+// kernels (padded or swizzled images).  Read after the barrier that publishes L.dst / L.src / L.d2.
+template <int ESZ>
+struct BuildRows {
+  int brow, kg;
+  unsigned vdst0, vsrc0, vdst1, vsrc1, offP, offQ;
+  float d2r0, d2r1;
+  rsrc_t tab;
+  __device__ __forceinline__ unsigned row_off(const EdgeParams& p, int node) const {
+    return (unsigned)node * (unsigned)p.TC * (unsigned)ESZ + (unsigned)kg * (8u * ESZ);
+  }
+  // (d0, s0, d1, s1: the rows' node indices where the caller holds them in registers already)
+  __device__ __forceinline__ BuildRows(const EdgeParams& p, const Lds& L, int tid, bool is_m, unsigned table_bytes, int d0, int s0,
+                                       int d1, int s1)
+      : brow(tid >> 3), kg(tid & 7), vdst0(row_off(p, d0)), vsrc0(row_off(p, s0)), vdst1(row_off(p, d1)), vsrc1(row_off(p, s1)),
+        offP((is_m ? 2u * p.WxP : 0u) * ESZ), offQ((is_m ? 2u * p.WxP + p.WmP : (unsigned)p.WxP) * ESZ), d2r0(L.d2[brow]),
+        d2r1(L.d2[brow + 64]), tab(make_rsrc(p.table, table_bytes)) {}
+  __device__ __forceinline__ BuildRows(const EdgeParams& p, const Lds& L, int tid, bool is_m, unsigned table_bytes)
+      : brow(tid >> 3), kg(tid & 7), vdst0(row_off(p, L.dst[brow])), vsrc0(row_off(p, L.src[brow])),
+        vdst1(row_off(p, L.dst[brow + 64])), vsrc1(row_off(p, L.src[brow + 64])), offP((is_m ? 2u * p.WxP : 0u) * ESZ),
+        offQ((is_m ? 2u * p.WxP + p.WmP : (unsigned)p.WxP) * ESZ), d2r0(L.d2[brow]), d2r1(L.d2[brow + 64]),
+        tab(make_rsrc(p.table, table_bytes)) {}
+};
+
+// Chunk loop with the two waves of a SIMD (w and w + 4) in opposite phase: waves 0-3 multiply chunk c and then build chunk
+// c + 1, waves 4-7 build chunk c + 1 first and then multiply chunk c -- one wave's vector work runs under its partner's
+// matrix work instead of both alternating in lockstep.  One barrier per chunk either way.  The table rows are requested
+// again as soon as they have been consumed (for waves 0-3 that is ahead of the barrier: the vector-memory issue time then
+// overlaps the group's barrier wait).  The loop bodies are branch-free so that hipcc's waitcnt insertion can keep counted
+// vmcnt waits across the back edge.  Chunk 0 is built by the caller; mphase(c, last), vfinish(c), vload(c) (clamped by
+// the caller: c may be NC).  Ends behind a barrier.  Each arm is written out in full, first request and last matrix phase
+// included: with either outside the wave branch the two-block recompute kernel of edge_bf16_v3.hip spills 8 / 20 bytes more.
+// Who runs it: edge_bf16_v3.hip (one unit set; its two-set form is this loop unrolled by two, written there).  The same loop
+// with request and last phase outside the branch stays written out in edge_bf16x3.hip (through this form: +0.4 % per step,
+// 20 fewer registers, another schedule) and edge_x_m16.hip (segment modes in the wave < 4 arm; 256 registers):
+// profiles/edge_tile_refactor_ab.txt, profiles/edge_tile_refactor_resource_usage.txt.
+template <class MPhase, class VFinish, class VLoad>
+__device__ __forceinline__ void phase_opposed_k_loop(int NC, int wave, MPhase&& mphase, VFinish&& vfinish, VLoad&& vload) {
+  if (wave < 4) {
+    vload(1);
+    for (int i = 0; i < NC - 1; ++i) {
+      mphase(i, false);
+      vfinish(i + 1);
+      vload(i + 2);
+      __syncthreads();
+    }
+    mphase(NC - 1, true);
+    __syncthreads();
+  } else {
+    vload(1);
+    for (int i = 0; i < NC - 1; ++i) {
+      vfinish(i + 1);
+      vload(i + 2);
+      __builtin_amdgcn_sched_barrier(0);
+      mphase(i, false);
+      __syncthreads();
+    }
+    mphase(NC - 1, true);
+    __syncthreads();
+  }
+}
+
+// Training kernels: the wave's accumulators acc[rb][0 .. CB) (128 rows x 32 CB columns, CB <= 2) as row-major bf16 to `out`
+// (address of row 0 of the tile at the wave's first column, `ld` columns per row; rows >= nvalid are skipped), 16-byte
+// stores through the wave's [32][72] bf16 block of `stage` (kStageBytes of the K-loop buffers, free behind the loop's
+// last barrier).
+template <int CB>
+__device__ __forceinline__ void stage_store_rows(const f32x16 (&acc)[4][CB], char* stage, __bf16* out, size_t ld, int nvalid,
+                                                 int lane, int wave) {
+  static_assert(CB == 1 || CB == 2, "store_block_bf16 takes one or two 32-column blocks");
+  __bf16* stg = reinterpret_cast<__bf16*>(stage) + (size_t)wave * 32 * 72;
+#pragma unroll
+  for (int rb = 0; rb < 4; ++rb) {
+    f32x16 blk[2];
+    blk[0] = acc[rb][0];
+    blk[1] = acc[rb][CB - 1];
+    store_block_bf16(blk, CB, stg, out + (size_t)(32 * rb) * ld, ld, nvalid - 32 * rb, lane);
+  }
+}
+
 // Coordinate messages of the tile (:62-65): sum over each segment's rows of (x_i - x_j) * s_ij (L.val) into the node's /
 // the tile's slot of copy `half` of the coordinate sums; component 3 carries the segment's sum of |x_i - x_j|^2 (plain
 // squares: the Frobenius norm of :64 is the root of the sum over ALL edges), so the normaliser needs no edge pass of its
@@ -172,9 +267,13 @@ __device__ __forceinline__ void coordinate_segment_sums(const EdgeParams& p, con
 // Head of the coordinate branch (:62-63): L.val[row] = [b3 +] sum over this workgroup's columns of w3[n] SiLU(a2[row][n]),
 // the bias only in column share 0.  Ends behind a barrier (L.val ordered for every thread).
 // acc_scale: t2 = acc_scale * acc + b2 (-log2(e); the fp16 streams of precision f16c8 carry 2^8, divided out here)
-template <int CB>
+// PRE_SCALED: acc already holds t2 = -log2(e) * (a2 + b2) (the training forward stores it before this call).
+// STORE_SHARE (training forward): rows [e0, e0 + nvalid) of this column share of s_e also go to p.s_half_out (the backward's
+// dL/d(x_i - x_j) needs them).
+template <int CB, bool PRE_SCALED = false, bool STORE_SHARE = false>
 __device__ __forceinline__ void x_head(const EdgeParams& p, const Lds& L, const f32x16 (&acc)[4][CB], int colblk0, int half,
-                                       int tid, int lane, int wave, const float acc_scale = kNegLog2e) {
+                                       int tid, int lane, int wave, const float acc_scale = kNegLog2e, int e0 = 0,
+                                       int nvalid = 0) {
   const int r = lane & 31;
   float part[64];
 #pragma unroll
@@ -186,7 +285,8 @@ __device__ __forceinline__ void x_head(const EdgeParams& p, const Lds& L, const 
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) part[rb * 16 + i] = fmaf(w, silu_s(fmaf(acc[rb][cb][i], acc_scale, bb)), part[rb * 16 + i]);
+      for (int i = 0; i < 16; ++i)
+        part[rb * 16 + i] = fmaf(w, silu_s(PRE_SCALED ? acc[rb][cb][i] : fmaf(acc[rb][cb][i], acc_scale, bb)), part[rb * 16 + i]);
   }
   {
     float lo[32], hi[32];
@@ -203,6 +303,7 @@ __device__ __forceinline__ void x_head(const EdgeParams& p, const Lds& L, const 
 #pragma unroll
     for (int w = 0; w < 8; ++w) v += L.part[w * kR + tid];
     L.val[tid] = v;
+    if constexpr (STORE_SHARE) { if (tid < nvalid) p.s_half_out[(size_t)half * p.E + e0 + tid] = v; }
   }
   __syncthreads();
 }

@@ -1,4 +1,4 @@
-// Coordinate edge kernel on v_mfma_f32_16x16x32_bf16 (gfx950): the SAME workgroup tile as edge_kernel_bf16_v3<2, false>
+// Coordinate edge kernel on v_mfma_f32_16x16x32_bf16 (gfx950): the SAME workgroup tile as edge_kernel_bf16_v3<2, false, ...>
 // (128 edges x 512 columns of mlp_x.2, EquivariantGraphNeuralNetwork.py:19-25, :62-65; 8 waves, 128 rows x 64 columns per
 // wave, 64-deep activation chunks, phase-opposed SIMD partners, weight fragments streamed from L2), with the matrix
 // instruction's shape changed.  Why build it: the coordinate kernel runs against the power limit (held clock 1.9-2.1 GHz),
@@ -13,7 +13,10 @@
 //     slots of the 256-B load bank row (no padding: 16 KiB per chunk);
 //   * weight fragments packed [16-column block][32-deep k-step][lane][8 bf16] (pack_frags_bf16_n16);
 //   * the row sums of the head s = w3 . SiLU(a2) + b3 run over the 16 lanes of a DPP row (tile128::butterfly16).
-// Prologue and segment sums are the shared ones of edge_tile.h.
+// Holds the forward kernels for WxP = 512 and 1024 (per (tile, column share) unit and persistent, bf16 and fp16 operands)
+// and the training-forward kernel (bf16).  Prologue, build-thread setup (BuildRows), the operand-read helpers and the
+// segment sums are the shared ones of edge_tile.h; the chunk loop and the head are this kernel's own (16x16 accumulator
+// tiles, and 256 registers: see the notes at the loop).
 #include <cstdlib>
 
 #include "diag.h"
@@ -33,10 +36,10 @@ __device__ unsigned long long g_xwg_stamps[20000][12];
 #endif
 
 using namespace tile128;
-constexpr int kT = 512;
-constexpr int kKC = 64;                       // activation chunk depth
-constexpr size_t kA1 = (size_t)8 * kR * 16;   // one activation chunk: [8 k-groups][128 rows][8 bf16], XOR-swizzled rows
-__host__ __device__ inline size_t x16_smem_bytes(int KP) { return kOffLoop + 2 * kA1 + (size_t)KP * 4; }
+constexpr size_t kA1 = (size_t)8 * kR * 16;   // one activation chunk: [8 k-groups][128 rows][8 bf16], XOR-swizzled rows (no padding)
+__host__ __device__ constexpr size_t x16_smem_bytes(int KP) { return kOffLoop + 2 * kA1 + (size_t)KP * 4; }
+static_assert(x16_smem_bytes(256) == 48192 && x16_smem_bytes(512) == 49216 && x16_smem_bytes(1024) == 51264,
+              "LDS allocation of the 16x16x32 coordinate kernels");
 
 typedef __attribute__((ext_vector_type(4))) float f32x4v;
 
@@ -51,7 +54,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4v;
 // arithmetic, the matrix pipe idle): the three dependent memory round trips of the prologue (2.2 us of a 26 us workgroup,
 // profiles/r03t_fwd_wg_stamps.txt) and the dispatch gap between workgroups (0.3 us) leave the critical path.
 template <bool SAVE, typename V8 = bf16x8, bool PERSIST = false>
-__global__ __launch_bounds__(kT, 2) void edge_x_m16_kernel(const EdgeParams p) {
+__global__ __launch_bounds__(kTileThreads, 2) void edge_x_m16_kernel(const EdgeParams p) {
   static_assert(!(SAVE && OpTraits<V8>::f16), "the training forward keeps bf16 activations");
   static_assert(!(SAVE && PERSIST), "the persistent form is the inference kernel");
   if constexpr (OpTraits<V8>::f16) f16_saturate_mode();
@@ -65,8 +68,7 @@ __global__ __launch_bounds__(kT, 2) void edge_x_m16_kernel(const EdgeParams p) {
   const int r15 = lane & 15, q4 = lane >> 4;
   const int KP = p.WxP;
   const int nsplit = p.WxP / 512;
-  const int NC = KP / kKC, KS = KP / 32;
-  const int brow = tid >> 3, kg = tid & 7;   // this thread builds rows brow and brow + 64, columns 8 kg .. 8 kg + 7 of a chunk
+  const int NC = KP / kChunkK, KS = KP / 32;
   const rsrc_t rs_tab = make_rsrc(p.table, diag::drop_table_loads(p.dbg) ? 0u : (unsigned)((size_t)p.N * p.TC * 2));
   const rsrc_t rs_w = make_rsrc(p.w2x, diag::drop_weight_loads(p.dbg) ? 0u : (unsigned)((size_t)p.WxP * KP * 2));
   const unsigned offP = 0u, offQ = (unsigned)p.WxP * 2u;   // fp16 table: {Px | Qx | Pm | Qm}
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(kT, 2) void edge_x_m16_kernel(const EdgeParams p) {
       for (int cb = 0; cb < 4; ++cb) bq[s][cb] = ldbuf_v8<V8>(rs_w, l16, nw0 + ((unsigned)cb * KS + s) * 1024u);
   };
   if constexpr (PERSIST) {
-    for (int i = tid; i < KP; i += kT) s_wd[i] = p.wdx[i];   // (ordered by the first unit's row barrier)
+    for (int i = tid; i < KP; i += kTileThreads) s_wd[i] = p.wdx[i];   // (ordered by the first unit's row barrier)
     prefetch_indices(blockIdx.x, tid);
     prefetch_data(blockIdx.x, tid);
   }
@@ -149,12 +151,10 @@ __global__ __launch_bounds__(kT, 2) void edge_x_m16_kernel(const EdgeParams p) {
   WG_STAMP(1);
 
   // ---- K loop ----
-  const unsigned vdst0 = (unsigned)(PERSIST ? pf_d0 : L.dst[brow]) * (unsigned)p.TC * 2u + (unsigned)kg * 16u;
-  const unsigned vsrc0 = (unsigned)(PERSIST ? pf_s0 : L.src[brow]) * (unsigned)p.TC * 2u + (unsigned)kg * 16u;
-  const unsigned vdst1 = (unsigned)(PERSIST ? pf_d1 : L.dst[brow + 64]) * (unsigned)p.TC * 2u + (unsigned)kg * 16u;
-  const unsigned vsrc1 = (unsigned)(PERSIST ? pf_s1 : L.src[brow + 64]) * (unsigned)p.TC * 2u + (unsigned)kg * 16u;
-  const float d2r0 = L.d2[brow], d2r1 = L.d2[brow + 64];
-  char* slot0 = s_a1 + (size_t)kg * (kR * 16) + (size_t)(brow ^ kg) * 16;
+  const BuildRows<2> b(p, L, tid, false, diag::drop_table_loads(p.dbg) ? 0u : (unsigned)((size_t)p.N * p.TC * 2),
+                       PERSIST ? pf_d0 : L.dst[tid >> 3], PERSIST ? pf_s0 : L.src[tid >> 3], PERSIST ? pf_d1 : L.dst[(tid >> 3) + 64],
+                       PERSIST ? pf_s1 : L.src[(tid >> 3) + 64]);   // (PERSIST: the indices are in registers already)
+  char* slot0 = s_a1 + (size_t)b.kg * (kR * 16) + (size_t)(b.brow ^ b.kg) * 16;
   char* slot1 = slot0 + 64 * 16;
   // LDS byte address of this lane's operand piece in buffer 0 for the two k-steps of a chunk (k-groups q4 and 4 + q4)
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)s_a1;
@@ -177,11 +177,11 @@ __global__ __launch_bounds__(kT, 2) void edge_x_m16_kernel(const EdgeParams p) {
   // rows past the edge list fall outside the descriptor and are dropped by the hardware.  Flat 64-bit addresses cost the
   // four registers that made hipcc spill 20 bytes per lane around the K loop.)
   const rsrc_t rs_s1 = make_rsrc(SAVE ? p.s1_out : nullptr, SAVE ? (unsigned)((size_t)p.E * KP * 2) : 0u);   // < 4 GiB: checked by the host
-  const unsigned vs1_0 = (unsigned)(e0 + brow) * (unsigned)KP * 2u + (unsigned)kg * 16u, vs1_1 = vs1_0 + 64u * (unsigned)KP * 2u;
+  const unsigned vs1_0 = (unsigned)(e0 + b.brow) * (unsigned)KP * 2u + (unsigned)b.kg * 16u, vs1_1 = vs1_0 + 64u * (unsigned)KP * 2u;
   auto s1_store = [&](const V8 o0, const V8 o1, const int c) {
     if (half != 0) return;
     if constexpr (diag::kNoS1) return;
-    const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)c * kKC * 2u);
+    const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)c * kChunkK * 2u);
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o0), rs_s1, vs1_0, soff, 0);
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), rs_s1, vs1_1, soff, 0);
   };
@@ -189,8 +189,8 @@ __global__ __launch_bounds__(kT, 2) void edge_x_m16_kernel(const EdgeParams p) {
   // worked out (two barriers, waves 0 and 1 only) while they are in flight, then the activations are finished
   // (one row after the other and the segment structure in front of them: 2.3 us per 27 us workgroup, tools/fwd_stamps.py)
   if constexpr (!PERSIST) {
-    unith_load(uc0, rs_tab, vdst0, vsrc0, offP, offQ);
-    unith_load(uc1, rs_tab, vdst1, vsrc1, offP, offQ);
+    unith_load(uc0, b.tab, b.vdst0, b.vsrc0, b.offP, b.offQ);
+    unith_load(uc1, b.tab, b.vdst1, b.vsrc1, b.offP, b.offQ);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -206,8 +206,8 @@ __global__ __launch_bounds__(kT, 2) void edge_x_m16_kernel(const EdgeParams p) {
     }
   }
   {
-    const V8 o0 = unith_finish<V8>(uc0, s_wd + kg * 8, d2r0, slot0);
-    const V8 o1 = unith_finish<V8>(uc1, s_wd + kg * 8, d2r1, slot1);
+    const V8 o0 = unith_finish<V8>(uc0, s_wd + b.kg * 8, b.d2r0, slot0);
+    const V8 o1 = unith_finish<V8>(uc1, s_wd + b.kg * 8, b.d2r1, slot1);
     if constexpr (SAVE) s1_store(o0, o1, 0);
   }
   __syncthreads();
@@ -222,17 +222,15 @@ __global__ __launch_bounds__(kT, 2) void edge_x_m16_kernel(const EdgeParams p) {
     const unsigned ab0 = abase0 + boff, ab1 = abase1 + boff;
     V8 a[3];   // ring of 3 operand pieces: use u = 8 s + rb takes a[u % 3], which is refilled for use u + 3 right after
                    // (a fourth set costs the 4 registers that made hipcc spill around the K loop: 63 MB of scratch traffic per launch)
-#define LDS_RD(dst, base, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(base), "n"(off))
-#define LDS_WAIT(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
-    LDS_RD(a[0], ab0, 0); LDS_RD(a[1], ab0, 256); LDS_RD(a[2], ab0, 512);
+    TILE_LDS_RD(a[0], ab0, 0); TILE_LDS_RD(a[1], ab0, 256); TILE_LDS_RD(a[2], ab0, 512);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
 #pragma unroll
       for (int rb = 0; rb < 8; ++rb) {
         const int u = 8 * s + rb;
-        if (u <= 13) LDS_WAIT(2);
-        else if (u == 14) LDS_WAIT(1);
-        else LDS_WAIT(0);
+        if (u <= 13) TILE_LDS_WAIT(2);
+        else if (u == 14) TILE_LDS_WAIT(1);
+        else TILE_LDS_WAIT(0);
         asm volatile("" : "+v"(a[u % 3]));   // uses of the piece stay below the wait
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
@@ -241,11 +239,11 @@ __global__ __launch_bounds__(kT, 2) void edge_x_m16_kernel(const EdgeParams p) {
         __builtin_amdgcn_sched_barrier(0);
 #endif
         // refill in place for use u + 3 (the MFMAs above have read the registers at issue): row block (u + 3) & 7 of k-step (u + 3) >> 3
-        if (u == 0) LDS_RD(a[0], ab0, 768); if (u == 1) LDS_RD(a[1], ab0, 1024); if (u == 2) LDS_RD(a[2], ab0, 1280);
-        if (u == 3) LDS_RD(a[0], ab0, 1536); if (u == 4) LDS_RD(a[1], ab0, 1792); if (u == 5) LDS_RD(a[2], ab1, 0);
-        if (u == 6) LDS_RD(a[0], ab1, 256); if (u == 7) LDS_RD(a[1], ab1, 512); if (u == 8) LDS_RD(a[2], ab1, 768);
-        if (u == 9) LDS_RD(a[0], ab1, 1024); if (u == 10) LDS_RD(a[1], ab1, 1280); if (u == 11) LDS_RD(a[2], ab1, 1536);
-        if (u == 12) LDS_RD(a[0], ab1, 1792);
+        if (u == 0) TILE_LDS_RD(a[0], ab0, 768); if (u == 1) TILE_LDS_RD(a[1], ab0, 1024); if (u == 2) TILE_LDS_RD(a[2], ab0, 1280);
+        if (u == 3) TILE_LDS_RD(a[0], ab0, 1536); if (u == 4) TILE_LDS_RD(a[1], ab0, 1792); if (u == 5) TILE_LDS_RD(a[2], ab1, 0);
+        if (u == 6) TILE_LDS_RD(a[0], ab1, 256); if (u == 7) TILE_LDS_RD(a[1], ab1, 512); if (u == 8) TILE_LDS_RD(a[2], ab1, 768);
+        if (u == 9) TILE_LDS_RD(a[0], ab1, 1024); if (u == 10) TILE_LDS_RD(a[1], ab1, 1280); if (u == 11) TILE_LDS_RD(a[2], ab1, 1536);
+        if (u == 12) TILE_LDS_RD(a[0], ab1, 1792);
       }
       if (!last) {
         const unsigned ksn = (unsigned)((c + 1) * 2 + s) * 1024u;
@@ -253,25 +251,26 @@ __global__ __launch_bounds__(kT, 2) void edge_x_m16_kernel(const EdgeParams p) {
         for (int cb = 0; cb < 4; ++cb) bq[s][cb] = ldbuf_v8<V8>(rs_w, lane16, w0 + (unsigned)cb * KS * 1024u + ksn);
       }
     }
-#undef LDS_WAIT
-#undef LDS_RD
   };
   UnitH ua0, ua1;
   auto vload = [&](const int cq) {   // table rows for the activations of chunk cq (clamped: a harmless repeat at the end)
     const int c = cq < NC ? cq : NC - 1;
-    const unsigned kb = (unsigned)c * kKC * 2u;
-    unith_load(ua0, rs_tab, vdst0, vsrc0, offP + kb, offQ + kb);
-    unith_load(ua1, rs_tab, vdst1, vsrc1, offP + kb, offQ + kb);
+    const unsigned kb = (unsigned)c * kChunkK * 2u;
+    unith_load(ua0, b.tab, b.vdst0, b.vsrc0, b.offP + kb, b.offQ + kb);
+    unith_load(ua1, b.tab, b.vdst1, b.vsrc1, b.offP + kb, b.offQ + kb);
   };
   auto vfinish = [&](const int c) {  // SiLU + bf16 pack of chunk c into its LDS buffer
     const size_t nbuf = (size_t)(c & 1) * kA1;
     __builtin_amdgcn_s_setprio(3);   // vector work wins issue arbitration over the partner wave's MFMAs
-    const V8 o0 = unith_finish<V8>(ua0, s_wd + c * kKC + kg * 8, d2r0, slot0 + nbuf);
-    const V8 o1 = unith_finish<V8>(ua1, s_wd + c * kKC + kg * 8, d2r1, slot1 + nbuf);
+    const V8 o0 = unith_finish<V8>(ua0, s_wd + c * kChunkK + b.kg * 8, b.d2r0, slot0 + nbuf);
+    const V8 o1 = unith_finish<V8>(ua1, s_wd + c * kChunkK + b.kg * 8, b.d2r1, slot1 + nbuf);
     __builtin_amdgcn_s_setprio(0);
     if constexpr (SAVE) s1_store(o0, o1, c);
   };
-  // SIMD partners (waves w and w + 4) in opposite phase, one barrier per chunk (edge_bf16_v3.hip)
+  // SIMD partners (waves w and w + 4) in opposite phase, one barrier per chunk: phase_opposed_k_loop of edge_tile.h, written
+  // out here because the segment modes ride in the wave < 4 arm -- through the shared loop (their loads folded into the
+  // matrix-phase hook) the training-forward kernel spills 32 bytes per lane at its 256 registers, and with request and last
+  // phase outside the branch a bf16 step takes 0.14 % longer (profiles/edge_tile_refactor_ab.txt).
   DIAG_STAMP(30, 2);   // chunk 0 built, first weights requested
   WG_STAMP(2);
   DIAG_RSTAMP(31, 1);
@@ -454,15 +453,15 @@ int launch_edge_x_m16(const EdgeParams& p, hipStream_t st, bool f16, XForm form,
   switch (form) {
     case XForm::kSave:
       if (f16) { set_error("edge_x_m16: the training forward runs on bf16 operands"); return EGNN_EINVAL; }
-      hipLaunchKernelGGL(edge_x_m16_kernel<true>, dim3(units), dim3(kT), sm, st, q);
+      hipLaunchKernelGGL(edge_x_m16_kernel<true>, dim3(units), dim3(kTileThreads), sm, st, q);
       break;
     case XForm::kPersistent:
-      if (f16) hipLaunchKernelGGL((edge_x_m16_kernel<false, f16x8, true>), dim3(grid), dim3(kT), sm, st, q);
-      else hipLaunchKernelGGL((edge_x_m16_kernel<false, bf16x8, true>), dim3(grid), dim3(kT), sm, st, q);
+      if (f16) hipLaunchKernelGGL((edge_x_m16_kernel<false, f16x8, true>), dim3(grid), dim3(kTileThreads), sm, st, q);
+      else hipLaunchKernelGGL((edge_x_m16_kernel<false, bf16x8, true>), dim3(grid), dim3(kTileThreads), sm, st, q);
       break;
     case XForm::kPerUnit:
-      if (f16) hipLaunchKernelGGL((edge_x_m16_kernel<false, f16x8>), dim3(units), dim3(kT), sm, st, q);
-      else hipLaunchKernelGGL(edge_x_m16_kernel<false>, dim3(units), dim3(kT), sm, st, q);
+      if (f16) hipLaunchKernelGGL((edge_x_m16_kernel<false, f16x8>), dim3(units), dim3(kTileThreads), sm, st, q);
+      else hipLaunchKernelGGL(edge_x_m16_kernel<false>, dim3(units), dim3(kTileThreads), sm, st, q);
       break;
   }
   EGNN_HIP(hipGetLastError());

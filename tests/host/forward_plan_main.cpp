@@ -32,8 +32,9 @@ KernelSupport support(const ModelDims& d, int H, bool packed) {
   KernelSupport s;
   if (!packed) return s;
   const bool w3 = d.WxP == 256 || d.WxP == 512 || d.WxP == 1024, w2 = d.WxP == 512 || d.WxP == 1024, m = d.MP == 256;
-  s.v3 = s.bf16x3 = w3 && m && d.WmP % 64 == 0;                    // edge_bf16_v3.hip, edge_bf16x3.hip
-  s.v4 = s.v3 && d.WmP >= 192;                                     // edge_bf16_v4.hip
+  s.v3 = w3;                                                       // edge_bf16_v3.hip: the coordinate kernels' own widths
+  s.v4 = m && d.WmP % 64 == 0 && d.WmP >= 192;                     // edge_bf16_v4.hip: the message kernels' own widths
+  s.bf16x3 = w3 && m && d.WmP % 64 == 0;                           // edge_bf16x3.hip: both branches
   s.x_m16 = w2;                                                    // edge_x_m16.hip
   s.small = w2 && m && d.WmP % 128 == 0 && d.WmP >= 256;           // edge_small.hip
   s.f16c8w = w2 && m && d.WmP % 128 == 0 && d.WmP >= 128;          // edge_f16c8w.hip
@@ -297,6 +298,56 @@ void golden_shapes() {
   }
 }
 
+// edge_bf16_v3_supported / edge_bf16_v4_supported used to test each other's widths and LDS sizes; each now states the
+// conditions of its own kernel.  Nothing reads one without the other (plan_forward: v4 && v3, v4 && x_m16;
+// backward_recompute_supported: v4 && v3), so what must hold is that those conjunctions answer as before on every shape.
+// Both forms restated here with the kernels' LDS formulas (edge_tile.h: 14,400 bytes of per-tile arrays, 16,512-byte
+// activation chunks, 36,864 bytes of store staging); the formulas themselves are pinned by static_asserts next to them.
+void predicate_conjunctions() {
+  struct P { int WxP, WmP, MP; bool w2x, w2m, w2x16; size_t N, TC; };
+  const size_t kLoop = 14400, kChunk = 16512, kStage = 36864, kLds = 160 * 1024;
+  const auto v3_smem = [=](int KP) { const size_t loop = 2 * kChunk + (size_t)KP * 4; return kLoop + (kStage > loop ? kStage : loop); };
+  const auto v4_smem = [=](int KP) { return kLoop + 3 * kChunk + (size_t)KP * 4; };
+  const auto x16_smem = [=](int KP) { return kLoop + 2 * (size_t)16384 + (size_t)KP * 4; };
+  const auto w3 = [](int WxP) { return WxP == 256 || WxP == 512 || WxP == 1024; };
+  const auto table_ok = [](const P& p) { return p.N * p.TC * 4 < ((size_t)1 << 32); };
+  const auto old_v3 = [&](const P& p) {
+    return w3(p.WxP) && p.MP == 256 && p.WmP % 64 == 0 && p.w2x && v3_smem(p.WmP) <= kLds && v3_smem(p.WxP) <= kLds && table_ok(p);
+  };
+  const auto old_v4 = [&](const P& p) {
+    return w3(p.WxP) && p.MP == 256 && p.WmP % 64 == 0 && p.WmP >= 192 && p.w2m && v4_smem(p.WmP) <= kLds && v4_smem(p.WxP) <= kLds &&
+           table_ok(p);
+  };
+  const auto new_v3 = [&](const P& p) { return w3(p.WxP) && p.w2x && v3_smem(p.WxP) <= kLds && table_ok(p); };
+  const auto new_v4 = [&](const P& p) {
+    return p.MP == 256 && p.WmP % 64 == 0 && p.WmP >= 192 && p.w2m && v4_smem(p.WmP) <= kLds && table_ok(p);
+  };
+  const auto x_m16 = [&](const P& p) { return (p.WxP == 512 || p.WxP == 1024) && p.w2x16 && x16_smem(p.WxP) <= kLds && p.N * p.TC * 2 < ((size_t)1 << 32); };
+  // the allocations the launchers ask for, as on the parent (staged coordinate kernels; the plain forward at 256: 48,448)
+  const int kps[] = {256, 512, 1024};
+  const size_t want_v3[] = {51264, 51264, 51520}, want_v4[] = {64960, 65984, 68032};
+  for (int i = 0; i < 3; ++i) {
+    ++g_cases;
+    if (v3_smem(kps[i]) != want_v3[i] || v4_smem(kps[i]) != want_v4[i]) { printf("FAILED smem bytes at KP = %d\n", kps[i]); ++g_failed; }
+  }
+  const int wx[] = {64, 128, 256, 512, 1024}, wm[] = {64, 128, 192, 256, 320}, mp[] = {128, 256};
+  for (int WxP : wx)
+    for (int WmP : wm)
+      for (int MP : mp)
+        for (int streams = 0; streams < 8; ++streams)      // every combination of present / null weight streams
+          for (int big = 0; big < 2; ++big) {              // a first-layer table inside / past the 4 GiB the row offsets reach
+            ++g_cases;
+            P p{WxP, WmP, MP, (streams & 1) != 0, (streams & 2) != 0, (streams & 4) != 0, big ? (size_t)1 << 20 : (size_t)128,
+                (size_t)(2 * WxP + 2 * WmP)};
+            const bool o3 = old_v3(p), o4 = old_v4(p), n3 = new_v3(p), n4 = new_v4(p), xm = x_m16(p);
+            if ((o3 && o4) != (n3 && n4) || (o4 && xm) != (n4 && xm)) {
+              printf("FAILED predicates WxP %d WmP %d MP %d streams %d big %d: v4 && v3 %d -> %d, v4 && x_m16 %d -> %d\n", WxP, WmP, MP,
+                     streams, big, o3 && o4, n3 && n4, o4 && xm, n4 && xm);
+              ++g_failed;
+            }
+          }
+}
+
 }  // namespace
 
 int main() {
@@ -306,6 +357,7 @@ int main() {
   node_kernels();
   sq_sources();
   golden_shapes();
+  predicate_conjunctions();
   // the helpers the launcher shares with the planner
   if (path_of_precision(EGNN_PREC_F16C8) != EdgePath::kF16c8 || path_of_precision(EGNN_PREC_F32) != EdgePath::kGeneric ||
       node_pre_form(true, 2016, 36, 4096) != NodePre::kHilo2 || node_pre_form(true, 2017, 36, 4096) != NodePre::kHilo8 ||

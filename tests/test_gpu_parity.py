@@ -138,7 +138,7 @@ def test_f16c8_saturates_instead_of_overflowing():
 FP16_TOL = 2.5e-3
 @pytest.mark.parametrize("tag", EGNN_CASES)
 def test_egnn_fp16_against_reference_golden(tag):
-    """Full-width cases run the fp16-operand kernels (edge_x_m16_kernel<false, f16x8>, edge_kernel_bf16_v4<..., f16x8>,
+    """Full-width cases run the fp16-operand kernels (edge_x_m16_kernel<false, f16x8>, edge_kernel_bf16_v4<1, true, false, false, f16x8>,
     node_post_bf16_kernel<., f16x8>); the other widths fall to the exact fp32 kernels (include/egnn_amd.h EGNN_PREC_F16)."""
     sd, h, x, sizes, layers, d = golden_case(G_EGNN, tag)
     net = build_net(sd, d, len(layers), precision="fp16")
@@ -347,8 +347,9 @@ def test_graph_permutation_seed_is_fp32_reassociation(precision):
 
 @pytest.mark.parametrize("precision,tol", [("fp32", 1e-4), ("bf16x3", 1e-4), ("f16c8", 1e-4), ("bf16", 3e-2), ("fp16", 3e-3)])
 def test_full_size_c3_properties(precision, tol):
-    """BASELINE configs[2] size at FULL width (32 graphs x 512 atoms, E = 8,372,224, L=4, widths 1024/256: the
-    edge_kernel_bf16_v3<2,false> / <1,true> kernels on degree-511 rows, 4 tiles per receiving node): E(3)
+    """BASELINE configs[2] size at FULL width (32 graphs x 512 atoms, E = 8,372,224, L=4, widths 1024/256: for bf16
+    the persistent edge_x_m16_kernel<false, bf16x8, true> and edge_kernel_bf16_v4<1, true> on degree-511 rows, 4 tiles per
+    receiving node): E(3)
     equivariance, graph-permutation equivariance, run-to-run bitwise determinism, and one whole 512-atom graph
     against the oracle (261,632 edges x 4 layers on the CPU)."""
     B, n = 32, 512

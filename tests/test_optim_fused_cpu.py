@@ -158,5 +158,5 @@ def test_measurement_fingerprints_are_unchanged():
     assert _lib.training_sources_sha256() == tj["training_sources_sha256"]
     tj = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
     assert _lib.edge_kernel_sources_sha256() == tj["edge_kernel_sources_sha256"]
-    head = open(os.path.join(ROOT, "profiles", "r08a_prec_errors.log")).readline()
+    head = open(os.path.join(ROOT, "profiles", "r09a_prec_errors.log")).readline()
     assert head.split("forward_sources_sha256=")[-1].split()[0] == _lib.forward_sources_sha256()

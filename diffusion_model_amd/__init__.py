@@ -5,9 +5,10 @@ declared in include/egnn_amd.h."""
 from .egnn import EGCL, EquivariantGNN  # noqa: F401
 from .diffusion import E3DiffusionProcess, E3DiffusionProcessLegacy, E3DiffusionProcessXOnly, remove_mean  # noqa: F401
 from .graph import GraphPlan, fully_connected_edge_index, fully_connected_plan, plan_edge_index, radius_plan  # noqa: F401
-from . import cells, partition, stats  # noqa: F401
+from . import cells, partition, soap, stats  # noqa: F401
 from .cells import PeriodicCell, bond_list, lattice_from_parameters, local_environments  # noqa: F401
 from .partition import PartitionedSampler  # noqa: F401
+from .soap import SoapBasis, nearest_spectra, soap_descriptors, soap_similarity, template_matching  # noqa: F401
 from .optim import FusedAdam, FusedAdamW, FusedRAdamScheduleFree, RAdamScheduleFree, define_optimizer  # noqa: F401
 from .sampler import DeviceSampler, generate  # noqa: F401
 from .preprocessor import SpectrumCompressor  # noqa: F401

@@ -560,6 +560,54 @@ int egnn_topo_host(int B, int A, const float* pos, const int32_t* type, const in
                    int32_t* row_ptr, int32_t* neighbours, int32_t* degree, int32_t* overflow, uint16_t* dist, int32_t* component,
                    int32_t* fragments, int32_t* fp, int n_pairs, const int32_t* pairs, double* sim, int64_t* sa, int64_t* sb);
 
+/* ---- SOAP descriptors and spectrum template matching (csrc/eval/soap.hip; definitions in csrc/eval/soap_math.h) -------------
+ * template_matching.py:41-68 finds, for every target record, the three reference records with the nearest XANES spectrum (MSE of
+ * spectrum[0]) and reports the cosine similarity of dscribe's SOAP power spectrum of atom 0.  These entries restate it for a ragged
+ * batch without ASE or dscribe, from the descriptor's definition (soap_math.h states every formula and every summation order).
+ * Atoms and graphs as in the topo block: d_type int32 [N] in [0, A), A <= 4, d_graph_ptr int32 [B+1] over N atoms; species order
+ * is type order.  The tables (K, gamma, beta, the harmonic norms and the l weights: egnn_soap_table_doubles(n_max, l_max) doubles in
+ * the layout of soap_math.h) are built by the caller ONCE per configuration, exactly (the package: SoapBasis, mpmath at 60 digits).
+ * No kernel has an atomic: a repeated call is bitwise reproducible.  Bad arguments (A > 4, n_max outside [1, 16], l_max outside
+ * [0, 10], k outside [1, 8], a cut that is not positive and finite, a centre outside [0, N), a required pointer NULL) return
+ * EGNN_EINVAL before anything is launched; a kernel ignores a type outside [0, A) (the atom contributes nothing).
+ *
+ * egnn_soap_features: F = (A n(n+1)/2 + A(A-1)/2 n^2)(l_max+1), 5,115 at A = 2, n_max = 15, l_max = 10; EGNN_EINVAL outside the limits. */
+int egnn_soap_features(int A, int n_max, int l_max);
+int egnn_soap_table_doubles(int n_max, int l_max);
+/* egnn_soap_descriptor: one workgroup per centre.  centres is a HOST list int32 [n_centres] of atom indices counted over the batch,
+ * in any order, repeats allowed (it is checked against N here), d_centres the same list on the device.  Neighbours of a centre are
+ * the atoms of its graph with d2 < neighbour_cut^2, the centre included.
+ *   d_desc double [n_centres, F]:                         the power spectrum, (Z1 <= Z2) outermost, then n, n' (n' >= n where Z1 = Z2), l innermost;
+ *   d_coeff double [n_centres, A, n_max, (l_max+1)^2]:    the orthonormalised coefficients c[Z][n][l*l + l + m], or NULL.
+ * Dynamic LDS: (A n_max (l_max+1)^2 + 32 ((l_max+1)^2 + n_max (l_max+1) + 4)) * 8 + 128 bytes, 136 KiB at the limits. */
+int egnn_soap_descriptor(void* stream, int B, int N, int A, const float* d_pos, const int32_t* d_type, const int32_t* d_graph_ptr,
+                         int n_max, int l_max, double neighbour_cut, const double* d_tables, int n_centres, const int32_t* centres,
+                         const int32_t* d_centres, double* d_desc, double* d_coeff);
+/* egnn_soap_cosine: pair p compares row d_pairs[2p] of d_a [rows_a, F] with row d_pairs[2p+1] of d_b [rows_b, F] (d_pairs int32
+ * [n_pairs, 2]; NULL = row p with row p): d_cos double [n_pairs] = dot / (sqrt(sum a^2) sqrt(sum b^2)), every sum in the one order
+ * of soap_math.h.  A pair that names no row gets NaN. */
+int egnn_soap_cosine(void* stream, int n_pairs, int F, const double* d_a, int rows_a, const double* d_b, int rows_b,
+                     const int32_t* d_pairs, double* d_cos);
+/* egnn_soap_gram: d_gram double [rows_a, rows_b], every entry the value egnn_soap_cosine gives for that pair (bitwise); d_norms is a
+ * workspace double [rows_a + rows_b] that receives the squared norms, computed once per row. */
+int egnn_soap_gram(void* stream, int F, const double* d_a, int rows_a, const double* d_b, int rows_b, double* d_norms, double* d_gram);
+/* egnn_spectrum_nearest: d_target float [T, S], d_reference float [R, S] -> for every target the k <= 8 references of smallest
+ * mse = (sum_s ((double)t_s - (double)r_s)^2) / S, ascending, ties to the lower index: d_idx int32 [T, k], d_mse double [T, k]
+ * (bitwise the host statement's); missing entries are index -1, mse +inf.  A reference whose group (d_reference_group int32 [R])
+ * equals the target's (d_target_group int32 [T]) is skipped; a group < 0 matches nothing; both NULL = no exclusion.  One wavefront
+ * per target streams the references: the [T, R] matrix is never stored. */
+int egnn_spectrum_nearest(void* stream, int T, int R, int S, int k, const float* d_target, const float* d_reference,
+                          const int32_t* d_target_group, const int32_t* d_reference_group, int32_t* d_idx, double* d_mse);
+/* Host statement of the four entries above: HOST pointers, no GPU, the same definitions in plain C++.  Three parts, each skipped
+ * where its count is 0: descriptors (n_centres > 0); cosines of the pairs and / or the whole matrix gram [n_a, n_b] of rows_a
+ * [n_a, F] and rows_b [n_b, F] (n_pairs > 0 or gram given); nearest spectra (T > 0).  Also EGNN_EINVAL: a type outside [0, A), a
+ * graph_ptr that does not run from 0 to N, a pair that names no row. */
+int egnn_soap_host(int B, int N, int A, const float* pos, const int32_t* type, const int32_t* graph_ptr, int n_max, int l_max,
+                   double neighbour_cut, const double* tables, int n_centres, const int32_t* centres, double* desc, double* coeff, int F,
+                   const double* rows_a, int n_a, const double* rows_b, int n_b, int n_pairs, const int32_t* pairs, double* cosine,
+                   double* gram, int T, int R, int S, int k, const float* target, const float* reference, const int32_t* target_group,
+                   const int32_t* reference_group, int32_t* idx, double* mse);
+
 /* ---- local environments of periodic cells (csrc/cells/cell_env.hip; definitions in csrc/cells/cell_math.h) ---------------
  * Every record of the reference is a local environment cut out of a periodic cell: make_dataset.py:79-142 builds the 3x3x3
  * supercell (:79-92), its full distance matrix (:99), takes the sites closer than 2.0 A to the excited oxygen

@@ -1,0 +1,62 @@
+"""Measure the error of the SOAP power spectrum against the mpmath truth (tests/golden/soap_golden.npz) and write it next to its
+bars: E = max |p - p_truth| / max |p_truth| per configuration, the largest over A = 1, 2, 3 atom types.
+
+  host     egnn_soap_host on the golden's centres: E_host, which must stay below 1e-7 (the condition that tells exact tables from
+           float64 ones: those land between 4e-5 and 2e-2);
+  device   egnn_soap_descriptor on the same centres, where a GPU is visible: its bar is 8 E_host.  Without a GPU the device
+           entries of an existing record are kept as they are.
+
+  python tools/soap_accuracy.py                   # -> profiles/soap_accuracy.json
+"""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    import numpy as np
+    import torch
+    from diffusion_model_amd import soap
+    from tests import _soap_util as SU
+    CAP, G, _host = SU.CAP, SU.golden(), SU.host_on_golden
+    out = os.path.join(ROOT, "profiles", "soap_accuracy.json")
+    old = json.load(open(out)) if os.path.exists(out) else {}
+    gpu = torch.cuda.is_available()
+    record = {"truth": "tests/golden/soap_golden.npz (mpmath, 60 digits)", "measure": "max |p - p_truth| / max |p_truth|, largest over A = 1, 2, 3",
+              "host_cap": CAP, "device_bar": "8 x host", "configurations": {}}
+    for name, cfg in SU.CONFIGS.items():
+        rec = dict(cfg, graphs=SU.SIZES[:SU.GOLDEN_GRAPHS[name]], centres="atom 0 of every graph" if name == "default" else "every atom")
+        host, device, coeff_host, coeff_device = [], [], None, None
+        for A in SU.TYPES:
+            truth = G[f"{name}_A{A}_desc"]
+            desc, coeff = _host(name, A)
+            host.append(SU.descriptor_error(desc, truth))
+            if A == 2:
+                coeff_host = SU.descriptor_error(coeff, G[f"{name}_A2_coeff"])
+            if gpu:
+                pos, types, sizes = SU.fixture(A, SU.GOLDEN_GRAPHS[name])
+                eye = torch.eye(A, dtype=torch.int64)
+                got = soap.soap_descriptors(torch.from_numpy(pos).cuda(), eye[torch.from_numpy(types).long()].cuda(), sizes,
+                                            torch.from_numpy(G[f"{name}_A{A}_centres"].astype(np.int64)), soap.SoapBasis(**cfg),
+                                            return_coefficients=True)
+                device.append(SU.descriptor_error(got[0].cpu().numpy(), truth))
+                if A == 2:
+                    coeff_device = SU.descriptor_error(got[1].cpu().numpy(), G[f"{name}_A2_coeff"])
+        rec.update(host_error_by_types=host, host_error=max(host), host_coefficient_error_A2=coeff_host, device_bar=8 * max(host))
+        if gpu:
+            rec.update(device_error_by_types=device, device_error=max(device), device_coefficient_error_A2=coeff_device,
+                       gcn_arch=torch.cuda.get_device_properties(0).gcnArchName)
+        else:
+            rec.update({k: v for k, v in old.get("configurations", {}).get(name, {}).items() if k.startswith("device_e") or k.startswith("device_c") or k == "gcn_arch"})
+        assert rec["host_error"] <= CAP
+        record["configurations"][name] = rec
+        print(name, json.dumps(rec))
+    json.dump(record, open(out, "w"), indent=1)
+    print("wrote", out)
+
+
+if __name__ == "__main__":
+    main()

@@ -19,6 +19,7 @@ STRUCT_MAX_TYPES, STRUCT_MAX_ATOMS = 4, 32768   # kStructMaxTypes, kStructMaxAto
 STRUCT_CENTRE_BLOCK, STRUCT_CHUNK, STRUCT_BOND_CENTRES = 64, 1024, 8   # the tiles of egnn_struct_pair_counts / egnn_struct_bonds
 CELL_MAX_TYPES, CELL_MAX_SHELLS, CELL_MAX_ENV_ATOMS, CELL_SHIFT_CODES = 4, 4, 1024, 729   # kCell* of csrc/cells/cell_math.h
 TOPO_MAX_ATOMS, TOPO_MAX_DEGREE, TOPO_BRANCH_MODULUS, TOPO_MAX_LENGTH = 1024, 32, 7, 64   # csrc/eval/topo_math.h
+RING_MAX_SITES, RING_MAX_SIZE = 4096, 32   # RING_MAX_SITES, kRingMaxSize of csrc/eval/rings_math.h
 SOAP_MAX_TYPES, SOAP_MAX_N, SOAP_MAX_L, SOAP_MAX_K = 4, 16, 10, 8   # kSoap* of csrc/eval/soap_math.h
 CELL_CENTRE_BLOCK = 64    # kCellCentreBlock: the centres of one tile of egnn_cell_bonds_count / _fill
 PREALIGN_MIN_ATOMS = 5    # kPrealignMinAtoms of csrc/eval/assign_host.h: atom 0 and its four nearest neighbours
@@ -170,6 +171,8 @@ SIGNATURES = {
     "egnn_topo_paths": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "egnn_topo_tanimoto": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "egnn_topo_host": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i] + [_vp] * 8 + [_i] + [_vp] * 4),
+    "egnn_rings": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i] + [_vp] * 8),
+    "egnn_rings_host": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i] + [_vp] * 4),
     "egnn_soap_features": (_i, [_i, _i, _i]),
     "egnn_soap_table_doubles": (_i, [_i, _i]),
     "egnn_soap_descriptor": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, C.c_double, _vp, _i, _vp, _vp, _vp, _vp]),

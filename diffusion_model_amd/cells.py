@@ -318,3 +318,28 @@ def local_environments(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centr
     return EnvironmentBatch(pos=pos, x=torch.nn.functional.one_hot(e_type.long(), cb.A), exO=exO, sizes=size_h.tolist(), ptr=ptr_h,
                             atom=e_atom.long() - cb.cell_ptr.long()[row_cell], shift=decode_shift(e_code), shift_code=e_code,
                             centre_cell=cell_h, centre_atom=local_h, id=ids, bonds=bonds)
+
+
+def ring_statistics(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centres=None, cutoff: float = 2.0, max_size: int = 16,
+                    max_sites: int = 4096, device=None):
+    """Shortest-path ring statistics on the infinite lattice of every cell (``stats.ring_statistics`` states the definition; not in
+    the reference): the bond list is ``bond_list``'s, a site is (atom, lattice shift), and a ring closes only where the very same
+    site is reached -- an image is never folded onto its atom, so a cell smaller than its rings gives the rings of the crystal,
+    not of the torus (ideal beta-cristobalite in its 24-atom cell: size 12 through every angle).  ``centres`` as in
+    ``local_environments``: None, a type index, or an index tensor into the concatenated atoms.  -> ``RingStatistics``.  Raises
+    ValueError naming cell and atom where an atom has more than 32 bonds or a search labels more than ``max_sites`` (<= 4096)
+    sites."""
+    from . import _rings
+    cb = _CellBatch(_as_cells(cells), device)
+    bonds = _bond_list(cb, cutoff)
+    idx_h, cell_h = _centres(cb, centres)
+    local_h = idx_h - cb.cell_ptr_h.long()[cell_h]
+
+    def describe(m, limit):
+        head = f"cell {int(cell_h[m])}, atom {int(local_h[m])}: "
+        if limit == "degree":
+            return head + "more than 32 bonds; no ring is searched (lower the cutoff)"
+        return head + (f"a ring search labelled more than max_sites = {int(max_sites)} sites; raise max_sites (at most "
+                       f"{_lib.RING_MAX_SITES}) or lower max_size / cutoff")
+
+    return _rings.run(bonds.row_ptr, bonds.atom, bonds.shift.contiguous(), cb.types, cb.A, idx_h, max_size, max_sites, describe)

@@ -748,3 +748,82 @@ def fingerprint_similarity(original_graph_list, generated_graph_list, radii=COVA
     _raise_on_topo_overflow(out[2 * B:], "generated")
     skipped = [i for i, n in enumerate(sizes) if n == 1]
     return [float(out[i]) for i, n in enumerate(sizes) if n != 1], skipped
+
+
+# ---- shortest-path ring statistics (csrc/eval/rings.hip) ------------------------------------------------------------
+def _ring_statistics(inp, centres, max_size, max_sites, side=""):
+    from . import _rings
+    what = f"{side + ' ' if side else ''}graph"
+    gp_h = np.concatenate([[0], np.cumsum(inp.sizes)])
+    where = lambda i: (int(np.searchsorted(gp_h, i, side="right") - 1), int(i - gp_h[np.searchsorted(gp_h, i, side="right") - 1]))
+    crowded = torch.nonzero(inp.degree > _lib.TOPO_MAX_DEGREE).reshape(-1)
+    if crowded.numel():
+        g, a = where(int(crowded[0]))
+        raise ValueError(f"{what} {g}, atom {a}: more than 32 bonds; no ring is searched (lower the scale or the radii)")
+    if centres is None:
+        idx = torch.arange(inp.N, dtype=torch.int64)
+    else:
+        idx = torch.as_tensor(centres).detach().cpu().reshape(-1).to(torch.int64)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= inp.N):
+            raise ValueError(f"a centre lies outside the {inp.N} atoms of the batch")
+
+    def describe(m, limit):
+        g, a = where(int(idx[m]))
+        return (f"{what} {g}, atom {a}: a ring search labelled more than max_sites = {int(max_sites)} sites; raise max_sites (at most "
+                f"{_lib.RING_MAX_SITES}) or lower max_size")
+
+    E = int(inp.row_ptr[-1])
+    # a search inside a graph of n atoms labels at most n sites: a table sized for the largest graph gives the same result as a
+    # larger one and leaves room for more searches per CU (the kernel's LDS grows with max_sites)
+    sites = min(int(max_sites), max(inp.max_atoms, 1)) if int(max_sites) >= 1 else int(max_sites)
+    return _rings.run(inp.row_ptr, inp.neighbours[:E], None, inp.type, inp.A, idx, max_size, sites, describe)
+
+
+def ring_statistics(pos: torch.Tensor, onehot: torch.Tensor, sizes: Sequence[int], radii=COVALENT_RADII, scale=1.2, centres=None,
+                    max_size=16, max_sites=4096):
+    """Shortest-path ring statistics of the bond graph of ``bond_graph`` (King's criterion per angle, as Rino et al. apply it to
+    silica; not in the reference): for every pair (p, q), p < q, of neighbours of a centre, the size of the smallest ring through
+    centre and both -- 2 + the bonds on a shortest path from one neighbour to the other that avoids the centre, so it counts ATOMS:
+    a "6-membered" silica ring has size 12 -- and the number of such shortest paths.  ``centres``: None = every atom, or an index
+    tensor into the concatenated atoms (any order, duplicates allowed).  3 <= max_size <= 32; a ring above max_size is no ring
+    (size 0).  -> ``RingStatistics`` (size, count, angle_ptr, neighbours, centre, histogram, per_centre_smallest).  Raises
+    ValueError naming graph and atom where an atom has more than 32 bonds or a search labels more than ``max_sites`` (<= 4096)
+    sites."""
+    inp = _TopoInput(pos, onehot, sizes, radii, scale, "ring_statistics")
+    return _ring_statistics(inp, centres, max_size, max_sites)
+
+
+def _ring_histograms(inp, rs):
+    """per graph: ring sizes 1 .. max_size over every angle of the graph's atoms, normalised to sum 1 (zeros where it has no ring)"""
+    gp = inp.gp.long()
+    graph = torch.searchsorted(gp, rs.centre[rs.angle_centre], right=True) - 1
+    bins = rs.max_size + 1
+    keep = rs.size > 0
+    h = torch.bincount(graph[keep] * bins + rs.size[keep], minlength=inp.B * bins).view(inp.B, bins).double()
+    total = h.sum(1, keepdim=True)
+    return torch.where(total > 0, h / total.clamp(min=1.0), h)
+
+
+def compare_rings(original_graph_list, generated_graph_list, radii=COVALENT_RADII, scale=1.2, max_size=16, max_sites=4096):
+    """Ring statistics of both sides of what generate() returns (the list conventions of evaluate_by_rmsd): for every original and the
+    LAST element of its generated entry, the ring-size histogram over every angle of every atom (bins 0 .. max_size, bin 0 unused),
+    normalised to sum 1.  -> dict(sizes; original, generated: float64 [B, max_size + 1]; l1: list of float, sum |a - b|; cosine:
+    list of float, ``cos_similarity``).  A pair with no ring on both sides gets l1 = 0 and cosine = 1; a pair with rings on one
+    side only gets l1 = 1 and cosine = 0."""
+    col = _collate_pairs(original_graph_list, generated_graph_list, True)
+    if col is None:
+        return dict(sizes=[], original=None, generated=None, l1=[], cosine=[])
+    sizes, _, po, pg, xo, xg = col
+    if xo.shape[1:] != xg.shape[1:]:
+        raise ValueError("originals and samples differ in the number of atom types")
+    a = _TopoInput(po, xo, sizes, radii, scale, "compare_rings")
+    b = _TopoInput(pg, xg, sizes, radii, scale, "compare_rings")
+    ha = _ring_histograms(a, _ring_statistics(a, None, max_size, max_sites, "original"))
+    hb = _ring_histograms(b, _ring_statistics(b, None, max_size, max_sites, "generated"))
+    both = torch.stack([ha, hb]).cpu()      # ONE download
+    l1, cosine = [], []
+    for x, y in zip(both[0], both[1]):
+        l1.append(float((x - y).abs().sum()))
+        empty_x, empty_y = not bool(x.any()), not bool(y.any())
+        cosine.append(1.0 if empty_x and empty_y else (0.0 if empty_x or empty_y else cos_similarity(x, y)))
+    return dict(sizes=sizes, original=both[0], generated=both[1], l1=l1, cosine=cosine)

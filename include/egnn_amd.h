@@ -560,6 +560,39 @@ int egnn_topo_host(int B, int A, const float* pos, const int32_t* type, const in
                    int32_t* row_ptr, int32_t* neighbours, int32_t* degree, int32_t* overflow, uint16_t* dist, int32_t* component,
                    int32_t* fragments, int32_t* fp, int n_pairs, const int32_t* pairs, double* sim, int64_t* sa, int64_t* sb);
 
+/* ---- shortest-path ring statistics (csrc/eval/rings.hip; definitions in csrc/eval/rings_math.h) ----------------------------
+ * The medium-range order of a network: for every angle (p, q), p < q, of positions in the bond-list row of a centre c, the size of
+ * the smallest ring through it (King's shortest-path criterion, per angle as Rino et al. apply it) and the number of shortest
+ * closing paths.  No reference file computes rings: an extension beyond the reference.  The input is a bond list in CSR form over
+ * the N atoms: d_row_ptr int32 [N+1], d_atom int32 [E], and for periodic cells d_shift int32 [E, 3], the lattice shift of every
+ * bond, each component in {-1, 0, 1} (NULL for clusters).  A site is (atom, shift) of the infinite lattice: following bond e of
+ * atom a from (a, s) leads to (d_atom[e], s + d_shift[e]); images are never folded.  d_centre int32 [M] indexes the atoms, any
+ * order, repeats allowed; d_angle_ptr int32 [M+1] is the exclusive prefix sum of d (d - 1) / 2 over the centres' degrees d, and
+ * n_angles its last entry.  A centre's angles are in lexicographic order of (p, q).
+ *   d_size int32 [n_angles]:         2 + the bonds on a shortest path from site row[p] to site row[q] with the site (c, 0) removed
+ *                                    (it counts ATOMS on the ring: a "6-membered" silica ring has size 12); 0 where no such path
+ *                                    has size <= max_size; -1 where the search overflowed;
+ *   d_count int32 [n_angles]:        the number of distinct shortest such paths, saturating at 2^31 - 1; 0 where size <= 0;
+ *   d_overflow int32 [M]:            1 where a search of the centre labelled more than max_sites sites or the centre has more than
+ *                                    32 bonds (all its angles -1), else 0;
+ *   d_hist int32 [A, max_size + 1]:  angles by centre type (d_type int32 [N]) and size, bin 0 = no ring, overflowed angles not
+ *                                    counted; or NULL.
+ * 3 <= max_size <= 32; 1 <= max_sites <= 4096 (RING_MAX_SITES).  One workgroup per (centre, p) labels sites in an LDS hash table
+ * of max(512, 2 max_sites rounded up to a power of two) * 12 + 4 max_sites bytes (112 KiB at 4096).  All outputs are integers,
+ * bitwise reproducible and equal to egnn_rings_host's.  row_ptr, atom, shift and centre are HOST copies of the lists, each may be
+ * NULL; those given are checked before anything is launched (a centre outside the atoms, a non-monotone row_ptr, a neighbour
+ * outside [0, N), a shift outside {-1, 0, 1}: EGNN_EINVAL, as max_size, max_sites and NULL pointers outside their limits).  The
+ * kernel trusts none of the device lists either way: it ignores a bond it cannot follow and a centre it cannot read. */
+int egnn_rings(void* stream, int N, const int32_t* d_row_ptr, int E, const int32_t* d_atom, const int32_t* d_shift, const int32_t* d_type,
+               int A, int M, const int32_t* d_centre, const int32_t* d_angle_ptr, int n_angles, int max_size, int max_sites, int32_t* d_size,
+               int32_t* d_count, int32_t* d_overflow, int32_t* d_hist, const int32_t* row_ptr, const int32_t* atom, const int32_t* shift,
+               const int32_t* centre);
+/* Host statement of egnn_rings: HOST pointers, no GPU, the same definitions in plain C++.  Also EGNN_EINVAL: a type outside
+ * [0, A), an angle_ptr that is not the prefix sum of d (d - 1) / 2 ending at n_angles. */
+int egnn_rings_host(int N, const int32_t* row_ptr, int E, const int32_t* atom, const int32_t* shift, const int32_t* type, int A, int M,
+                    const int32_t* centre, const int32_t* angle_ptr, int n_angles, int max_size, int max_sites, int32_t* size,
+                    int32_t* count, int32_t* overflow, int32_t* hist);
+
 /* ---- SOAP descriptors and spectrum template matching (csrc/eval/soap.hip; definitions in csrc/eval/soap_math.h) -------------
  * template_matching.py:41-68 finds, for every target record, the three reference records with the nearest XANES spectrum (MSE of
  * spectrum[0]) and reports the cosine similarity of dscribe's SOAP power spectrum of atom 0.  These entries restate it for a ragged

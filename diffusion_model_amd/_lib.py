@@ -21,6 +21,9 @@ CELL_MAX_TYPES, CELL_MAX_SHELLS, CELL_MAX_ENV_ATOMS, CELL_SHIFT_CODES = 4, 4, 10
 TOPO_MAX_ATOMS, TOPO_MAX_DEGREE, TOPO_BRANCH_MODULUS, TOPO_MAX_LENGTH = 1024, 32, 7, 64   # csrc/eval/topo_math.h
 RING_MAX_SITES, RING_MAX_SIZE = 4096, 32   # RING_MAX_SITES, kRingMaxSize of csrc/eval/rings_math.h
 SOAP_MAX_TYPES, SOAP_MAX_N, SOAP_MAX_L, SOAP_MAX_K = 4, 16, 10, 8   # kSoap* of csrc/eval/soap_math.h
+SQ_MAX_TYPES, SQ_MAX_Q, SQ_MAX_BINS, SQ_MAX_ATOMS, SQ_MAX_VECTORS = 4, 4096, 4096, 32768, 1 << 24   # kSq* of csrc/eval/sq_math.h
+SQ_ROW_BLOCK, SQ_CHUNK, SQ_VECTOR_BLOCK = 64, 256, 256   # the tiles of egnn_sq_debye and egnn_sq_cell_rho
+SQ_WINDOWS = {None: 0, "none": 0, "lorch": 1}
 CELL_CENTRE_BLOCK = 64    # kCellCentreBlock: the centres of one tile of egnn_cell_bonds_count / _fill
 PREALIGN_MIN_ATOMS = 5    # kPrealignMinAtoms of csrc/eval/assign_host.h: atom 0 and its four nearest neighbours
 
@@ -186,6 +189,13 @@ SIGNATURES = {
     "egnn_cell_env_count": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "egnn_cell_env_fill": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i] + [_vp] * 4),
     "egnn_cell_env_host": (_i, [_i, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, _vp, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64] + [_vp] * 4),
+    "egnn_sq_debye": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _vp, _i, _vp, _vp, _vp]),
+    "egnn_sq_cell_plan": (_i, [_i, _vp, C.c_double, _vp, _vp]),
+    "egnn_sq_cell_count": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),
+    "egnn_sq_cell_rho": (_i, [_vp, _i, _i, _i] + [_vp] * 10 + [C.c_double, C.c_double, _i, _i, _vp, _i, _vp, _i] + [_vp] * 4),
+    "egnn_sq_cell_shells": (_i, [_vp, _i, _i, _i, _vp, _vp, _i] + [_vp] * 6),
+    "egnn_sq_host": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp, C.c_double, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i,
+                          C.c_int64] + [_vp] * 8),
     "egnn_optim_step": (_i, [_vp, _i, _i, _pp, _pp, _pp, _pp, _pp, _i64p, C.POINTER(OptimConsts)]),
     "egnn_optim_interp": (_i, [_vp, _i, _pp, _pp, _i64p, _f]),
     "egnn_optim_tensors_per_launch": (_i, []),

@@ -9,6 +9,9 @@ of a batch of cells (or every atom of one type, or any list of atoms), by ``csrc
 * ``local_environments`` -- the shell cluster about each centre, as one batch that goes straight into the model
   (``.batch()``), the samplers and ``stats.compare_structures`` (``.to_data_list()``).
 
+``structure_factor`` (``csrc/eval/sq.hip``) is the reciprocal-space statistic of whole cells: rho_a on the reciprocal lattice and
+its shell averages, finished to partial and total S(q); no file of the reference computes it.
+
 The definitions (``csrc/cells/cell_math.h``) are those of the INFINITE lattice: a site is (atom, integer shift), a bond joins
 sites closer than the cutoff, an environment is what ``shells`` bonds reach.  Wherever the reference's search uses no bond that
 wraps round its 3x3x3 supercell the two site sets are identical; where it does, the reference aliases an image onto a site on the
@@ -343,3 +346,111 @@ def ring_statistics(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centres=
                        f"{_lib.RING_MAX_SITES}) or lower max_size / cutoff")
 
     return _rings.run(bonds.row_ptr, bonds.atom, bonds.shift.contiguous(), cb.types, cb.A, idx_h, max_size, max_sites, describe)
+
+
+# ---- structure factors of periodic cells (csrc/eval/sq.hip) ---------------------------------------------------------
+def _sq_vector_tiles(counts) -> np.ndarray:
+    """the work list of egnn_sq_cell_rho (include/egnn_amd.h): {cell, first vector (local)} for every block of 256 vectors"""
+    cnt = np.asarray(counts, dtype=np.int64)
+    per = -(-cnt // _lib.SQ_VECTOR_BLOCK)
+    ci = np.repeat(np.arange(cnt.size, dtype=np.int64), per)
+    t = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
+    return np.stack([ci, t * _lib.SQ_VECTOR_BLOCK], 1).astype(np.int32).reshape(-1, 2)
+
+
+class _SqCellRun:
+    """the reciprocal vectors of a batch of cells (plan, count pass, prefix sums, work list, outputs allocated); ``rho()`` and
+    ``shells()`` are the launches alone"""
+
+    def __init__(self, cb: _CellBatch, q_max: float, dq: float, nbins: int):
+        lib = _lib.lib()
+        self.cb, self.q_max, self.dq, self.nbins = cb, q_max, dq, nbins
+        self.plan_h, n_rows_h = torch.zeros(cb.C, 4, dtype=torch.int32), torch.zeros(1, dtype=torch.int32)
+        _lib.check(lib.egnn_sq_cell_plan(cb.C, _lib.ptr(cb.lattice_h), q_max, _lib.ptr(self.plan_h), _lib.ptr(n_rows_h)))
+        self.n_rows, self.plan = int(n_rows_h), self.plan_h.to(cb.dev)
+        row_count = torch.empty(self.n_rows, dtype=torch.int32, device=cb.dev)
+        _lib.check(lib.egnn_sq_cell_count(_lib.stream_ptr(), cb.C, _lib.ptr(cb.lattice_h), _lib.ptr(self.plan_h), _lib.ptr(cb.lattice),
+                                          _lib.ptr(self.plan), q_max, self.n_rows, _lib.ptr(row_count)))
+        row_ptr64 = torch.zeros(self.n_rows + 1, dtype=torch.int64, device=cb.dev)
+        row_ptr64[1:] = torch.cumsum(row_count.long(), 0)
+        first = torch.cat([self.plan_h[:, 3].long(), torch.tensor([self.n_rows])]).to(cb.dev)
+        self.vec_ptr64 = row_ptr64[first].cpu()
+        self.counts = (self.vec_ptr64[1:] - self.vec_ptr64[:-1]).tolist()
+        for c, n in enumerate(self.counts):
+            if n > _lib.SQ_MAX_VECTORS:
+                raise ValueError(f"cell {c}: {n} reciprocal vectors below q_max = {q_max} (at most {_lib.SQ_MAX_VECTORS}; lower q_max)")
+        self.K = K = int(self.vec_ptr64[-1])
+        if K >= 2 ** 31:
+            raise ValueError("more than 2^31 - 1 reciprocal vectors in the batch (fewer cells per call)")
+        self.vec_ptr_h = self.vec_ptr64.to(torch.int32)
+        self.vec_ptr, self.row_ptr = self.vec_ptr_h.to(cb.dev), row_ptr64.to(torch.int32)
+        tiles_h = _sq_vector_tiles(self.counts)
+        self.n_tiles, self.tiles = len(tiles_h), torch.from_numpy(tiles_h).to(cb.dev)
+        self.hkl = torch.empty(max(K, 1), 3, dtype=torch.int32, device=cb.dev)[:K]
+        self.kabs = torch.empty(max(K, 1), dtype=torch.float64, device=cb.dev)[:K]
+        self.bins = torch.empty(max(K, 1), dtype=torch.int32, device=cb.dev)[:K]
+        self.rho_out = torch.empty(max(K, 1), cb.A, 2, dtype=torch.float64, device=cb.dev)[:K]
+
+    def rho(self):
+        cb, K = self.cb, self.K
+        _lib.check(_lib.lib().egnn_sq_cell_rho(
+            _lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(self.plan_h), _lib.ptr(self.vec_ptr_h),
+            _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice), _lib.ptr(self.plan), _lib.ptr(self.vec_ptr), _lib.ptr(cb.frac) if cb.N else None,
+            _lib.ptr(cb.types) if cb.N else None, self.q_max, self.dq, self.nbins, self.n_rows, _lib.ptr(self.row_ptr), K,
+            _lib.ptr(self.tiles) if self.n_tiles else None, self.n_tiles, _lib.ptr(self.hkl) if K else None, _lib.ptr(self.kabs) if K else None,
+            _lib.ptr(self.bins) if K else None, _lib.ptr(self.rho_out) if K else None))
+
+    def shells(self):
+        cb, K, A, nbins = self.cb, self.K, self.cb.A, self.nbins
+        count = torch.empty(cb.C, nbins, dtype=torch.int64, device=cb.dev)
+        mean_k = torch.empty(cb.C, nbins, dtype=torch.float64, device=cb.dev)
+        s = torch.empty(cb.C, A, A, nbins, dtype=torch.float64, device=cb.dev)
+        _lib.check(_lib.lib().egnn_sq_cell_shells(_lib.stream_ptr(), cb.C, A, nbins, _lib.ptr(self.vec_ptr_h), _lib.ptr(self.vec_ptr), K,
+                                                  _lib.ptr(self.kabs) if K else None, _lib.ptr(self.bins) if K else None,
+                                                  _lib.ptr(self.rho_out) if K else None, _lib.ptr(count), _lib.ptr(mean_k), _lib.ptr(s)))
+        return count, mean_k, s
+
+
+def structure_factor(cells, q_max: float = 15.0, dq: float = 0.05, weights=None, form: str = "faber-ziman", vectors: bool = False,
+                     device=None):
+    """Static structure factors of periodic cells on their reciprocal lattices (csrc/eval/sq_math.h): for every integer vector
+    m = (h, k, l) of the half space with |k_m| < q_max, k_m = 2 pi m L^-T, rho_a(m) = sum_{j in a} exp(-i k_m . r_j); shell bin
+    floor(|k_m| / dq), nbins = ceil(q_max / dq) <= 4096.  -> a namespace with q float64 [nbins] (bin centres), mean_k and count
+    (int64, over the full sphere) [C, nbins], s [C, A, A, nbins] = the shell mean of Re(rho_a rho_b*), partial [C, A, A, nbins] and
+    total [C, nbins] from D_ab = s_ab - delta_ab N_a in the forms and with the weights of stats.structure_factor, n_type [C, A],
+    sizes; an empty shell has count 0 and NaN means.  ``vectors=True`` adds hkl int32 [K, 3], k float64 [K], bin int32 [K], rho
+    complex128 [K, A] and vec_ptr int64 [C+1] (host), cell by cell and ascending (h, k, l).  q_max must keep
+    floor(q_max |a_i| / 2 pi) <= 1023 and at most 2^24 vectors per cell."""
+    from types import SimpleNamespace
+    from .stats import _sf_finish, _sf_weights
+    cells = _as_cells(cells)
+    q_max, dq = float(q_max), float(dq)
+    if not (q_max > 0 and math.isfinite(q_max) and dq > 0 and math.isfinite(dq)):
+        raise ValueError("q_max and dq must be positive and finite")
+    nbins = math.ceil(q_max / dq)
+    if nbins > _lib.SQ_MAX_BINS:
+        raise ValueError(f"ceil(q_max / dq) = {nbins} shell bins (at most {_lib.SQ_MAX_BINS})")
+    for c, cell in enumerate(cells):
+        if cell.num_types > _lib.SQ_MAX_TYPES:
+            raise ValueError(f"cell {c}: {cell.num_types} atom types (at most {_lib.SQ_MAX_TYPES})")
+        L = cell.lattice
+        if abs(float(torch.linalg.det(L))) <= 1e-9 * float(L.norm(dim=1).prod()):
+            raise ValueError(f"cell {c}: singular lattice")
+        need = int(math.floor(q_max * float(L.norm(dim=1).max()) / (2 * math.pi)))
+        if need > 1023:
+            raise ValueError(f"cell {c}: q_max = {q_max} needs a Miller index of {need} (at most 1023)")
+    cb = _CellBatch(cells, device)
+    _sf_weights(weights, cb.A, nbins, cb.dev)   # a bad shape fails before the launch
+    run = _SqCellRun(cb, q_max, dq, nbins)
+    run.rho()
+    count, mean_k, s = run.shells()
+    A, K, hkl, kabs, bins, rho, vec_ptr64 = cb.A, run.K, run.hkl, run.kabs, run.bins, run.rho_out, run.vec_ptr64
+    n_type_h = torch.stack([torch.bincount(c.types.long(), minlength=A)[:A] for c in cells])
+    n_type = n_type_h.to(cb.dev)
+    D = s - torch.diag_embed(n_type.to(torch.float64))[..., None]
+    partial, total = _sf_finish(D, n_type, weights, form)
+    out = SimpleNamespace(q=(torch.arange(nbins, dtype=torch.float64, device=cb.dev) + 0.5) * dq, mean_k=mean_k, count=count, s=s,
+                          partial=partial, total=total, n_type=n_type, sizes=list(cb.sizes))
+    if vectors:
+        out.hkl, out.k, out.bin, out.rho, out.vec_ptr = hkl, kabs, bins, torch.view_as_complex(rho), vec_ptr64
+    return out

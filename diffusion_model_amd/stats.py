@@ -827,3 +827,176 @@ def compare_rings(original_graph_list, generated_graph_list, radii=COVALENT_RADI
         empty_x, empty_y = not bool(x.any()), not bool(y.any())
         cosine.append(1.0 if empty_x and empty_y else (0.0 if empty_x or empty_y else cos_similarity(x, y)))
     return dict(sizes=sizes, original=both[0], generated=both[1], l1=l1, cosine=cosine)
+
+
+# ---- structure factors (csrc/eval/sq.hip) --------------------------------------------------------------------------
+NEUTRON_LENGTHS = (5.803, 4.1491)   # coherent neutron scattering lengths in fm, (O, Si), in the order of the one-hot columns
+_SQ_PARTIAL_BYTES = 256 << 20       # workspace of one egnn_sq_debye call; a longer q list is taken in slabs
+SQ_FORMS = ("faber-ziman", "ashcroft-langreth")
+
+
+def _sq_tiles(sizes):
+    """The work list of egnn_sq_debye (include/egnn_amd.h) from the graph sizes, on the host: {g, c0, j0} for every block of 64
+    atoms i and 256 atoms j of a graph that holds a pair i < j, graph by graph -- 256 graphs of 64 atoms give 256 workgroups, 32
+    of 512 atoms 384 and one of 4096 atoms 544 -- and tile_ptr [B+1], the first tile of each graph.
+    -> (int32 [n_tiles, 3], int32 [B+1])"""
+    sz = np.asarray(list(sizes), dtype=np.int64)
+    n_cb, n_jb = -(-sz // _lib.SQ_ROW_BLOCK), -(-sz // _lib.SQ_CHUNK)
+    per = n_cb * n_jb
+    gi = np.repeat(np.arange(sz.size, dtype=np.int64), per)
+    t = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
+    c0, j0 = (t // np.maximum(n_jb[gi], 1)) * _lib.SQ_ROW_BLOCK, (t % np.maximum(n_jb[gi], 1)) * _lib.SQ_CHUNK
+    keep = np.minimum(j0 + _lib.SQ_CHUNK, sz[gi]) - 1 > c0   # the last j of the block lies above its first i
+    tiles = np.stack([gi[keep], c0[keep], j0[keep]], 1).astype(np.int32).reshape(-1, 3)
+    tile_ptr = np.zeros(sz.size + 1, dtype=np.int64)
+    tile_ptr[1:] = np.cumsum(np.bincount(gi[keep], minlength=sz.size))
+    return tiles, tile_ptr.astype(np.int32)
+
+
+def _sq_q(q):
+    qh = np.ascontiguousarray(np.asarray(q.detach().cpu() if isinstance(q, torch.Tensor) else q, dtype=np.float64).reshape(-1))
+    if qh.size < 1:
+        raise ValueError("q must hold at least one value")
+    if qh.size > _lib.SQ_MAX_Q:
+        raise ValueError(f"{qh.size} q values (at most {_lib.SQ_MAX_Q} per call)")
+    if not np.all(np.isfinite(qh)) or np.any(qh < 0):
+        raise ValueError("every q must be finite and not negative")
+    return qh
+
+
+class _DebyePlan:
+    """everything one Debye call needs on the device (checks, the tile list, q and the workspace uploaded / allocated once);
+    ``run()`` is the launches alone"""
+
+    def __init__(self, inp, qh, r_max, window, what):
+        if inp.A > _lib.SQ_MAX_TYPES:
+            raise ValueError(f"{what}: {inp.A} atom types (at most {_lib.SQ_MAX_TYPES})")
+        for g, n in enumerate(inp.sizes):
+            if n > _lib.SQ_MAX_ATOMS:
+                raise ValueError(f"{what}: graph {g} has {n} atoms (at most {_lib.SQ_MAX_ATOMS})")
+        if window not in _lib.SQ_WINDOWS:
+            raise ValueError(f"window must be None or 'lorch', not {window!r}")
+        self.r_max = float("inf") if r_max is None else float(r_max)
+        if not self.r_max > 0:
+            raise ValueError("r_max must be positive (None: no cut)")
+        self.window = _lib.SQ_WINDOWS[window]
+        if self.window == 1 and not np.isfinite(self.r_max):
+            raise ValueError("the Lorch window needs a finite r_max")
+        tiles, tile_ptr = _sq_tiles(inp.sizes)
+        self.inp, self.qh, self.n_tiles, self.Q = inp, qh, len(tiles), int(qh.size)
+        P = inp.A * (inp.A + 1) // 2
+        blob = torch.from_numpy(np.concatenate([tile_ptr, tiles.reshape(-1)])).to(inp.dev)
+        self.tile_ptr, self.tiles = blob.split([inp.B + 1, tiles.size])
+        self.q = torch.from_numpy(qh).to(inp.dev)
+        self.slab = max(1, min(self.Q, _SQ_PARTIAL_BYTES // max(1, self.n_tiles * P * 8)))
+        self.partial = torch.empty(max(self.n_tiles * P * self.slab, 1), dtype=torch.float64, device=inp.dev)
+
+    def run(self):
+        inp, Q = self.inp, self.Q
+        out = torch.empty(inp.B, inp.A, inp.A, Q, dtype=torch.float64, device=inp.dev)
+        for s in range(0, Q, self.slab):
+            m = min(self.slab, Q - s)
+            piece = out if m == Q else torch.empty(inp.B, inp.A, inp.A, m, dtype=torch.float64, device=inp.dev)
+            _lib.check(_lib.lib().egnn_sq_debye(_lib.stream_ptr(), inp.B, inp.A, _lib.ptr(inp.pos), _lib.ptr(inp.type), _lib.ptr(inp.gp),
+                                                inp.max_atoms, m, self.qh[s:].ctypes.data, _lib.ptr(self.q[s:]), self.r_max, self.window,
+                                                _lib.ptr(self.tiles) if self.n_tiles else None, self.n_tiles, _lib.ptr(self.tile_ptr),
+                                                _lib.ptr(self.partial), _lib.ptr(piece)))
+            if m != Q:
+                out[..., s:s + m] = piece
+        return out
+
+
+def _debye_sums(inp, qh, r_max, window, what):
+    return _DebyePlan(inp, qh, r_max, window, what).run()
+
+
+def debye_sums(pos: torch.Tensor, onehot: torch.Tensor, sizes: Sequence[int], q, r_max=None, window=None) -> torch.Tensor:
+    """Debye sums of every graph: float64 [B, A, A, Q], D[g, a, b, k] = sum over the pairs i != j of graph g with type(i) = a,
+    type(j) = b and r_ij < r_max of w(r_ij) sinc(q_k r_ij) (csrc/eval/sq_math.h): r in fp64 from the float32 positions, sinc(0) = 1,
+    ``r_max=None`` no cut, ``window`` None (w = 1) or 'lorch' (w = sinc(pi r / r_max), needs r_max).  ``q``: up to 4096 finite
+    values >= 0 in any order.  D is symmetric in (a, b) and D(0) without a cut is exactly N_a N_b - delta_ab N_a.  No file of the
+    reference computes this ("Structure factors")."""
+    inp = _StructInput(pos, onehot, sizes, "debye_sums")
+    return _debye_sums(inp, _sq_q(q), r_max, window, "debye_sums")
+
+
+def _sf_weights(weights, A, Q, dev):
+    """scattering lengths -> float64 [A, Q] on the device ([A] is broadcast along q)"""
+    if weights is None:
+        if A != 2:
+            raise ValueError(f"weights is required for {A} atom types (the default NEUTRON_LENGTHS is (O, Si))")
+        weights = NEUTRON_LENGTHS
+    b = torch.as_tensor(weights, dtype=torch.float64).detach().to(dev)
+    if b.dim() == 1 and b.shape[0] == A:
+        return b[:, None].expand(A, Q)
+    if b.shape != (A, Q):
+        raise ValueError(f"weights must be [A] or [A, Q] = [{A}] or [{A}, {Q}], not {list(b.shape)}")
+    return b
+
+
+def _sf_finish(D, n_type, weights, form):
+    """partials and total of ``form`` from D [B, A, A, Q] (float64) and n_type [B, A]: float64 element-wise ops on the device.
+    faber-ziman: 1 + N / (N_a N_b) D_ab; ashcroft-langreth: delta_ab + D_ab / sqrt(N_a N_b); an absent type gives rows of zeros;
+    total = 1 + sum_ab b_a b_b D_ab / (N <b>^2), <b> = sum_a (N_a / N) b_a (zeros for a graph without atoms)."""
+    if form not in SQ_FORMS:
+        raise ValueError(f"form must be one of {SQ_FORMS}, not {form!r}")
+    B, A, _, Q = D.shape
+    n = n_type.to(torch.float64)
+    N = n.sum(1)
+    nn = n[:, :, None] * n[:, None, :]
+    present = nn > 0
+    safe = torch.where(present, nn, torch.ones_like(nn))
+    if form == "faber-ziman":
+        partial = 1.0 + (N[:, None, None] / safe)[..., None] * D
+    else:
+        partial = torch.eye(A, dtype=torch.float64, device=D.device)[None, :, :, None] + D / safe.sqrt()[..., None]
+    partial = torch.where(present[..., None], partial, torch.zeros_like(partial))
+    b = _sf_weights(weights, A, Q, D.device)
+    some = N > 0
+    Ns = torch.where(some, N, torch.ones_like(N))
+    mean_b = (n / Ns[:, None]) @ b                                      # [B, Q]
+    mean_b = torch.where(some[:, None], mean_b, torch.ones_like(mean_b))
+    total = 1.0 + torch.einsum("aq,bq,gabq->gq", b, b, D) / (Ns[:, None] * mean_b * mean_b)
+    return partial, torch.where(some[:, None], total, torch.zeros_like(total))
+
+
+def structure_factor(pos: torch.Tensor, onehot: torch.Tensor, sizes: Sequence[int], q, weights=None, r_max=None, window=None,
+                     form="faber-ziman"):
+    """Static structure factors of every graph from its Debye sums: a namespace with q float64 [Q], debye [B, A, A, Q],
+    partial [B, A, A, Q] (``form`` 'faber-ziman': 1 + N / (N_a N_b) D_ab, or 'ashcroft-langreth': delta_ab + D_ab / sqrt(N_a N_b);
+    zeros for an absent type), total [B, Q] = 1 + sum_ab b_a b_b D_ab / (N <b>^2), n_type int64 [B, A] and sizes.  ``weights``:
+    scattering lengths [A], or [A, Q] for q-dependent form factors; default NEUTRON_LENGTHS for (O, Si) when A = 2.  The Debye
+    sum of a finite cluster carries the cluster's shape at small q ("Structure factors")."""
+    from types import SimpleNamespace
+    inp = _StructInput(pos, onehot, sizes, "structure_factor")
+    qh = _sq_q(q)
+    _sf_weights(weights, inp.A, int(qh.size), inp.dev)   # a bad shape fails before the launch
+    D = _debye_sums(inp, qh, r_max, window, "structure_factor")
+    n_type = inp.n_type()
+    partial, total = _sf_finish(D, n_type, weights, form)
+    return SimpleNamespace(q=torch.from_numpy(qh).to(inp.dev), debye=D, partial=partial, total=total, n_type=n_type, sizes=list(inp.sizes))
+
+
+def compare_structure_factors(original_graph_list, generated_graph_list, q=None, weights=None, r_max=None, window=None,
+                              form="faber-ziman"):
+    """Reciprocal-space comparison of what generate() returns with the originals (the list conventions and the collation of
+    compare_structures): both sides get structure_factor on ``q`` (default 0.5 ... 25.0 in steps of 0.05), then every partial and
+    the total of a sample are compared with the original's by the reference's curve metrics.
+    -> dict: 'partial' and 'total_curve' = {cos, l2, mse, wasserstein} per graph (float64 [B, A, A] and [B]), 'total' = the same
+    metrics of the curves summed over all graphs ({'partial': [A, A], 'total_curve': scalar}), 'original' / 'generated' the two
+    profiles, 'q', 'sizes'.  Originals and samples are clusters of the same size and shape, so the small-q shape term of the
+    Debye sum is compared like for like."""
+    col = _collate_pairs(original_graph_list, generated_graph_list, True)
+    if col is None:
+        return {}
+    sizes, _, po, pg, xo, xg = col
+    if q is None:
+        q = 0.5 + 0.05 * np.arange(491)
+    kw = dict(weights=weights, r_max=r_max, window=window, form=form)
+    o, g = structure_factor(po, xo, sizes, q, **kw), structure_factor(pg, xg, sizes, q, **kw)
+    if o.partial.shape != g.partial.shape:
+        raise ValueError("originals and samples differ in the number of atom types")
+    return dict(sizes=sizes, q=o.q, partial=_curve_metrics(o.partial, g.partial), total_curve=_curve_metrics(o.total, g.total),
+                total=dict(partial=_curve_metrics(o.partial.sum(0), g.partial.sum(0)),
+                           total_curve=_curve_metrics(o.total.sum(0), g.total.sum(0))),
+                original=o, generated=g)

@@ -694,6 +694,60 @@ int egnn_cell_env_host(int C, int A, const int32_t* cell_ptr, const double* latt
                        int32_t* bond_ptr, int64_t bond_cap, int32_t* bond_atom, int32_t* bond_shift, int32_t* env_size,
                        int64_t env_cap, int32_t* env_atom, int32_t* env_shift, int32_t* env_type, float* env_pos);
 
+/* ---- structure factors (csrc/eval/sq.hip; definitions in csrc/eval/sq_math.h) -----------------------------------------------
+ * Reciprocal-space statistics: Debye sums of clusters and reciprocal-lattice sums of periodic cells.  No file of the reference
+ * computes them (an extension, like the rings).  All sums are fp64 in one fixed order, no floating-point atomic: results are
+ * bitwise reproducible and a graph gives the same bits in any batch.  Bad arguments return EGNN_EINVAL with a message before
+ * anything is launched; every output is written by the call.
+ *
+ * egnn_sq_debye: d_out double [B, A, A, Q], D_ab(q_k) = sum_{i in a} sum_{j in b, j != i, r_ij < r_max} w(r_ij) sinc(q_k r_ij);
+ * r in fp64 from the float32 positions, sinc(0) = 1, r_max = +inf no cut, window 0 (w = 1) or 1 (Lorch, sinc(pi r / r_max),
+ * finite r_max).  q double [Q], finite and >= 0, any order, Q <= 4096, given twice (HOST copy for the checks, device copy for
+ * the kernel); A <= 4; graphs of at most 32768 atoms.  d_tiles int32 [n_tiles, 3] = {graph, first atom i, first atom j} (local
+ * indices; multiples of 64 and of 256): every 64 x 256 block of a graph that holds a pair i < j, the tiles of a graph contiguous,
+ * d_tile_ptr int32 [B+1] the first tile of each graph; d_partial double [n_tiles, A(A+1)/2, Q] is workspace.  One workgroup per
+ * tile visits each unordered pair once (r once per pair and 512 q values); a finishing pass adds the tiles of a graph in
+ * ascending index.  D_ab(0) without a cut is exactly N_a N_b - delta_ab N_a. */
+int egnn_sq_debye(void* stream, int B, int A, const float* d_pos, const int32_t* d_type, const int32_t* d_graph_ptr, int max_atoms, int Q,
+                  const double* q, const double* d_q, double r_max, int window, const int32_t* d_tiles, int n_tiles,
+                  const int32_t* d_tile_ptr, double* d_partial, double* d_out);
+/* Cells: lattice double [C, 9] (rows a_1, a_2, a_3), frac double [N, 3] (wrapped to [0, 1) as in egnn_cell_*), k_m = 2 pi m L^-T
+ * for integer m = (h, k, l); the vectors of a cell are the m of the half space (h > 0, or h = 0 and k > 0, or h = k = 0 and
+ * l > 0) with |k_m| < q_max, each standing for +-m, ordered cell by cell and ascending (h, k, l).  q_max must keep
+ * floor(q_max |a_i| / 2 pi) <= 1023 on every axis and at most 2^24 vectors per cell.
+ *
+ * egnn_sq_cell_plan (host only, no GPU): plan int32 [C, 4] = {H, K, L, first row}, the index box of each cell (one wider than
+ * the bound, at most 1023) and where its (H + 1)(2K + 1) rows (h, k) start; *n_rows their total.
+ * egnn_sq_cell_count: d_row_count int32 [n_rows], the vectors of every (h, k) row.  The caller takes the exclusive prefix sum
+ * d_row_ptr int32 [n_rows + 1] and, at the first row of each cell, vec_ptr int32 [C+1].
+ * egnn_sq_cell_rho (the fill pass): d_hkl int32 [K, 3], d_k double [K] = |k_m|, d_bin int32 [K] = floor(|k_m| / dq) (nbins =
+ * ceil(q_max / dq) <= 4096) and d_rho double [K, A, 2] = (re, im) of rho_a(m) = sum_{j in a} exp(-i k_m . r_j), the phase
+ * h f_1 + k f_2 + l f_3 taken mod 1 before the sine and cosine.  d_tiles int32 [n_tiles, 2] = {cell, first vector (local, a
+ * multiple of 256)}: one workgroup per 256 vectors of a cell, the cell's atoms staged in LDS and shared by them.  cell_ptr,
+ * lattice, plan and vec_ptr are given twice (HOST copies for the checks).
+ * egnn_sq_cell_shells: per cell and shell bin, d_count int64 [C, nbins] = vectors over the full sphere (2 x the half space),
+ * d_mean_k double [C, nbins] and d_s double [C, A, A, nbins] = the mean of Re(rho_a rho_b*), every sum over the bin's vectors in
+ * ascending vector index; an empty bin has count 0 and NaN means. */
+int egnn_sq_cell_plan(int C, const double* lattice, double q_max, int32_t* plan, int32_t* n_rows);
+int egnn_sq_cell_count(void* stream, int C, const double* lattice, const int32_t* plan, const double* d_lattice, const int32_t* d_plan,
+                       double q_max, int n_rows, int32_t* d_row_count);
+int egnn_sq_cell_rho(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* plan,
+                     const int32_t* vec_ptr, const int32_t* d_cell_ptr, const double* d_lattice, const int32_t* d_plan,
+                     const int32_t* d_vec_ptr, const double* d_frac, const int32_t* d_type, double q_max, double dq, int nbins, int n_rows,
+                     const int32_t* d_row_ptr, int K, const int32_t* d_tiles, int n_tiles, int32_t* d_hkl, double* d_k, int32_t* d_bin,
+                     double* d_rho);
+int egnn_sq_cell_shells(void* stream, int C, int A, int nbins, const int32_t* vec_ptr, const int32_t* d_vec_ptr, int K, const double* d_k,
+                        const int32_t* d_bin, const double* d_rho, int64_t* d_count, double* d_mean_k, double* d_s);
+/* Host statement of the entries above: HOST pointers, no GPU, no tiles, the same definitions in plain C++ with a summation order of
+ * its own (pairs i < j ascending; atoms ascending; vectors ascending).  Two parts, each skipped where its count is 0: Debye sums
+ * (B > 0) and cells (C > 0; cell_A types).  vec_ptr int64 [C+1] is always written; hkl, kabs, bin, rho are written where given and
+ * vec_cap holds them (call once with vec_cap 0 to learn K); count, mean_k and s where all three are given.  Also EGNN_EINVAL: a
+ * type outside [0, A), a graph_ptr that does not run from 0 to N (cell_ptr: to cell_N) or decreases, a coordinate that is not finite. */
+int egnn_sq_host(int B, int N, int A, const float* pos, const int32_t* type, const int32_t* graph_ptr, int Q, const double* q, double r_max,
+                 int window, double* debye, int C, int cell_N, int cell_A, const int32_t* cell_ptr, const double* lattice, const double* frac,
+                 const int32_t* cell_type, double q_max, double dq, int nbins, int64_t vec_cap, int64_t* vec_ptr, int32_t* hkl, double* kabs,
+                 int32_t* bin, double* rho, int64_t* count, double* mean_k, double* s);
+
 /* ---- the two small networks at the edge of the path ---------------------------------------------------
  * gamma_tilde(t_i) = l1(t_i) + l3(sigmoid(l2(l1(t_i)))) of GammaNetwork (SNR.py:50-52) with PositiveLinear's softplus weights
  * (:5-22) for n time points; d_l1_w [1], d_l2_w [hidden], d_l3_w [hidden] are the RAW parameters (l1.weight, l2.weight,

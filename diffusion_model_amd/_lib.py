@@ -28,7 +28,6 @@ CELL_CENTRE_BLOCK = 64    # kCellCentreBlock: the centres of one tile of egnn_ce
 PREALIGN_MIN_ATOMS = 5    # kPrealignMinAtoms of csrc/eval/assign_host.h: atom 0 and its four nearest neighbours
 
 
-
 _FLAGS_FALLBACK = b"FLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -fvisibility=hidden"
 
 
@@ -236,6 +235,11 @@ def check(rc):
 def ptr(t):
     """Device pointer of a tensor (None -> NULL)."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def host_ptr(a):
+    """Pointer of a contiguous numpy array, for the entries that read a host copy."""
+    return C.c_void_p(a.ctypes.data)
 
 
 def stream_ptr(stream=None):

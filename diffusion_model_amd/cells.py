@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._batch import block_index
 from .data import Batch, GraphData, make_graph
 
 
@@ -104,9 +105,7 @@ def _as_cells(cells) -> List[PeriodicCell]:
 def _bond_tiles(sizes) -> np.ndarray:
     """the work list of egnn_cell_bonds_count / _fill (include/egnn_amd.h): {cell, first centre} for every block of 64 centres"""
     sz = np.asarray(sizes, dtype=np.int64)
-    per = -(-sz // _lib.CELL_CENTRE_BLOCK)
-    ci = np.repeat(np.arange(sz.size, dtype=np.int64), per)
-    t = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
+    ci, t = block_index(-(-sz // _lib.CELL_CENTRE_BLOCK))
     return np.stack([ci, t * _lib.CELL_CENTRE_BLOCK], 1).astype(np.int32).reshape(-1, 2)
 
 
@@ -352,9 +351,7 @@ def ring_statistics(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centres=
 def _sq_vector_tiles(counts) -> np.ndarray:
     """the work list of egnn_sq_cell_rho (include/egnn_amd.h): {cell, first vector (local)} for every block of 256 vectors"""
     cnt = np.asarray(counts, dtype=np.int64)
-    per = -(-cnt // _lib.SQ_VECTOR_BLOCK)
-    ci = np.repeat(np.arange(cnt.size, dtype=np.int64), per)
-    t = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
+    ci, t = block_index(-(-cnt // _lib.SQ_VECTOR_BLOCK))
     return np.stack([ci, t * _lib.SQ_VECTOR_BLOCK], 1).astype(np.int32).reshape(-1, 2)
 
 

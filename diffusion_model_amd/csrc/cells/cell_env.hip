@@ -9,21 +9,11 @@
 //
 // A kernel trusts no index: tile, cell, centre, bond row, neighbour and shift code are checked against the extents of the arrays
 // before they are used, and every write is checked against the extent of its output.
-#include "../common.h"
+#include "../eval/eval_device.h"
 #include "cell_host.h"
 #include "cell_math.h"
 
 namespace egnn {
-
-__device__ __forceinline__ void cell_wave_sync() {   // one wavefront: its LDS operations complete in order (eval/structure.hip)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-__device__ __forceinline__ int cell_lane_prefix(unsigned long long mask, int lane) {
-  return __popcll(mask & ((1ull << lane) - 1ull));
-}
 
 // ---- periodic bond list ------------------------------------------------------------------------------------------------------
 // One workgroup of 256 threads per tile {cell, first centre}: 64 centres, 16 per wavefront, against the whole cell in chunks of
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(256) void cell_bond_kernel(const double* __restrict
     }
   }
   if (!FILL) {
-    cell_wave_sync();   // the wavefront reads what its lane 0 wrote
+    wave_sync();   // the wavefront reads what its lane 0 wrote
     for (int ci = wave * per_wave + lane; ci < ci_end; ci += 64) degree[lo + c0 + ci] = s_cnt[ci];
   }
 }
@@ -163,12 +153,12 @@ __global__ __launch_bounds__(256) void cell_env_kernel(const double* __restrict_
   }
   for (int t = lane; t < H; t += 64) table[t] = -1;
   const int key0 = (ctr - lo) * kCellShiftCodes + kCellCentreCode;
-  cell_wave_sync();
+  wave_sync();
   if (lane == 0) {
     list[0] = key0;
     table[((unsigned)key0 * 2654435761u) >> (32 - log_table)] = key0;
   }
-  cell_wave_sync();
+  wave_sync();
   int count = 1, begin = 0;
   for (int hop = 0; hop < shells && count <= max_atoms; ++hop) {
     const int end = count;
@@ -203,9 +193,9 @@ __global__ __launch_bounds__(256) void cell_env_kernel(const double* __restrict_
           }
         }
         const unsigned long long winners = __ballot(won);
-        if (won) list[count + cell_lane_prefix(winners, lane)] = fresh;   // count <= max_atoms here: below max_atoms + 64
+        if (won) list[count + lane_prefix(winners, lane)] = fresh;   // count <= max_atoms here: below max_atoms + 64
         count += __popcll(winners);
-        cell_wave_sync();
+        wave_sync();
       }
     }
     begin = end;
@@ -255,13 +245,12 @@ static size_t cell_env_lds_bytes(int max_atoms) {
 }
 
 // A launch that needs more dynamic LDS than a function is given by default (64 KiB; 81 KiB at max_atoms = 1024, a CU has 160 KiB)
-// raises the function's limit first: on the CURRENT device and at every such launch -- no process-wide flag that a second device
-// or a second thread would find already set.  The default max_atoms = 256 needs 21 KiB and makes no call.
+// raises the function's limit first, once per device (eval/lds_limit.h).  The default max_atoms = 256 needs 21 KiB and makes no
+// call.
 template <bool FILL>
 static int cell_env_configure(size_t lds_bytes) {
-  if (lds_bytes > 64u * 1024u)
-    EGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&cell_env_kernel<FILL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)cell_env_lds_bytes(kCellMaxEnvAtoms)));
+  static LdsLimitRecord raised;   // one per instantiation: one per kernel
+  if (lds_bytes > 64u * 1024u) return raise_lds_limit(raised, &cell_env_kernel<FILL>, cell_env_lds_bytes(kCellMaxEnvAtoms));
   return EGNN_OK;
 }
 
@@ -280,7 +269,7 @@ int egnn_cell_bonds_count(void* stream, int C, int N, const int32_t* cell_ptr, c
     return EGNN_EINVAL;
   }
   if (int rc = cell_batch_check(who, C, N, cell_ptr, lattice, cutoff)) return rc;
-  if (int rc = cell_tiles_check(who, d_tiles, n_tiles)) return rc;
+  if (int rc = tiles_check(who, d_tiles, n_tiles)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (N > 0) EGNN_HIP(hipMemsetAsync(d_degree, 0, sizeof(int32_t) * (size_t)N, st));
   if (n_tiles > 0)
@@ -301,7 +290,7 @@ int egnn_cell_bonds_fill(void* stream, int C, int N, const int32_t* cell_ptr, co
     return EGNN_EINVAL;
   }
   if (int rc = cell_batch_check(who, C, N, cell_ptr, lattice, cutoff)) return rc;
-  if (int rc = cell_tiles_check(who, d_tiles, n_tiles)) return rc;
+  if (int rc = tiles_check(who, d_tiles, n_tiles)) return rc;
   if (n_tiles > 0 && n_bonds > 0)
     hipLaunchKernelGGL(cell_bond_kernel<true>, dim3(n_tiles), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), d_frac, d_lattice,
                        d_cell_ptr, C, N, d_tiles, cutoff, d_row_ptr, n_bonds, (int*)nullptr, d_bond_atom, d_bond_shift);
@@ -343,7 +332,7 @@ int egnn_cell_env_fill(void* stream, int C, int N, int A, const int32_t* cell_pt
               "n_sites >= 0 entries of the four outputs)", who);
     return EGNN_EINVAL;
   }
-  if (int rc = cell_types_check(who, A)) return rc;
+  if (int rc = atom_types_check(who, A, kCellMaxTypes)) return rc;
   if (int rc = cell_env_params_check(who, M, shells, max_atoms, d_centre_cell, d_centre)) return rc;
   if (int rc = cell_batch_check(who, C, N, cell_ptr, lattice, 1e-300)) return rc;   // no cutoff here: a singular lattice is refused
   if (M == 0 || n_sites == 0) return EGNN_OK;

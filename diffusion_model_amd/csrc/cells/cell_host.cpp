@@ -2,7 +2,6 @@
 // egnn_cell_env_host -- the bond list and the shell clusters of a batch of cells computed on the CPU through cell_math.h, the text
 // the kernels compile.  No HIP call, no device code: checked (and run under the sanitizers, make asan) on a machine without a GPU.
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "cell_host.h"
@@ -14,11 +13,8 @@ int cell_batch_check(const char* who, int C, int N, const int32_t* cell_ptr, con
   if (C < 1 || N < 0 || !cell_ptr) { set_error("bad %s arguments (C >= 1, N >= 0, the host copy of cell_ptr given)", who); return EGNN_EINVAL; }
   if (!(cutoff > 0.0) || !(cutoff < 1e30)) { set_error("%s: cutoff must be positive and finite", who); return EGNN_EINVAL; }
   if (cell_ptr[0] != 0 || cell_ptr[C] != N) { set_error("%s: cell_ptr must run from 0 to N = %d", who, N); return EGNN_EINVAL; }
-  for (int c = 0; c < C; ++c) {
-    const long long n = (long long)cell_ptr[c + 1] - cell_ptr[c];
-    if (n < 0) { set_error("%s: cell_ptr decreases at cell %d", who, c); return EGNN_EINVAL; }
-    if (n > kCellMaxAtoms) { set_error("%s: cell %d has %lld atoms (at most %d)", who, c, n, kCellMaxAtoms); return EGNN_EINVAL; }
-  }
+  for (int c = 0; c < C; ++c)
+    if (int rc = ptr_step_check(who, "cell_ptr", "cell", cell_ptr, c, kCellMaxAtoms)) return rc;
   if (!lattice) return EGNN_OK;
   for (int c = 0; c < C; ++c) {
     double w[3];
@@ -32,11 +28,6 @@ int cell_batch_check(const char* who, int C, int N, const int32_t* cell_ptr, con
   return EGNN_OK;
 }
 
-int cell_tiles_check(const char* who, const void* tiles, int n_tiles) {
-  if (n_tiles < 0 || (n_tiles > 0 && !tiles)) { set_error("bad %s arguments (n_tiles >= 0 tiles given)", who); return EGNN_EINVAL; }
-  return EGNN_OK;
-}
-
 int cell_env_params_check(const char* who, int M, int shells, int max_atoms, const void* centre_cell, const void* centre) {
   if (M < 0 || (M > 0 && (!centre_cell || !centre))) { set_error("bad %s arguments (M >= 0 centres given)", who); return EGNN_EINVAL; }
   if (shells < 1 || shells > kCellMaxShells) { set_error("%s: shells %d (1 <= shells <= %d)", who, shells, kCellMaxShells); return EGNN_EINVAL; }
@@ -46,32 +37,6 @@ int cell_env_params_check(const char* who, int M, int shells, int max_atoms, con
   }
   return EGNN_OK;
 }
-
-int cell_types_check(const char* who, int A) {
-  if (A < 1 || A > kCellMaxTypes) { set_error("%s: %d atom types (1 <= A <= %d)", who, A, kCellMaxTypes); return EGNN_EINVAL; }
-  return EGNN_OK;
-}
-
-namespace {
-
-// scratch of the host statement.  Not std::vector: a constructor or push_back the compiler does not inline is instantiated as a
-// weak symbol with default visibility, and the library exports nothing but the header's functions (tests/test_cabi_and_host.py)
-template <typename T>
-struct Scratch {
-  T* p;
-  explicit Scratch(size_t n) : p(static_cast<T*>(calloc(n ? n : 1, sizeof(T)))) {}
-  ~Scratch() { free(p); }
-  Scratch(const Scratch&) = delete;
-  Scratch& operator=(const Scratch&) = delete;
-  bool reset(size_t n) {
-    free(p);
-    p = static_cast<T*>(calloc(n ? n : 1, sizeof(T)));
-    return p != nullptr;
-  }
-  T& operator[](size_t i) { return p[i]; }
-};
-
-}  // namespace
 
 }  // namespace egnn
 
@@ -88,7 +53,7 @@ int egnn_cell_env_host(int C, int A, const int32_t* cell_ptr, const double* latt
     set_error("bad %s arguments (C >= 1; cell_ptr, lattice, frac, type, bond_ptr and env_size given)", who);
     return EGNN_EINVAL;
   }
-  if (int rc = cell_types_check(who, A)) return rc;
+  if (int rc = atom_types_check(who, A, kCellMaxTypes)) return rc;
   if (int rc = cell_env_params_check(who, M, shells, max_atoms, centre_cell, centre)) return rc;
   const int N = cell_ptr[C];
   if (int rc = cell_batch_check(who, C, N, cell_ptr, lattice, cutoff)) return rc;

@@ -1,7 +1,7 @@
 // Host-only argument validation of the periodic-cell entries (cell_env.hip) and their host statement egnn_cell_env_host.  Plain C++
 // beside host_logic: it is also compiled into the CPU-only sanitizer library (make asan).
 #pragma once
-#include "../host_logic.h"
+#include "../eval/eval_host.h"
 
 namespace egnn {
 
@@ -9,8 +9,6 @@ namespace egnn {
 // cell_ptr and lattice are HOST arrays here: sizes, monotony, cutoff > 0, a singular lattice and a perpendicular width below the
 // cutoff are refused, naming the cell.  lattice may be null where an entry reads no lattice (the environment count).
 int cell_batch_check(const char* who, int C, int N, const int32_t* cell_ptr, const double* lattice, double cutoff);
-int cell_tiles_check(const char* who, const void* tiles, int n_tiles);
 int cell_env_params_check(const char* who, int M, int shells, int max_atoms, const void* centre_cell, const void* centre);
-int cell_types_check(const char* who, int A);
 
 }  // namespace egnn

@@ -15,14 +15,7 @@
 //  * environment of centre i to depth `shells`: the sites reachable from (i, 0) in at most `shells` bonds, the centre first, the
 //    others by ascending key.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define CELL_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define CELL_HD inline
-#endif
+#include "../eval/eval_math.h"
 
 namespace egnn {
 
@@ -38,19 +31,19 @@ constexpr int kCellChunk = 1024;            // bond tile: neighbour atoms staged
 constexpr int kCellEnvWaves = 4;            // environment tile: centres, one wavefront each
 constexpr int kCellEnvSlack = 64;           // sites one breadth-first step of a wavefront can append beyond max_atoms
 
-CELL_HD double cell_wrap(double f) {
+EGNN_HD double cell_wrap(double f) {
   const double w = f - floor(f);
   return w < 1.0 ? w : 0.0;
 }
 
-CELL_HD int cell_shift_code(int sx, int sy, int sz) { return ((sx + 4) * kCellShiftSpan + (sy + 4)) * kCellShiftSpan + (sz + 4); }
-CELL_HD void cell_shift_decode(int code, int* s) {
+EGNN_HD int cell_shift_code(int sx, int sy, int sz) { return ((sx + 4) * kCellShiftSpan + (sy + 4)) * kCellShiftSpan + (sz + 4); }
+EGNN_HD void cell_shift_decode(int code, int* s) {
   s[0] = code / (kCellShiftSpan * kCellShiftSpan) - 4;
   s[1] = code / kCellShiftSpan % kCellShiftSpan - 4;
   s[2] = code % kCellShiftSpan - 4;
 }
 // the code of the sum of two shifts, -1 where a component leaves [-4, 4]
-CELL_HD int cell_shift_add(int code_a, int code_b) {
+EGNN_HD int cell_shift_add(int code_a, int code_b) {
   int a[3], b[3];
   cell_shift_decode(code_a, a);
   cell_shift_decode(code_b, b);
@@ -61,20 +54,20 @@ CELL_HD int cell_shift_add(int code_a, int code_b) {
   return cell_shift_code(a[0], a[1], a[2]);
 }
 
-CELL_HD double cell_delta(double wj, double wi, int s) { return (wj - wi) + (double)s; }
-CELL_HD void cell_cartesian(double d0, double d1, double d2, const double* L, double* r) {
+EGNN_HD double cell_delta(double wj, double wi, int s) { return (wj - wi) + (double)s; }
+EGNN_HD void cell_cartesian(double d0, double d1, double d2, const double* L, double* r) {
   for (int x = 0; x < 3; ++x) r[x] = (d0 * L[x] + d1 * L[3 + x]) + d2 * L[6 + x];
 }
-CELL_HD double cell_norm2(const double* r) { return (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]; }
+EGNN_HD double cell_norm2(const double* r) { return (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]; }
 
 // vector from the wrapped centre (fractional wi) to site (wj, s)
-CELL_HD void cell_site_vector(const double* wj, const double* wi, const int* s, const double* L, double* r) {
+EGNN_HD void cell_site_vector(const double* wj, const double* wi, const int* s, const double* L, double* r) {
   cell_cartesian(cell_delta(wj[0], wi[0], s[0]), cell_delta(wj[1], wi[1], s[1]), cell_delta(wj[2], wi[2], s[2]), L, r);
 }
 
 // perpendicular widths w_k = |det L| / |a_{k+1} x a_{k+2}|; false for a lattice that is singular (|det| <= 1e-9 |a||b||c|) or not
 // finite
-CELL_HD bool cell_widths(const double* L, double* w) {
+EGNN_HD bool cell_widths(const double* L, double* w) {
   const double* a = L;
   const double* b = L + 3;
   const double* c = L + 6;

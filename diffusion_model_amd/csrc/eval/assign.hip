@@ -21,7 +21,7 @@
 
 #include <limits.h>
 
-#include "../common.h"
+#include "eval_device.h"
 #include "kabsch_math.h"
 
 namespace egnn {
@@ -46,12 +46,6 @@ __device__ __forceinline__ void wave_argmin(T& v, int& j) {   // butterfly: ever
   }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 struct AssignPartial {
   double v;
   int j;
@@ -63,9 +57,7 @@ struct AssignPartial {
 template <int WAVES>
 __device__ __forceinline__ void solver_sync() {
   if constexpr (WAVES == 1) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    wave_sync();
   } else {
     __syncthreads();
   }

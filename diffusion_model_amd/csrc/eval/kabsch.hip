@@ -27,16 +27,10 @@
 //    no dependence on arrival order.
 #include "kabsch.h"
 
-#include "../common.h"
+#include "eval_device.h"
 
 namespace egnn {
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);   // butterfly: every lane ends with the same bits
-  return v;
-}
 
 // Kabsch fit of n atom pairs by one wavefront: P row order[i] (order == nullptr: row i) against Q row i.
 // All lanes return the same R [9], t [3] = c_Q - c_P and rmsd; the backward also takes the centres and the factors of the fit.

@@ -15,20 +15,14 @@
 //    iterate is itself an upper bound and the caller may stop as soon as one drops below the score it has to beat.
 //  * kabsch_fit_backward: the derivative of kabsch_fit, dL/dH from dL/dR, from the same factors (for the RMSD loss).
 #pragma once
-#include <math.h>
-
-#if defined(__HIPCC__)
-#define KABSCH_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define KABSCH_HD inline
-#endif
+#include "eval_math.h"
 
 namespace egnn {
 
 constexpr int kKabschCentroid = 0, kKabschFirst = 1;   // center
 constexpr int kKabschFlipRow = 0, kKabschFlipColumn = 1;
 
-KABSCH_HD void kabsch_jacobi_pair(double* A, double* V, int p, int q, bool& rotated) {
+EGNN_HD void kabsch_jacobi_pair(double* A, double* V, int p, int q, bool& rotated) {
   double alpha = 0.0, beta = 0.0, gamma = 0.0;
   for (int r = 0; r < 3; ++r) {
     alpha += A[3 * r + p] * A[3 * r + p];
@@ -50,7 +44,7 @@ KABSCH_HD void kabsch_jacobi_pair(double* A, double* V, int p, int q, bool& rota
   }
 }
 
-KABSCH_HD void kabsch_swap_cols(double* A, double* V, double* s, int i, int j) {
+EGNN_HD void kabsch_swap_cols(double* A, double* V, double* s, int i, int j) {
   if (s[i] >= s[j]) return;
   double t = s[i]; s[i] = s[j]; s[j] = t;
   for (int r = 0; r < 3; ++r) {
@@ -69,7 +63,7 @@ struct KabschFactors {
 };
 
 // R [9] row-major such that R p_i ~ q_i, and the factors it was formed from
-KABSCH_HD void kabsch_fit_factors(const double* H, int flip, double* R, KabschFactors& F) {
+EGNN_HD void kabsch_fit_factors(const double* H, int flip, double* R, KabschFactors& F) {
   double A[9], V[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
   for (int k = 0; k < 9; ++k) A[k] = H[k];
   for (int sweep = 0; sweep < 16; ++sweep) {
@@ -122,7 +116,7 @@ KABSCH_HD void kabsch_fit_factors(const double* H, int flip, double* R, KabschFa
 }
 
 // R [9] row-major such that R p_i ~ q_i
-KABSCH_HD void kabsch_fit(const double* H, int flip, double* R) {
+EGNN_HD void kabsch_fit(const double* H, int flip, double* R) {
   KabschFactors F;
   kabsch_fit_factors(H, flip, R, F);
 }
@@ -134,7 +128,7 @@ KABSCH_HD void kabsch_fit(const double* H, int flip, double* R) {
 // No 1 / (s_i^2 - s_j^2): the denominators are s_i + s_j, which with the signed s[2] is sigma_i - sigma_3 in a row-flip reflection
 // case.  A term whose denominator is at most 1e-12 s[0] in magnitude is dropped (kabsch_fit's rank threshold: the forward
 // completes that direction by a fixed rule, which is locally constant), so the result is finite for every H.
-KABSCH_HD void kabsch_fit_backward_factors(const KabschFactors& F, const double* Rbar, double* Hbar) {
+EGNN_HD void kabsch_fit_backward_factors(const KabschFactors& F, const double* Rbar, double* Hbar) {
   const double j[3] = {1.0, 1.0, F.w3};
   double T[9], K[9], M[9];
   for (int i = 0; i < 3; ++i)     // T = V^T J Rbar
@@ -158,7 +152,7 @@ KABSCH_HD void kabsch_fit_backward_factors(const KabschFactors& F, const double*
     for (int c = 0; c < 3; ++c) Hbar[3 * r + c] = T[3 * r] * F.V[3 * c] + T[3 * r + 1] * F.V[3 * c + 1] + T[3 * r + 2] * F.V[3 * c + 2];
 }
 
-KABSCH_HD void kabsch_fit_backward(const double* H, int flip, const double* Rbar, double* Hbar) {
+EGNN_HD void kabsch_fit_backward(const double* H, int flip, const double* Rbar, double* Hbar) {
   double R[9];
   KabschFactors F;
   kabsch_fit_factors(H, flip, R, F);
@@ -166,7 +160,7 @@ KABSCH_HD void kabsch_fit_backward(const double* H, int flip, const double* Rbar
 }
 
 // -> the largest eigenvalue of Horn's matrix of H, or -1 as soon as an iterate (an upper bound of it) is below `beat`
-KABSCH_HD double kabsch_trace(const double* H, double beat) {
+EGNN_HD double kabsch_trace(const double* H, double beat) {
   double a = 0.0;
   for (int k = 0; k < 9; ++k) a += H[k] * H[k];
   double x = sqrt(3.0 * a) * (1.0 + 1e-15);

@@ -8,16 +8,13 @@
 //
 // The kernel trusts no entry it reads: a centre is checked against N, a row against E, a neighbour against N, a shift against
 // {-1, 0, 1}, an angle range against n_angles.
-#include <atomic>
-
-#include "../common.h"
+#include "eval_device.h"
 #include "rings_host.h"
 #include "rings_math.h"
 
 namespace egnn {
 
 constexpr int kRingThreads = 256;
-constexpr int kRingMaxDevices = 64;   // devices whose raised LDS limit is remembered (beyond: set at every call)
 
 // ---- one search per workgroup -----------------------------------------------------------------------------------------------------
 // Workgroup (m, p) runs the search of centre m from row position p (rings_math.h); p >= degree - 1 has nothing to do.  The labels
@@ -205,16 +202,9 @@ int egnn_rings(void* stream, int N, const int32_t* d_row_ptr, int E, const int32
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int slots = ring_slots(max_sites);
   const size_t lds = (size_t)slots * (sizeof(uint64_t) + sizeof(int32_t)) + 2 * (size_t)max_sites * sizeof(uint16_t);
-  // up to 112 KiB beside 0.5 KiB of static LDS; a CU has 160 KiB.  The limit belongs to the function ON ONE DEVICE (topo.hip)
-  static std::atomic<bool> configured[kRingMaxDevices];
-  int device = 0;
-  EGNN_HIP(hipGetDevice(&device));
-  const bool known = device >= 0 && device < kRingMaxDevices;
-  if (!known || !configured[device].load(std::memory_order_acquire)) {
-    EGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rings_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)((size_t)ring_slots(kRingMaxSites) * 12 + 4 * (size_t)kRingMaxSites)));
-    if (known) configured[device].store(true, std::memory_order_release);
-  }
+  // up to 112 KiB beside 0.5 KiB of static LDS; a CU has 160 KiB
+  static LdsLimitRecord raised;
+  if (int rc = raise_lds_limit(raised, &rings_kernel, (size_t)ring_slots(kRingMaxSites) * 12 + 4 * (size_t)kRingMaxSites)) return rc;
   if (M > 0) EGNN_HIP(hipMemsetAsync(d_overflow, 0, sizeof(int32_t) * (size_t)M, st));
   if (n_angles > 0) {   // a centre the kernel refuses (outside N, a row outside E) leaves zeros
     EGNN_HIP(hipMemsetAsync(d_size, 0, sizeof(int32_t) * (size_t)n_angles, st));

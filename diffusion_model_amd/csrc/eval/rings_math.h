@@ -27,13 +27,7 @@
 // max_size - 2 <= 30 bonds of |shift| <= 1 reach |s| <= 31.  The level of a labelled site rides in the top byte of its table
 // entry, so that one 64-bit compare-and-swap labels a site; kRingEmpty (all ones) is no entry.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define RING_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define RING_HD inline
-#endif
+#include "eval_math.h"
 
 #define RING_MAX_SITES 4096
 
@@ -49,42 +43,42 @@ constexpr uint64_t kRingEmpty = ~0ull;
 constexpr uint64_t kRingKeyMask = (1ull << 50) - 1ull;
 constexpr int kRingLevelShift = 56;
 
-RING_HD bool ring_shift_ok(int s) { return s >= -1 && s <= 1; }
+EGNN_HD bool ring_shift_ok(int s) { return s >= -1 && s <= 1; }
 
-RING_HD uint64_t ring_key(int atom, int sx, int sy, int sz) {
+EGNN_HD uint64_t ring_key(int atom, int sx, int sy, int sz) {
   return ((uint64_t)(uint32_t)atom << 18) | ((uint64_t)(uint32_t)(sx + 32) << 12) | ((uint64_t)(uint32_t)(sy + 32) << 6) |
          (uint64_t)(uint32_t)(sz + 32);
 }
-RING_HD int ring_key_atom(uint64_t key) { return (int)(uint32_t)((key & kRingKeyMask) >> 18); }
-RING_HD int ring_key_sx(uint64_t key) { return (int)((key >> 12) & 63) - 32; }
-RING_HD int ring_key_sy(uint64_t key) { return (int)((key >> 6) & 63) - 32; }
-RING_HD int ring_key_sz(uint64_t key) { return (int)(key & 63) - 32; }
+EGNN_HD int ring_key_atom(uint64_t key) { return (int)(uint32_t)((key & kRingKeyMask) >> 18); }
+EGNN_HD int ring_key_sx(uint64_t key) { return (int)((key >> 12) & 63) - 32; }
+EGNN_HD int ring_key_sy(uint64_t key) { return (int)((key >> 6) & 63) - 32; }
+EGNN_HD int ring_key_sz(uint64_t key) { return (int)(key & 63) - 32; }
 
 // the site bond (atom, shift) leads to from the site `key`; shift = NULL for clusters
-RING_HD uint64_t ring_step(uint64_t key, int atom, const int32_t* shift) {
+EGNN_HD uint64_t ring_step(uint64_t key, int atom, const int32_t* shift) {
   if (!shift) return ring_key(atom, ring_key_sx(key), ring_key_sy(key), ring_key_sz(key));
   return ring_key(atom, ring_key_sx(key) + shift[0], ring_key_sy(key) + shift[1], ring_key_sz(key) + shift[2]);
 }
 
-RING_HD uint64_t ring_entry(uint64_t key, int level) { return key | ((uint64_t)level << kRingLevelShift); }
-RING_HD int ring_entry_level(uint64_t entry) { return (int)(entry >> kRingLevelShift); }
+EGNN_HD uint64_t ring_entry(uint64_t key, int level) { return key | ((uint64_t)level << kRingLevelShift); }
+EGNN_HD int ring_entry_level(uint64_t entry) { return (int)(entry >> kRingLevelShift); }
 
-RING_HD int ring_sat_add(int a, int b) {   // a, b >= 0
+EGNN_HD int ring_sat_add(int a, int b) {   // a, b >= 0
   const int64_t s = (int64_t)a + (int64_t)b;
   return s > kRingCountMax ? kRingCountMax : (int)s;
 }
 
-RING_HD int ring_angles(int degree) { return degree * (degree - 1) / 2; }
+EGNN_HD int ring_angles(int degree) { return degree * (degree - 1) / 2; }
 // the first angle of row position p in a centre of degree d (angles in lexicographic order of (p, q))
-RING_HD int ring_angle_first(int p, int d) { return p * d - p * (p + 1) / 2; }
+EGNN_HD int ring_angle_first(int p, int d) { return p * d - p * (p + 1) / 2; }
 
-RING_HD int ring_slots(int max_sites) {
+EGNN_HD int ring_slots(int max_sites) {
   int s = kRingMinSlots;
   while (s < 2 * max_sites) s <<= 1;
   return s;
 }
 
-RING_HD uint32_t ring_hash(uint64_t key) {   // the finaliser of splitmix64
+EGNN_HD uint32_t ring_hash(uint64_t key) {   // the finaliser of splitmix64
   key ^= key >> 30; key *= 0xbf58476d1ce4e5b9ull;
   key ^= key >> 27; key *= 0x94d049bb133111ebull;
   key ^= key >> 31;

@@ -5,24 +5,15 @@
 // No kernel has an atomic: every output is the sum of one thread (or of one wavefront's fixed butterfly), so a repeated call is
 // bitwise reproducible.  A kernel trusts no entry it reads: a centre is checked against N, its graph against N, a type against
 // A, a pair against the row counts.
-#include <atomic>
-
-#include "../common.h"
+#include "eval_device.h"
 #include "soap_host.h"
 #include "soap_math.h"
 
 namespace egnn {
 
 constexpr int kSoapThreads = 1024;    // threads of a descriptor workgroup (16 wavefronts share the staging of a chunk)
-constexpr int kSoapMaxDevices = 64;   // devices whose raised LDS limit is remembered (beyond: set at every call)
 constexpr int kSoapGramA = 4;         // rows of a in one tile of the cosine matrix: one per wavefront
 constexpr int kSoapGramB = 8;         // rows of b in one tile: eight running sums per lane
-
-__device__ __forceinline__ double soap_wave_sum(double x) {   // the butterfly of soap_row_sum: every lane ends with the sum
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
 
 // LDS of the descriptor kernel, in doubles: coefficients [A][n_max][LM] | solid harmonics [chunk][LM] | radial values
 // [chunk][n_max (l_max+1)] | dx, dy, dz, d2 [chunk][4]; then the species of the chunk's atoms, int [chunk]
@@ -164,9 +155,9 @@ __global__ __launch_bounds__(256) void soap_cosine_kernel(const double* __restri
     na += u * u;
     nb += v * v;
   }
-  dot = soap_wave_sum(dot);
-  na = soap_wave_sum(na);
-  nb = soap_wave_sum(nb);
+  dot = wave_sum(dot);
+  na = wave_sum(na);
+  nb = wave_sum(nb);
   if (lane == 0) out[p] = soap_cosine(dot, na, nb);
 }
 
@@ -177,7 +168,7 @@ __global__ __launch_bounds__(256) void soap_norm_kernel(const double* __restrict
   const double* x = a + (size_t)r * F;
   double na = 0.0;
   for (int f = lane; f < F; f += 64) na += x[f] * x[f];
-  na = soap_wave_sum(na);
+  na = wave_sum(na);
   if (lane == 0) out[r] = na;
 }
 
@@ -202,7 +193,7 @@ __global__ __launch_bounds__(256) void soap_gram_kernel(const double* __restrict
   const double na = norm_a[ra];
 #pragma unroll
   for (int q = 0; q < kSoapGramB; ++q) {
-    const double d = soap_wave_sum(dot[q]);
+    const double d = wave_sum(dot[q]);
     if (lane == 0 && rb0 + q < rows_b) gram[(size_t)ra * rows_b + rb0 + q] = soap_cosine(d, na, norm_b[rb0 + q]);
   }
 }
@@ -224,7 +215,7 @@ __global__ __launch_bounds__(256) void soap_nearest_kernel(const float* __restri
     const float* y = reference + (size_t)r * S;
     double sum = 0.0;
     for (int s = lane; s < S; s += 64) sum += soap_sq_diff(x[s], y[s]);
-    soap_best_insert(&best, soap_wave_sum(sum) / (double)S, r);
+    soap_best_insert(&best, wave_sum(sum) / (double)S, r);
   }
   if (lane == 0) {
 #pragma unroll
@@ -248,17 +239,9 @@ int egnn_soap_descriptor(void* stream, int B, int N, int A, const float* d_pos, 
     return rc;
   if (!d_centres) { set_error("bad %s arguments (d_centres given)", who); return EGNN_EINVAL; }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // up to 136 KiB of dynamic LDS; a CU has 160 KiB.  The limit belongs to the function ON ONE DEVICE, so it is raised once for
-  // every device this entry is called on (topo.hip: egnn_topo_paths).
-  static std::atomic<bool> configured[kSoapMaxDevices];
-  int device = 0;
-  EGNN_HIP(hipGetDevice(&device));
-  const bool known = device >= 0 && device < kSoapMaxDevices;
-  if (!known || !configured[device].load(std::memory_order_acquire)) {
-    EGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&soap_descriptor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)soap_lds_bytes(kSoapMaxTypes, kSoapMaxN, kSoapMaxL)));
-    if (known) configured[device].store(true, std::memory_order_release);
-  }
+  // up to 136 KiB of dynamic LDS; a CU has 160 KiB
+  static LdsLimitRecord raised;
+  if (int rc = raise_lds_limit(raised, &soap_descriptor_kernel, soap_lds_bytes(kSoapMaxTypes, kSoapMaxN, kSoapMaxL))) return rc;
   hipLaunchKernelGGL(soap_descriptor_kernel, dim3(n_centres), dim3(kSoapThreads), soap_lds_bytes(A, n_max, l_max), st, d_pos, d_type,
                      d_graph_ptr, B, N, A, n_max, l_max, neighbour_cut * neighbour_cut, d_tables, d_centres, n_centres, d_desc, d_coeff);
   EGNN_HIP(hipGetLastError());

@@ -16,7 +16,7 @@ int soap_descriptor_check(const char* who, int B, int N, int A, const void* pos,
     set_error("bad %s arguments (B, N, n_centres >= 1; pos, type, graph_ptr, tables, centres and desc given)", who);
     return EGNN_EINVAL;
   }
-  if (A < 1 || A > kSoapMaxTypes) { set_error("%s: %d atom types (1 <= A <= %d)", who, A, kSoapMaxTypes); return EGNN_EINVAL; }
+  if (int rc = atom_types_check(who, A, kSoapMaxTypes)) return rc;
   if (n_max < 1 || n_max > kSoapMaxN) { set_error("%s: n_max %d (1 <= n_max <= %d)", who, n_max, kSoapMaxN); return EGNN_EINVAL; }
   if (l_max < 0 || l_max > kSoapMaxL) { set_error("%s: l_max %d (0 <= l_max <= %d)", who, l_max, kSoapMaxL); return EGNN_EINVAL; }
   if (!soap_cut_ok(neighbour_cut)) { set_error("%s: neighbour_cut must be positive and finite", who); return EGNN_EINVAL; }
@@ -91,8 +91,7 @@ int egnn_soap_host(int B, int N, int A, const float* pos, const int32_t* type, c
         return EGNN_EINVAL;
       }
     }
-    for (int i = 0; i < N; ++i)
-      if (type[i] < 0 || type[i] >= A) { set_error("%s: atom %d has type %d outside [0, %d)", who, i, type[i], A); return EGNN_EINVAL; }
+    if (int rc = type_range_check(who, type, 0, N, A)) return rc;
     const int L1 = l_max + 1, LM = soap_lm_count(l_max), nF = soap_feature_count(A, n_max, l_max);
     const double cut2 = neighbour_cut * neighbour_cut;
     const double* norm = tables + soap_table_norm(n_max, l_max);

@@ -3,7 +3,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "../host_logic.h"
+#include "eval_host.h"
 
 namespace egnn {
 

@@ -36,14 +36,7 @@
 //    equal.  The k smallest over the references whose group differs from the target's (a group < 0 matches nothing) ascending,
 //    ties to the lower reference index, missing entries index -1 and mse +inf.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define SOAP_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define SOAP_HD inline
-#endif
+#include "eval_math.h"
 
 namespace egnn {
 
@@ -53,30 +46,30 @@ constexpr int kSoapMaxL = 10;       // l_max
 constexpr int kSoapMaxK = 8;        // nearest spectra kept
 constexpr int kSoapChunk = 32;      // neighbours staged at a time by the descriptor kernel
 
-SOAP_HD int soap_lm_count(int l_max) { return (l_max + 1) * (l_max + 1); }
-SOAP_HD int soap_feature_count(int A, int n_max, int l_max) {
+EGNN_HD int soap_lm_count(int l_max) { return (l_max + 1) * (l_max + 1); }
+EGNN_HD int soap_feature_count(int A, int n_max, int l_max) {
   return (A * (n_max * (n_max + 1) / 2) + A * (A - 1) / 2 * n_max * n_max) * (l_max + 1);
 }
-SOAP_HD bool soap_config_ok(int A, int n_max, int l_max) {
+EGNN_HD bool soap_config_ok(int A, int n_max, int l_max) {
   return A >= 1 && A <= kSoapMaxTypes && n_max >= 1 && n_max <= kSoapMaxN && l_max >= 0 && l_max <= kSoapMaxL;
 }
-SOAP_HD bool soap_cut_ok(double cut) { return cut > 0.0 && cut < 1e150; }   // positive, finite, not NaN, and its square finite
+EGNN_HD bool soap_cut_ok(double cut) { return cut > 0.0 && cut < 1e150; }   // positive, finite, not NaN, and its square finite
 
 // offsets into the table buffer
-SOAP_HD int soap_table_gamma(int n_max, int l_max) { return n_max * (l_max + 1); }
-SOAP_HD int soap_table_beta(int n_max, int l_max) { return 2 * n_max * (l_max + 1); }
-SOAP_HD int soap_table_norm(int n_max, int l_max) { return soap_table_beta(n_max, l_max) + (l_max + 1) * n_max * n_max; }
-SOAP_HD int soap_table_weight(int n_max, int l_max) { return soap_table_norm(n_max, l_max) + soap_lm_count(l_max); }
-SOAP_HD int soap_table_count(int n_max, int l_max) { return soap_table_weight(n_max, l_max) + (l_max + 1); }
+EGNN_HD int soap_table_gamma(int n_max, int l_max) { return n_max * (l_max + 1); }
+EGNN_HD int soap_table_beta(int n_max, int l_max) { return 2 * n_max * (l_max + 1); }
+EGNN_HD int soap_table_norm(int n_max, int l_max) { return soap_table_beta(n_max, l_max) + (l_max + 1) * n_max * n_max; }
+EGNN_HD int soap_table_weight(int n_max, int l_max) { return soap_table_norm(n_max, l_max) + soap_lm_count(l_max); }
+EGNN_HD int soap_table_count(int n_max, int l_max) { return soap_table_weight(n_max, l_max) + (l_max + 1); }
 
-SOAP_HD int soap_l_of(int lm) {
+EGNN_HD int soap_l_of(int lm) {
   int l = 0;
   while ((l + 1) * (l + 1) <= lm) ++l;
   return l;
 }
 
 // d2 and the differences neighbour - centre
-SOAP_HD double soap_dist2(const float* centre, const float* q, double* dx, double* dy, double* dz) {
+EGNN_HD double soap_dist2(const float* centre, const float* q, double* dx, double* dy, double* dz) {
   *dx = (double)q[0] - (double)centre[0];
   *dy = (double)q[1] - (double)centre[1];
   *dz = (double)q[2] - (double)centre[2];
@@ -84,7 +77,7 @@ SOAP_HD double soap_dist2(const float* centre, const float* q, double* dx, doubl
 }
 
 // radial value of neighbour at d2 for entry q = n (l_max+1) + l of the K and gamma tables
-SOAP_HD double soap_radial(const double* tables, int n_max, int l_max, int q, double d2) {
+EGNN_HD double soap_radial(const double* tables, int n_max, int l_max, int q, double d2) {
   const double g = tables[soap_table_gamma(n_max, l_max) + q] * d2;
   return tables[q] * exp(-g);
 }
@@ -92,7 +85,7 @@ SOAP_HD double soap_radial(const double* tables, int n_max, int l_max, int q, do
 // R_lm for one m >= 0 and l = m .. l_max, written to out[l*l + l + m] and (m > 0) out[l*l + l - m].
 //   (x + i y)^m = ca + i sa by m complex products;  P_m^m = (2m-1)!!,  P_l^m = ((2l-1) z P_(l-1)^m - (l+m-1) r2 P_(l-2)^m) / (l-m)
 // (the associated Legendre function times d^(l-m) / sin^m, without the Condon-Shortley sign), R_lm = (N_lm P_l^m) * ca or sa.
-SOAP_HD void soap_solid_column(double x, double y, double z, double r2, int m, int l_max, const double* norm, double* out) {
+EGNN_HD void soap_solid_column(double x, double y, double z, double r2, int m, int l_max, const double* norm, double* out) {
   double ca = 1.0, sa = 0.0, pmm = 1.0;
   for (int k = 1; k <= m; ++k) {
     const double na = ca * x - sa * y, nb = ca * y + sa * x;
@@ -117,7 +110,7 @@ SOAP_HD void soap_solid_column(double x, double y, double z, double r2, int m, i
 }
 
 // feature f -> (Z1, Z2, n, n', l)
-SOAP_HD void soap_feature_decode(int f, int A, int n_max, int l_max, int* z1, int* z2, int* n, int* np, int* l) {
+EGNN_HD void soap_feature_decode(int f, int A, int n_max, int l_max, int* z1, int* z2, int* n, int* np, int* l) {
   const int L1 = l_max + 1, same = n_max * (n_max + 1) / 2 * L1, diff = n_max * n_max * L1;
   int a = 0, b = 0;
   for (;;) {
@@ -139,7 +132,7 @@ SOAP_HD void soap_feature_decode(int f, int A, int n_max, int l_max, int* z1, in
 }
 
 // one power-spectrum entry from the coefficients c [A][n_max][(l_max+1)^2] of one centre
-SOAP_HD double soap_power_entry(const double* c, const double* tables, int f, int A, int n_max, int l_max) {
+EGNN_HD double soap_power_entry(const double* c, const double* tables, int f, int A, int n_max, int l_max) {
   int z1, z2, n, np, l;
   soap_feature_decode(f, A, n_max, l_max, &z1, &z2, &n, &np, &l);
   const int LM = soap_lm_count(l_max);
@@ -151,7 +144,7 @@ SOAP_HD double soap_power_entry(const double* c, const double* tables, int f, in
 }
 
 // the butterfly of soap_row_sum on 64 partials held in an array (the host side of a wavefront's __shfl_xor steps)
-SOAP_HD double soap_butterfly(double* partial) {
+EGNN_HD double soap_butterfly(double* partial) {
   double next[64];
   for (int off = 32; off >= 1; off >>= 1) {
     for (int q = 0; q < 64; ++q) next[q] = partial[q] + partial[q ^ off];
@@ -160,21 +153,21 @@ SOAP_HD double soap_butterfly(double* partial) {
   return partial[0];
 }
 
-SOAP_HD double soap_row_dot(const double* a, const double* b, long F) {
+EGNN_HD double soap_row_dot(const double* a, const double* b, long F) {
   double partial[64];
   for (int q = 0; q < 64; ++q) partial[q] = 0.0;
   for (long f = 0; f < F; ++f) partial[f & 63] += a[f] * b[f];
   return soap_butterfly(partial);
 }
 
-SOAP_HD double soap_cosine(double dot, double na, double nb) { return dot / (sqrt(na) * sqrt(nb)); }
+EGNN_HD double soap_cosine(double dot, double na, double nb) { return dot / (sqrt(na) * sqrt(nb)); }
 
-SOAP_HD double soap_sq_diff(float t, float r) {
+EGNN_HD double soap_sq_diff(float t, float r) {
   const double d = (double)t - (double)r;
   return d * d;
 }
 
-SOAP_HD double soap_row_mse(const float* t, const float* r, int S) {
+EGNN_HD double soap_row_mse(const float* t, const float* r, int S) {
   double partial[64];
   for (int q = 0; q < 64; ++q) partial[q] = 0.0;
   for (int s = 0; s < S; ++s) partial[s & 63] += soap_sq_diff(t[s], r[s]);
@@ -187,11 +180,11 @@ struct SoapBest {
   int idx[kSoapMaxK];
 };
 
-SOAP_HD void soap_best_clear(SoapBest* b) {
+EGNN_HD void soap_best_clear(SoapBest* b) {
   for (int q = 0; q < kSoapMaxK; ++q) { b->mse[q] = INFINITY; b->idx[q] = -1; }
 }
 
-SOAP_HD void soap_best_insert(SoapBest* b, double mse, int r) {
+EGNN_HD void soap_best_insert(SoapBest* b, double mse, int r) {
   bool moving = false;
 #if defined(__HIPCC__)
 #pragma unroll
@@ -209,6 +202,6 @@ SOAP_HD void soap_best_insert(SoapBest* b, double mse, int r) {
   }
 }
 
-SOAP_HD bool soap_excluded(int target_group, int reference_group) { return target_group >= 0 && target_group == reference_group; }
+EGNN_HD bool soap_excluded(int target_group, int reference_group) { return target_group >= 0 && target_group == reference_group; }
 
 }  // namespace egnn

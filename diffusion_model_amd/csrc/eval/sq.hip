@@ -8,31 +8,16 @@
 //
 // Work lists come from the caller (built from the sizes on the host).  A kernel trusts no entry: graph / cell, blocks and offsets
 // are checked against graph_ptr / vec_ptr / the plan, and every index a kernel forms lies inside the arrays the entry was given.
-#include "../common.h"
+#include "eval_device.h"
 #include "sq_host.h"
 #include "sq_math.h"
 
 namespace egnn {
 
 // ---- Debye sums ----------------------------------------------------------------------------------------------------------------
-// tile {graph, first atom i, first atom j} (local indices): the pairs i < j of a 64 x 256 block
-struct SqTile {
-  int g, lo, c0, j0, nc, nj;
-};
-
-__device__ __forceinline__ bool sq_tile_read(const int* __restrict__ tiles, int t, const int* __restrict__ graph_ptr, int B, SqTile* T) {
-  T->g = tiles[3 * t];
-  T->c0 = tiles[3 * t + 1];
-  T->j0 = tiles[3 * t + 2];
-  if (T->g < 0 || T->g >= B) return false;
-  T->lo = graph_ptr[T->g];
-  const int n = graph_ptr[T->g + 1] - T->lo;
-  if (T->c0 < 0 || T->j0 < 0 || T->c0 >= n || T->j0 >= n) return false;
-  T->nc = min(kSqRowBlock, n - T->c0);
-  T->nj = min(kSqChunk, n - T->j0);
-  return true;
-}
-
+// tile {graph, first atom i, first atom j} (local indices): the pairs i < j of a 64 x 256 block, read and checked by
+// pair_tile_read<kSqRowBlock, kSqChunk> (eval_device.h)
+//
 // One workgroup of 256 threads per tile.  The 64 atoms i and the 256 atoms j (positions, types) are staged in LDS.  For each atom
 // i in turn, thread t takes the pair (i, j0 + t): r, the window and the unordered type pair go to LDS, ONCE per pair; then every
 // thread walks the row's pairs for ITS q values (two per thread, 512 per pass), all lanes reading the same pair (LDS broadcasts).
@@ -48,9 +33,9 @@ __global__ __launch_bounds__(256) void sq_debye_kernel(const float* __restrict__
   __shared__ double s_r[kSqChunk], s_w[kSqChunk];
   __shared__ int s_p[kSqChunk];
   const int tid = threadIdx.x;
-  SqTile T;
-  if (!sq_tile_read(tiles, blockIdx.x, graph_ptr, B, &T)) return;
-  const int P = sq_type_pairs(A);
+  PairTile T;
+  if (!pair_tile_read<kSqRowBlock, kSqChunk>(tiles, blockIdx.x, graph_ptr, B, &T)) return;
+  const int P = type_pairs(A);
   for (int t = tid; t < 3 * T.nj; t += 256) s_pj[t] = pos[3 * (size_t)(T.lo + T.j0) + t];
   for (int t = tid; t < T.nj; t += 256) s_tj[t] = type[T.lo + T.j0 + t];
   for (int t = tid; t < 3 * T.nc; t += 256) s_pi[t] = pos[3 * (size_t)(T.lo + T.c0) + t];
@@ -74,9 +59,9 @@ __global__ __launch_bounds__(256) void sq_debye_kernel(const float* __restrict__
         const int ti = s_ti[ii];
         if (tid < T.nj && tid >= first && ti >= 0 && ti < A) {
           const int tj = s_tj[tid];
-          r = sq_distance(s_pi[3 * ii], s_pi[3 * ii + 1], s_pi[3 * ii + 2], s_pj[3 * tid], s_pj[3 * tid + 1], s_pj[3 * tid + 2]);
+          r = distance64(s_pi[3 * ii], s_pi[3 * ii + 1], s_pi[3 * ii + 2], s_pj[3 * tid], s_pj[3 * tid + 1], s_pj[3 * tid + 2]);
           if (tj >= 0 && tj < A && r < r_max) {
-            p = sq_type_pair_index(ti, tj, A);
+            p = type_pair_index(ti, tj, A);
             w = sq_window(r, r_max, window);
           }
         }
@@ -118,12 +103,12 @@ __global__ __launch_bounds__(256) void sq_debye_finish_kernel(const int* __restr
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (size_t)B * A * A * Q) return;
   const int k = (int)(idx % Q), ab = (int)(idx / Q % (A * A)), g = (int)(idx / Q / (A * A));
-  const int a = ab / A, b = ab % A, P = sq_type_pairs(A), p = sq_type_pair_index(a, b, A);
+  const int a = ab / A, b = ab % A, P = type_pairs(A), p = type_pair_index(a, b, A);
   const int t_lo = min(max(tile_ptr[g], 0), n_tiles), t_hi = min(max(tile_ptr[g + 1], t_lo), n_tiles);
   double sum = 0.0;
   for (int t = t_lo; t < t_hi; ++t) {
-    SqTile T;
-    if (!sq_tile_read(tiles, t, graph_ptr, B, &T) || T.g != g) continue;
+    PairTile T;
+    if (!pair_tile_read<kSqRowBlock, kSqChunk>(tiles, t, graph_ptr, B, &T) || T.g != g) continue;
     sum += partial[((size_t)t * P + p) * Q + k];
   }
   out[idx] = a == b ? 2.0 * sum : sum;
@@ -268,7 +253,7 @@ __global__ __launch_bounds__(256) void sq_cell_shell_kernel(const int* __restric
     for (int sl = 0; sl < kSlices; ++sl)
 #pragma unroll
       for (int wv = 0; wv < 4; ++wv) {
-        if (match[sl] && wv == wave) s_list[total + __popcll(mask[sl] & ((1ull << lane) - 1ull))] = base + sl * 256 + tid;
+        if (match[sl] && wv == wave) s_list[total + lane_prefix(mask[sl], lane)] = base + sl * 256 + tid;
         total += s_cnt[sl * 4 + wv];
       }
     __syncthreads();

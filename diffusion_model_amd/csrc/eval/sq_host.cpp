@@ -3,7 +3,6 @@
 // CPU through sq_math.h, the text the kernels compile, in a summation order of its own (pairs i < j ascending; atoms ascending;
 // vectors ascending).  No HIP call, no device code: checked (and run under the sanitizers, make asan) on a machine without a GPU.
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "sq_host.h"
@@ -14,7 +13,7 @@ namespace egnn {
 int sq_debye_args_check(const char* who, int B, int A, const void* pos, const void* type, const void* graph_ptr, int max_atoms, int Q,
                         const double* q, double r_max, int window, const void* out) {
   if (B < 1 || !pos || !type || !graph_ptr || !out) { set_error("bad %s arguments (B >= 1; pos, type, graph_ptr and the output given)", who); return EGNN_EINVAL; }
-  if (A < 1 || A > kSqMaxTypes) { set_error("%s: %d atom types (1 <= A <= %d)", who, A, kSqMaxTypes); return EGNN_EINVAL; }
+  if (int rc = atom_types_check(who, A, kSqMaxTypes)) return rc;
   if (max_atoms < 0 || max_atoms > kSqMaxAtoms) { set_error("%s: a graph of %d atoms (at most %d)", who, max_atoms, kSqMaxAtoms); return EGNN_EINVAL; }
   if (Q < 1 || Q > kSqMaxQ || !q) { set_error("%s: %d q values (1 <= Q <= %d, the host copy of q given)", who, Q, kSqMaxQ); return EGNN_EINVAL; }
   for (int k = 0; k < Q; ++k)
@@ -35,14 +34,11 @@ int sq_tiles_args_check(const char* who, const void* tiles, int n_tiles, const v
 
 int sq_cells_check(const char* who, int C, int A, const int32_t* cell_ptr, const double* lattice, double q_max, int32_t* hkl_box) {
   if (C < 1 || C > 65535 || !lattice) { set_error("bad %s arguments (1 <= C <= 65535, the host copy of the lattices given)", who); return EGNN_EINVAL; }
-  if (A < 1 || A > kSqMaxTypes) { set_error("%s: %d atom types (1 <= A <= %d)", who, A, kSqMaxTypes); return EGNN_EINVAL; }
+  if (int rc = atom_types_check(who, A, kSqMaxTypes)) return rc;
   if (!(q_max > 0.0) || !(q_max < 1e30)) { set_error("%s: q_max must be positive and finite", who); return EGNN_EINVAL; }
   for (int c = 0; c < C; ++c) {
-    if (cell_ptr) {
-      const long long n = (long long)cell_ptr[c + 1] - cell_ptr[c];
-      if (n < 0) { set_error("%s: cell_ptr decreases at cell %d", who, c); return EGNN_EINVAL; }
-      if (n > kCellMaxAtoms) { set_error("%s: cell %d has %lld atoms (at most %d)", who, c, n, kCellMaxAtoms); return EGNN_EINVAL; }
-    }
+    if (cell_ptr)
+      if (int rc = ptr_step_check(who, "cell_ptr", "cell", cell_ptr, c, kCellMaxAtoms)) return rc;
     double Bm[9];
     int need[3];
     if (!sq_reciprocal(lattice + 9 * (size_t)c, Bm)) { set_error("%s: cell %d has a singular lattice", who, c); return EGNN_EINVAL; }
@@ -96,29 +92,14 @@ int sq_vec_ptr_check(const char* who, int C, const int32_t* vec_ptr, int K) {
 
 namespace {
 
-// scratch of the host statement (not std::vector: cells/cell_host.cpp says why)
-template <typename T>
-struct Scratch {
-  T* p;
-  explicit Scratch(size_t n) : p(static_cast<T*>(calloc(n ? n : 1, sizeof(T)))) {}
-  ~Scratch() { free(p); }
-  Scratch(const Scratch&) = delete;
-  Scratch& operator=(const Scratch&) = delete;
-  T& operator[](size_t i) { return p[i]; }
-};
-
 int debye_host(const char* who, int B, int N, int A, const float* pos, const int32_t* type, const int32_t* graph_ptr, int Q, const double* q,
                double r_max, int window, double* out) {
   if (int rc = sq_debye_args_check(who, B, A, pos, type, graph_ptr, 0, Q, q, r_max, window, out)) return rc;
   if (graph_ptr[0] != 0 || graph_ptr[B] != N) { set_error("%s: graph_ptr must run from 0 to N = %d", who, N); return EGNN_EINVAL; }
-  for (int g = 0; g < B; ++g) {
-    const long long n = (long long)graph_ptr[g + 1] - graph_ptr[g];
-    if (n < 0) { set_error("%s: graph_ptr decreases at graph %d", who, g); return EGNN_EINVAL; }
-    if (n > kSqMaxAtoms) { set_error("%s: graph %d has %lld atoms (at most %d)", who, g, n, kSqMaxAtoms); return EGNN_EINVAL; }
-  }
-  for (int i = 0; i < N; ++i)
-    if (type[i] < 0 || type[i] >= A) { set_error("%s: atom %d has type %d outside [0, %d)", who, i, type[i], A); return EGNN_EINVAL; }
-  const int P = sq_type_pairs(A);
+  for (int g = 0; g < B; ++g)
+    if (int rc = ptr_step_check(who, "graph_ptr", "graph", graph_ptr, g, kSqMaxAtoms)) return rc;
+  if (int rc = type_range_check(who, type, 0, N, A)) return rc;
+  const int P = type_pairs(A);
   Scratch<double> sum((size_t)P * Q);
   if (!sum.p) { set_error("%s: out of memory", who); return EGNN_EINVAL; }
   for (int g = 0; g < B; ++g) {
@@ -128,15 +109,15 @@ int debye_host(const char* who, int B, int N, int A, const float* pos, const int
       for (int j = i + 1; j < hi; ++j) {
         const float* a = pos + 3 * (size_t)i;
         const float* b = pos + 3 * (size_t)j;
-        const double r = sq_distance(a[0], a[1], a[2], b[0], b[1], b[2]);
+        const double r = distance64(a[0], a[1], a[2], b[0], b[1], b[2]);
         if (!(r < r_max)) continue;
         const double w = sq_window(r, r_max, window);
-        double* row = sum.p + (size_t)sq_type_pair_index(type[i], type[j], A) * Q;
+        double* row = sum.p + (size_t)type_pair_index(type[i], type[j], A) * Q;
         for (int k = 0; k < Q; ++k) row[k] += w * sq_sinc(q[k] * r);
       }
     for (int a = 0; a < A; ++a)
       for (int b = 0; b < A; ++b) {
-        const double* row = sum.p + (size_t)sq_type_pair_index(a, b, A) * Q;
+        const double* row = sum.p + (size_t)type_pair_index(a, b, A) * Q;
         double* o = out + (((size_t)g * A + a) * A + b) * Q;
         for (int k = 0; k < Q; ++k) o[k] = a == b ? 2.0 * row[k] : row[k];
       }

@@ -1,7 +1,7 @@
 // Host-only argument validation of the reciprocal-space statistics (sq.hip) and their host statement.  Plain C++ beside
 // host_logic: it is also compiled into the CPU-only sanitizer library (make asan).
 #pragma once
-#include "../host_logic.h"
+#include "eval_host.h"
 
 namespace egnn {
 

@@ -20,16 +20,9 @@
 //  * index box: |h| <= floor(q_max |a_1| / 2 pi) (|k_m . a_1| = 2 pi |h| <= |k_m| |a_1|), likewise k and l; the box the kernels
 //    walk is one wider (a rounding of the bound cannot lose a vector; the membership test rejects the extra ones), capped at 1023.
 #pragma once
-#include <math.h>
-#include <stdint.h>
+#include "eval_math.h"
 
 #include "../cells/cell_math.h"
-
-#if defined(__HIPCC__)
-#define SQ_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define SQ_HD inline
-#endif
 
 namespace egnn {
 
@@ -49,26 +42,15 @@ constexpr int kSqShellBlock = 1024;         // vectors one step of the shell ker
 constexpr int kSqWindowNone = 0, kSqWindowLorch = 1;
 constexpr double kSqTwoPi = 6.283185307179586476925286766559;
 
-SQ_HD int sq_type_pairs(int A) { return A * (A + 1) / 2; }
-SQ_HD int sq_type_pair_index(int b, int c, int A) {   // unordered, as struct_type_pair_index
-  const int lo = b < c ? b : c, hi = b < c ? c : b;
-  return lo * A - lo * (lo - 1) / 2 + (hi - lo);
-}
+EGNN_HD double sq_sinc(double x) { return x == 0.0 ? 1.0 : sin(x) / x; }
 
-SQ_HD double sq_distance(float px, float py, float pz, float qx, float qy, float qz) {
-  const double dx = (double)qx - (double)px, dy = (double)qy - (double)py, dz = (double)qz - (double)pz;
-  return sqrt((dx * dx + dy * dy) + dz * dz);
-}
-
-SQ_HD double sq_sinc(double x) { return x == 0.0 ? 1.0 : sin(x) / x; }
-
-SQ_HD double sq_window(double r, double r_max, int window) {
+EGNN_HD double sq_window(double r, double r_max, int window) {
   return window == kSqWindowLorch ? sq_sinc((M_PI * r) / r_max) : 1.0;
 }
 
 // ---- cells ----
 // reciprocal rows; false for a singular or non-finite lattice (the rule of cell_widths)
-SQ_HD bool sq_reciprocal(const double* L, double* Bm) {
+EGNN_HD bool sq_reciprocal(const double* L, double* Bm) {
   double w[3];
   if (!cell_widths(L, w)) return false;
   const double* a = L;
@@ -87,7 +69,7 @@ SQ_HD bool sq_reciprocal(const double* L, double* Bm) {
 }
 
 // largest index each axis needs: floor(q_max |a_i| / 2 pi); false where one exceeds kSqMaxIndex (or is not finite)
-SQ_HD bool sq_index_need(const double* L, double q_max, int* need) {
+EGNN_HD bool sq_index_need(const double* L, double q_max, int* need) {
   for (int i = 0; i < 3; ++i) {
     const double v = floor((q_max * sqrt(cell_norm2(L + 3 * i))) / kSqTwoPi);
     if (!(v <= (double)kSqMaxIndex)) return false;
@@ -95,37 +77,37 @@ SQ_HD bool sq_index_need(const double* L, double q_max, int* need) {
   }
   return true;
 }
-SQ_HD int sq_index_box(int need) { return need + 1 < kSqMaxIndex ? need + 1 : kSqMaxIndex; }
+EGNN_HD int sq_index_box(int need) { return need + 1 < kSqMaxIndex ? need + 1 : kSqMaxIndex; }
 
-SQ_HD bool sq_half_space(int h, int k, int l) { return h > 0 || (h == 0 && (k > 0 || (k == 0 && l > 0))); }
+EGNN_HD bool sq_half_space(int h, int k, int l) { return h > 0 || (h == 0 && (k > 0 || (k == 0 && l > 0))); }
 
-SQ_HD double sq_k2(int h, int k, int l, const double* Bm) {
+EGNN_HD double sq_k2(int h, int k, int l, const double* Bm) {
   double kv[3];
   for (int x = 0; x < 3; ++x) kv[x] = ((double)h * Bm[x] + (double)k * Bm[3 + x]) + (double)l * Bm[6 + x];
   return (kv[0] * kv[0] + kv[1] * kv[1]) + kv[2] * kv[2];
 }
 
-SQ_HD bool sq_is_vector(int h, int k, int l, const double* Bm, double q_max, double* k2) {
+EGNN_HD bool sq_is_vector(int h, int k, int l, const double* Bm, double q_max, double* k2) {
   *k2 = sq_k2(h, k, l, Bm);
   return sq_half_space(h, k, l) && *k2 < q_max * q_max;
 }
 
-SQ_HD int sq_nbins(double q_max, double dq) {
+EGNN_HD int sq_nbins(double q_max, double dq) {
   const double n = ceil(q_max / dq);
   return n >= 1.0 && n <= 1e9 ? (int)n : -1;
 }
 
-SQ_HD int sq_bin(double kabs, double dq, int nbins) {
+EGNN_HD int sq_bin(double kabs, double dq, int nbins) {
   const int n = (int)floor(kabs / dq);
   return n < nbins ? n : nbins - 1;
 }
 
 // sine and cosine of 2 pi t, t = the phase mod 1
-SQ_HD double sq_phase(int h, int k, int l, const double* w) {
+EGNN_HD double sq_phase(int h, int k, int l, const double* w) {
   const double t = ((double)h * w[0] + (double)k * w[1]) + (double)l * w[2];
   return t - floor(t);
 }
-SQ_HD void sq_phase_sincos(double t, double* s, double* c) {
+EGNN_HD void sq_phase_sincos(double t, double* s, double* c) {
 #if defined(__HIP_DEVICE_COMPILE__)
   sincospi(2.0 * t, s, c);   // 2 t is exact and the argument reduction of sincospi is exact
 #else
@@ -136,11 +118,11 @@ SQ_HD void sq_phase_sincos(double t, double* s, double* c) {
 }
 
 // rows of the index box of one cell: (h, k) with 0 <= h <= H, |k| <= K; row = h (2K + 1) + (k + K)
-SQ_HD int sq_box_rows(int H, int K) { return (H + 1) * (2 * K + 1); }
+EGNN_HD int sq_box_rows(int H, int K) { return (H + 1) * (2 * K + 1); }
 
 // vectors of row (h, k): the l in [-Lb, Lb] that pass sq_is_vector, ascending; `emit` is called for each
 template <typename F>
-SQ_HD int sq_row_vectors(int h, int k, int Lb, const double* Bm, double q_max, F emit) {
+EGNN_HD int sq_row_vectors(int h, int k, int Lb, const double* Bm, double q_max, F emit) {
   int n = 0;
   for (int l = -Lb; l <= Lb; ++l) {
     double k2;

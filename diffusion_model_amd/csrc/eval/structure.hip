@@ -9,19 +9,13 @@
 // Tiles come from the caller ({graph, first centre, first neighbour} int32 triples, built from the graph sizes on the host).  A
 // kernel trusts no entry: graph, centre block and neighbour chunk are checked against graph_ptr, and every atom index a kernel
 // forms lies in [graph_ptr[g], graph_ptr[g + 1]), also where the last centre block or neighbour chunk of a graph is partial.
-#include "../common.h"
+#include "eval_device.h"
 #include "structure_host.h"
 #include "structure_math.h"
 
 namespace egnn {
 
 constexpr int kStructWeightTaps = 128;   // half width of the smoothing filter up to which its weights are tabled in LDS
-
-__device__ __forceinline__ void struct_wave_sync() {   // one wavefront: its LDS operations complete in order (assign.hip)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // ---- ordered pairs -> c[g][a][b][k] --------------------------------------------------------------------------------------------
 // One workgroup of 256 threads per tile (graph, <= 64 centres, <= 1024 neighbour atoms): 256 graphs of 64 atoms, 32 of 512 and one
@@ -36,11 +30,9 @@ __global__ __launch_bounds__(256) void struct_pair_kernel(const float* __restric
   __shared__ float s_pos[3 * kStructChunk];
   __shared__ int s_type[kStructChunk];
   const int tid = threadIdx.x;
-  const int g = tiles[3 * blockIdx.x], c0 = tiles[3 * blockIdx.x + 1], j0 = tiles[3 * blockIdx.x + 2];
-  if (g < 0 || g >= B) return;
-  const int lo = graph_ptr[g], n = graph_ptr[g + 1] - lo;
-  if (c0 < 0 || j0 < 0 || c0 >= n || j0 >= n) return;
-  const int nc = min(kStructCentreBlock, n - c0), nj = min(kStructChunk, n - j0);
+  PairTile T;
+  if (!pair_tile_read<kStructCentreBlock, kStructChunk>(tiles, blockIdx.x, graph_ptr, B, &T)) return;
+  const int g = T.g, lo = T.lo, c0 = T.c0, j0 = T.j0, nc = T.nc, nj = T.nj;
   const int nh = A * A * nbins;
   for (int k = tid; k < nh; k += 256) pair_hist[k] = 0;
   for (int t = tid; t < 3 * nj; t += 256) s_pos[t] = pos[3 * (size_t)(lo + j0) + t];
@@ -98,7 +90,7 @@ __global__ __launch_bounds__(256) void struct_bond_kernel(const float* __restric
   const int lo = graph_ptr[g], n = graph_ptr[g + 1] - lo;
   if (c0 < 0 || c0 >= n) return;
   const int nc = min(kStructBondCentres, n - c0);
-  const int P = struct_type_pairs(A), ncn = max_cn + 1;
+  const int P = type_pairs(A), ncn = max_cn + 1;
   const int n_ang = A * P * nth, n_cn = A * A * ncn, nh = n_ang + n_cn + 1;
   int* h_ang = bond_hist;
   int* h_cn = bond_hist + n_ang;
@@ -116,7 +108,7 @@ __global__ __launch_bounds__(256) void struct_bond_kernel(const float* __restric
       const int j = j0 + lane;
       const int tj = lane < m ? type[lo + j] : -1;   // in flight together with the positions
       for (int t = lane; t < 3 * m; t += 64) W.stage[t] = pos[3 * (size_t)(lo + j0) + t];
-      struct_wave_sync();
+      wave_sync();
       bool bonded = false;
       float qx = 0.f, qy = 0.f, qz = 0.f;
       if (lane < m && j != c) {
@@ -126,7 +118,7 @@ __global__ __launch_bounds__(256) void struct_bond_kernel(const float* __restric
       const unsigned long long mask = __ballot(bonded);
 #pragma unroll
       for (int b = 0; b < kStructMaxTypes; ++b) nb[b] += __popcll(__ballot(bonded && tj == b));
-      const int slot = nlist + __popcll(mask & ((1ull << lane) - 1ull));
+      const int slot = nlist + lane_prefix(mask, lane);
       if (bonded && slot < kMaxNeighbours) {
         W.v[3 * slot] = (double)qx - (double)px;
         W.v[3 * slot + 1] = (double)qy - (double)py;
@@ -134,7 +126,7 @@ __global__ __launch_bounds__(256) void struct_bond_kernel(const float* __restric
         W.t[slot] = tj;
       }
       nlist += __popcll(mask);
-      struct_wave_sync();
+      wave_sync();
     }
     if (lane < A) atomicAdd(&h_cn[(ti * A + lane) * ncn + min(nb[lane], max_cn)], 1);
     if (nlist > kMaxNeighbours) {
@@ -144,10 +136,10 @@ __global__ __launch_bounds__(256) void struct_bond_kernel(const float* __restric
         const int a = p / nlist, b = p - a * nlist;
         if (a >= b) continue;
         const int k = struct_angle_bin(&W.v[3 * a], &W.v[3 * b], dtheta, nth);
-        if (k >= 0) atomicAdd(&h_ang[(ti * P + struct_type_pair_index(W.t[a], W.t[b], A)) * nth + k], 1);
+        if (k >= 0) atomicAdd(&h_ang[(ti * P + type_pair_index(W.t[a], W.t[b], A)) * nth + k], 1);
       }
     }
-    struct_wave_sync();   // the list is rewritten for the next centre
+    wave_sync();   // the list is rewritten for the next centre
   }
   __syncthreads();
   int* o_ang = angles + (size_t)g * n_ang;
@@ -219,15 +211,12 @@ int egnn_struct_pair_counts(void* stream, int B, int A, const float* pos, const 
                             int max_atoms, const int32_t* tiles, int n_tiles, double dR, int nbins, int32_t* counts) {
   const char* who = "egnn_struct_pair_counts";
   if (int rc = struct_pair_args_check(who, B, A, pos, type, graph_ptr, max_atoms, dR, nbins, counts)) return rc;
-  if (int rc = struct_tiles_args_check(who, tiles, n_tiles)) return rc;
+  if (int rc = tiles_check(who, tiles, n_tiles)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t lds = sizeof(int) * (size_t)A * A * nbins;
-  static bool configured = false;
-  if (!configured) {   // 64 KiB of histogram at A = 4, nbins = 1024, beside 16 KiB of staged neighbours; a CU has 160 KiB
-    EGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&struct_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(sizeof(int) * kStructMaxTypes * kStructMaxTypes * kStructMaxBins)));
-    configured = true;
-  }
+  // 64 KiB of histogram at A = 4, nbins = 1024, beside 16 KiB of staged neighbours; a CU has 160 KiB
+  static LdsLimitRecord raised;
+  if (int rc = raise_lds_limit(raised, &struct_pair_kernel, sizeof(int) * kStructMaxTypes * kStructMaxTypes * kStructMaxBins)) return rc;
   EGNN_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)B * A * A * nbins, st));
   if (n_tiles > 0)
     hipLaunchKernelGGL(struct_pair_kernel, dim3(n_tiles), dim3(256), lds, st, pos, type, graph_ptr, B, A, tiles, dR, nbins, counts);
@@ -240,19 +229,15 @@ int egnn_struct_bonds(void* stream, int B, int A, const float* pos, const int32_
                       int32_t* overflow) {
   const char* who = "egnn_struct_bonds";
   if (int rc = struct_bond_args_check(who, B, A, pos, type, graph_ptr, max_atoms, cutoff, dtheta, max_cn, cn, angles)) return rc;
-  if (int rc = struct_tiles_args_check(who, tiles, n_tiles)) return rc;
+  if (int rc = tiles_check(who, tiles, n_tiles)) return rc;
   if (!overflow) { set_error("bad %s arguments (overflow given)", who); return EGNN_EINVAL; }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int nth = struct_angle_bins(dtheta), P = struct_type_pairs(A), ncn = max_cn + 1;
+  const int nth = struct_angle_bins(dtheta), P = type_pairs(A), ncn = max_cn + 1;
   const size_t n_ang = (size_t)A * P * nth, n_cn = (size_t)A * A * ncn;
-  static bool configured = false;
-  if (!configured) {
-    const size_t most = (size_t)kStructMaxTypes * struct_type_pairs(kStructMaxTypes) * kStructMaxAngleBins +
-                        (size_t)kStructMaxTypes * kStructMaxTypes * (kStructMaxCn + 1) + 1;
-    EGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&struct_bond_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(sizeof(int) * most)));
-    configured = true;
-  }
+  const size_t most = (size_t)kStructMaxTypes * type_pairs(kStructMaxTypes) * kStructMaxAngleBins +
+                      (size_t)kStructMaxTypes * kStructMaxTypes * (kStructMaxCn + 1) + 1;
+  static LdsLimitRecord raised;
+  if (int rc = raise_lds_limit(raised, &struct_bond_kernel, sizeof(int) * most)) return rc;
   EGNN_HIP(hipMemsetAsync(cn, 0, sizeof(int32_t) * B * n_cn, st));
   EGNN_HIP(hipMemsetAsync(angles, 0, sizeof(int32_t) * B * n_ang, st));
   EGNN_HIP(hipMemsetAsync(overflow, 0, sizeof(int32_t) * (size_t)B, st));

@@ -12,7 +12,7 @@ namespace egnn {
 
 static int struct_common_check(const char* who, int B, int A, const void* pos, const void* type, const void* graph_ptr, int max_atoms) {
   if (B < 1 || !pos || !type || !graph_ptr) { set_error("bad %s arguments (B >= 1; pos, type and graph_ptr given)", who); return EGNN_EINVAL; }
-  if (A < 1 || A > kStructMaxTypes) { set_error("%s: %d atom types (1 <= A <= %d)", who, A, kStructMaxTypes); return EGNN_EINVAL; }
+  if (int rc = atom_types_check(who, A, kStructMaxTypes)) return rc;
   if (max_atoms < 0 || max_atoms > kStructMaxAtoms) {
     set_error("%s: a graph of %d atoms (at most %d: the ordered pairs of one graph are counted in int32)", who, max_atoms, kStructMaxAtoms);
     return EGNN_EINVAL;
@@ -42,15 +42,10 @@ int struct_bond_args_check(const char* who, int B, int A, const void* pos, const
   return EGNN_OK;
 }
 
-int struct_tiles_args_check(const char* who, const void* tiles, int n_tiles) {
-  if (n_tiles < 0 || (n_tiles > 0 && !tiles)) { set_error("bad %s arguments (n_tiles >= 0 tiles given)", who); return EGNN_EINVAL; }
-  return EGNN_OK;
-}
-
 int struct_finish_args_check(int B, int A, const void* counts, const void* type, const void* graph_ptr, double R, double dR,
                              double sigma, int nbins, const void* out) {
   if (B < 1 || !counts || !type || !graph_ptr || !out) { set_error("bad egnn_struct_rdf_finish arguments"); return EGNN_EINVAL; }
-  if (A < 1 || A > kStructMaxTypes) { set_error("egnn_struct_rdf_finish: %d atom types (1 <= A <= %d)", A, kStructMaxTypes); return EGNN_EINVAL; }
+  if (int rc = atom_types_check("egnn_struct_rdf_finish", A, kStructMaxTypes)) return rc;
   if (nbins < 1 || nbins > kStructMaxBins) { set_error("egnn_struct_rdf_finish: %d radial bins (1 <= nbins <= %d)", nbins, kStructMaxBins); return EGNN_EINVAL; }
   if (!(dR > 0.0) || !(R > 0.0) || !(sigma > 0.0)) { set_error("egnn_struct_rdf_finish: R, dR and sigma must be positive"); return EGNN_EINVAL; }
   if ((long long)B * A * A > 2147483647LL) { set_error("egnn_struct_rdf_finish: B * A * A exceeds the grid"); return EGNN_EINVAL; }
@@ -72,10 +67,9 @@ int egnn_struct_counts_host(int B, int A, const float* pos, const int32_t* type,
     const int lo = graph_ptr[g], hi = graph_ptr[g + 1];
     if (lo < 0 || hi < lo) { set_error("%s: graph_ptr must start at 0 or above and not decrease", who); return EGNN_EINVAL; }
     if (int rc = struct_common_check(who, B, A, pos, type, graph_ptr, hi - lo)) return rc;
-    for (int i = lo; i < hi; ++i)
-      if (type[i] < 0 || type[i] >= A) { set_error("%s: atom %d has type %d outside [0, %d)", who, i, type[i], A); return EGNN_EINVAL; }
+    if (int rc = type_range_check(who, type, lo, hi, A)) return rc;
   }
-  const int nth = struct_angle_bins(dtheta), P = struct_type_pairs(A), ncn = max_cn + 1;
+  const int nth = struct_angle_bins(dtheta), P = type_pairs(A), ncn = max_cn + 1;
   memset(counts, 0, sizeof(int32_t) * (size_t)B * A * A * nbins);
   memset(cn, 0, sizeof(int32_t) * (size_t)B * A * A * ncn);
   memset(angles, 0, sizeof(int32_t) * (size_t)B * A * P * nth);
@@ -117,7 +111,7 @@ int egnn_struct_counts_host(int B, int A, const float* pos, const int32_t* type,
       for (int a = 0; a < nlist; ++a)
         for (int b = a + 1; b < nlist; ++b) {
           const int k = struct_angle_bin(&bond[3 * (size_t)a], &bond[3 * (size_t)b], dtheta, nth);
-          if (k >= 0) ++ang_g[((size_t)ti * P + struct_type_pair_index(bond_type[a], bond_type[b], A)) * nth + k];
+          if (k >= 0) ++ang_g[((size_t)ti * P + type_pair_index(bond_type[a], bond_type[b], A)) * nth + k];
         }
     }
   }

@@ -1,7 +1,7 @@
 // Host-only argument validation of the whole-structure statistics (structure.hip) and their host statement.  Plain C++ beside
 // host_logic: it is also compiled into the CPU-only sanitizer library (make asan).
 #pragma once
-#include "../host_logic.h"
+#include "eval_host.h"
 
 namespace egnn {
 
@@ -10,7 +10,6 @@ int struct_pair_args_check(const char* who, int B, int A, const void* pos, const
                            double dR, int nbins, const void* counts);
 int struct_bond_args_check(const char* who, int B, int A, const void* pos, const void* type, const void* graph_ptr, int max_atoms,
                            float cutoff, double dtheta, int max_cn, const void* cn, const void* angles);
-int struct_tiles_args_check(const char* who, const void* tiles, int n_tiles);
 int struct_finish_args_check(int B, int A, const void* counts, const void* type, const void* graph_ptr, double R, double dR,
                              double sigma, int nbins, const void* out);
 

@@ -15,14 +15,7 @@
 //    bond vector has no angle.
 //  * smoothing: scipy's gaussian_filter1d(sigma) as rdf_kernel spells it (reflect boundary, truncation at 4 sigma).
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define STRUCT_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define STRUCT_HD inline
-#endif
+#include "eval_math.h"
 
 namespace egnn {
 
@@ -36,7 +29,7 @@ constexpr int kStructCentreBlock = 64;      // pair tile: centres
 constexpr int kStructChunk = 1024;          // pair tile: neighbour atoms
 constexpr int kStructBondCentres = 8;       // bond tile: centres
 
-STRUCT_HD float struct_distance(float px, float py, float pz, float qx, float qy, float qz) {
+EGNN_HD float struct_distance(float px, float py, float pz, float qx, float qy, float qz) {
   const float dx = qx - px, dy = qy - py, dz = qz - pz;
   return sqrtf((dx * dx + dy * dy) + dz * dz);
 }
@@ -44,28 +37,21 @@ STRUCT_HD float struct_distance(float px, float py, float pz, float qx, float qy
 // a bin index within one of the bin (if any) that holds d, from float32 arithmetic: d * inv_dR is within 1e-3 of d / dR for every
 // d below (nbins + 2) dR, and the bin that holds d is floor(d / dR) - 1 or its lower neighbour, so the caller tests guess - 1,
 // guess and guess + 1 with struct_in_bin.  Distances beyond the last bin (and NaN) return nbins + 2: no candidate is a bin.
-STRUCT_HD int struct_bin_guess(float d, float inv_dR, int nbins) {
+EGNN_HD int struct_bin_guess(float d, float inv_dR, int nbins) {
   const float t = d * inv_dR;
   if (!(t < (float)(nbins + 2))) return nbins + 2;
   return (int)t - 1;
 }
 
-STRUCT_HD bool struct_in_bin(float d, int k, double dR) {
+EGNN_HD bool struct_in_bin(float d, int k, double dR) {
   const double rk = dR + (double)k * dR;
   return (float)rk < d && d < (float)(rk + dR);
 }
 
-STRUCT_HD int struct_angle_bins(double dtheta) { return (int)floor(180.0 / dtheta + 0.5) + 1; }
-
-// number of unordered neighbour-type pairs and the index of (b, c), in either order
-STRUCT_HD int struct_type_pairs(int A) { return A * (A + 1) / 2; }
-STRUCT_HD int struct_type_pair_index(int b, int c, int A) {
-  const int lo = b < c ? b : c, hi = b < c ? c : b;
-  return lo * A - lo * (lo - 1) / 2 + (hi - lo);
-}
+EGNN_HD int struct_angle_bins(double dtheta) { return (int)floor(180.0 / dtheta + 0.5) + 1; }
 
 // angle bin of the bond vectors v and w, -1 where one of them has no length
-STRUCT_HD int struct_angle_bin(const double* v, const double* w, double dtheta, int nth) {
+EGNN_HD int struct_angle_bin(const double* v, const double* w, double dtheta, int nth) {
   const double vv = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
   const double ww = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
   if (!(vv > 0.0) || !(ww > 0.0)) return -1;
@@ -78,16 +64,16 @@ STRUCT_HD int struct_angle_bin(const double* v, const double* w, double dtheta, 
 }
 
 // ---- Gaussian smoothing of a curve of nbins values, as rdf_kernel's ----
-STRUCT_HD int struct_smooth_half_width(double sigma) { return (int)(4.0 * sigma + 0.5); }
-STRUCT_HD double struct_smooth_weight(int t, double sigma) { return exp(-0.5 * (double)t * t / (sigma * sigma)); }
-STRUCT_HD int struct_reflect(int idx, int nbins) {   // 'reflect': (d c b a | a b c d | d c b a)
+EGNN_HD int struct_smooth_half_width(double sigma) { return (int)(4.0 * sigma + 0.5); }
+EGNN_HD double struct_smooth_weight(int t, double sigma) { return exp(-0.5 * (double)t * t / (sigma * sigma)); }
+EGNN_HD int struct_reflect(int idx, int nbins) {   // 'reflect': (d c b a | a b c d | d c b a)
   const int period = 2 * nbins;
   idx %= period;
   if (idx < 0) idx += period;
   if (idx >= nbins) idx = period - 1 - idx;
   return idx;
 }
-STRUCT_HD double struct_smooth_at(const double* raw, int nbins, int k, double sigma, int lw, double wsum) {
+EGNN_HD double struct_smooth_at(const double* raw, int nbins, int k, double sigma, int lw, double wsum) {
   double acc = 0.0;
   for (int t = -lw; t <= lw; ++t) acc += raw[struct_reflect(k + t, nbins)] * struct_smooth_weight(t, sigma);
   return acc / wsum;

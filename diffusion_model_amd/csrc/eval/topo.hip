@@ -8,9 +8,7 @@
 //
 // A kernel trusts no entry it reads: graphs are checked against N, a bond list against the 32 N entries the caller allocates,
 // a neighbour against its graph, a degree against the list width.
-#include <atomic>
-
-#include "../common.h"
+#include "eval_device.h"
 #include "topo_host.h"
 #include "topo_math.h"
 
@@ -18,15 +16,8 @@ namespace egnn {
 
 constexpr int kTopoBondCentres = 16;   // centres of one workgroup of the bond kernels (four wavefronts, one centre each at a time)
 constexpr int kTopoPathWaves = 16;     // wavefronts of the path kernel: sources in flight per graph
-constexpr int kTopoMaxDevices = 64;    // devices whose raised LDS limit is remembered (beyond: set at every call)
 
 struct TopoThresholds { double v[kTopoMaxTypes * kTopoMaxTypes]; };
-
-__device__ __forceinline__ void topo_wave_sync() {   // one wavefront: its LDS operations complete in order (assign.hip)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 __device__ __forceinline__ int topo_list_width(int degree) { return degree < 0 ? 0 : (degree < kTopoMaxDegree ? degree : kTopoMaxDegree); }
 
@@ -63,7 +54,7 @@ __global__ __launch_bounds__(256) void topo_bonds_kernel(const float* __restrict
       }
       const unsigned long long mask = __ballot(bonded);
       if (kFill) {
-        const int slot = count + __popcll(mask & ((1ull << lane) - 1ull));
+        const int slot = count + lane_prefix(mask, lane);
         if (bonded && slot < kTopoMaxDegree && base >= 0 && base <= kTopoMaxDegree * N - kTopoMaxDegree) neighbours[base + slot] = lo + j;
       }
       count += __popcll(mask);
@@ -163,7 +154,7 @@ __global__ __launch_bounds__(1024) void topo_paths_kernel(const int* __restrict_
       V[lane] = w;
     }
     if (lane < 32) cnt[lane] = 0;
-    topo_wave_sync();
+    wave_sync();
     uint16_t* row = dist_g ? dist_g + (size_t)s * n : nullptr;
     if (row && lane == 0) row[s] = 0;
     const int cs = s_cls[s];
@@ -196,7 +187,7 @@ __global__ __launch_bounds__(1024) void topo_paths_kernel(const int* __restrict_
         }
       }
       if (!any) break;
-      topo_wave_sync();   // every read of this level's frontier and every count is done
+      wave_sync();   // every read of this level's frontier and every count is done
       if (lane < kTopoMaxAtoms / 64) {
         F[lane] = mine;
         V[lane] |= mine;
@@ -208,7 +199,7 @@ __global__ __launch_bounds__(1024) void topo_paths_kernel(const int* __restrict_
           cnt[lane] = 0;
         }
       }
-      topo_wave_sync();
+      wave_sync();
     }
     if (row)
       for (int c = 0; c < nchunks; ++c) {
@@ -219,19 +210,13 @@ __global__ __launch_bounds__(1024) void topo_paths_kernel(const int* __restrict_
       if (component) component[lo + s] = lo + lowest;
       if (lowest == s) atomicAdd(&s_roots, 1);
     }
-    topo_wave_sync();   // the sets are rewritten for the next source
+    wave_sync();   // the sets are rewritten for the next source
   }
   __syncthreads();
   if (fragments && tid == 0) fragments[g] = s_roots;
 }
 
 // ---- Tanimoto similarity of listed pairs of rows: one wavefront per pair ------------------------------------------------------
-__device__ __forceinline__ long long topo_wave_sum(long long x) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
-
 __global__ __launch_bounds__(256) void topo_tanimoto_kernel(const int* __restrict__ fp_a, int rows_a, const int* __restrict__ fp_b,
                                                             int rows_b, const int* __restrict__ pairs, int n_pairs, int K,
                                                             double* __restrict__ sim, long long* __restrict__ sa,
@@ -252,9 +237,9 @@ __global__ __launch_bounds__(256) void topo_tanimoto_kernel(const int* __restric
     ta += x;
     tb += y;
   }
-  both = topo_wave_sum(both);
-  ta = topo_wave_sum(ta);
-  tb = topo_wave_sum(tb);
+  both = wave_sum(both);
+  ta = wave_sum(ta);
+  tb = wave_sum(tb);
   if (lane == 0) {
     sim[p] = topo_tanimoto(both, ta, tb);
     sa[p] = ta;
@@ -313,18 +298,9 @@ int egnn_topo_paths(void* stream, int B, int N, int A, const int32_t* type, cons
   if (dist && !dist_ptr) { set_error("bad %s arguments (dist_ptr given with dist)", who); return EGNN_EINVAL; }
   if (int rc = topo_length_check(who, L)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // 64 KiB of bond lists at 1024 atoms beside 8 KiB of static LDS; a CU has 160 KiB.  The limit belongs to the function ON ONE
-  // DEVICE, so it is raised once for every device this entry is called on (a process may use several).  Two threads that meet
-  // here both set the same value: the flag only spares the repeated call.
-  static std::atomic<bool> configured[kTopoMaxDevices];
-  int device = 0;
-  EGNN_HIP(hipGetDevice(&device));
-  const bool known = device >= 0 && device < kTopoMaxDevices;
-  if (!known || !configured[device].load(std::memory_order_acquire)) {
-    EGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&topo_paths_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(sizeof(uint16_t) * kTopoMaxDegree * kTopoMaxAtoms)));
-    if (known) configured[device].store(true, std::memory_order_release);
-  }
+  // 64 KiB of bond lists at 1024 atoms beside 8 KiB of static LDS; a CU has 160 KiB
+  static LdsLimitRecord raised;
+  if (int rc = raise_lds_limit(raised, &topo_paths_kernel, sizeof(uint16_t) * kTopoMaxDegree * kTopoMaxAtoms)) return rc;
   if (fp) EGNN_HIP(hipMemsetAsync(fp, 0, sizeof(int32_t) * (size_t)B * topo_keys(A, L), st));
   const int npad = max_atoms > 0 ? (max_atoms + 63) / 64 * 64 : 64;
   hipLaunchKernelGGL(topo_paths_kernel, dim3(B), dim3(64 * kTopoPathWaves), sizeof(uint16_t) * kTopoMaxDegree * (size_t)npad, st, type,

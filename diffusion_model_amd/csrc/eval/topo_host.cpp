@@ -13,7 +13,7 @@ namespace egnn {
 
 int topo_common_check(const char* who, int B, int A, const void* type, const void* graph_ptr, int max_atoms) {
   if (B < 1 || !type || !graph_ptr) { set_error("bad %s arguments (B >= 1; type and graph_ptr given)", who); return EGNN_EINVAL; }
-  if (A < 1 || A > kTopoMaxTypes) { set_error("%s: %d atom types (1 <= A <= %d)", who, A, kTopoMaxTypes); return EGNN_EINVAL; }
+  if (int rc = atom_types_check(who, A, kTopoMaxTypes)) return rc;
   if (max_atoms < 0 || max_atoms > kTopoMaxAtoms) {
     set_error("%s: a graph of %d atoms (at most %d: one workgroup holds a graph's bond lists)", who, max_atoms, kTopoMaxAtoms);
     return EGNN_EINVAL;
@@ -61,8 +61,7 @@ int egnn_topo_host(int B, int A, const float* pos, const int32_t* type, const in
     const int lo = graph_ptr[g], hi = graph_ptr[g + 1];
     if (lo < 0 || hi < lo || (g == 0 && lo != 0)) { set_error("%s: graph_ptr must start at 0 and not decrease", who); return EGNN_EINVAL; }
     if (int rc = topo_common_check(who, B, A, type, graph_ptr, hi - lo)) return rc;
-    for (int i = lo; i < hi; ++i)
-      if (type[i] < 0 || type[i] >= A) { set_error("%s: atom %d has type %d outside [0, %d)", who, i, type[i], A); return EGNN_EINVAL; }
+    if (int rc = type_range_check(who, type, lo, hi, A)) return rc;
   }
   for (int p = 0; p < 2 * n_pairs; ++p)
     if (pairs[p] < 0 || pairs[p] >= B) { set_error("%s: pair %d names row %d outside [0, %d)", who, p / 2, pairs[p], B); return EGNN_EINVAL; }

@@ -6,7 +6,6 @@ The descriptor is the mathematically exact one: the orthonormalising matrices be
 4e15, so they are built in mpmath at 60 digits and rounded once to float64 (SoapBasis).  There is no CPU fallback."""
 from __future__ import annotations
 
-import ctypes
 import functools
 import math
 from typing import Sequence
@@ -15,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._batch import typed_batch
 
 DIGITS = 60   # working precision of the tables (decimal digits)
 
@@ -100,10 +100,6 @@ class SoapBasis:
         return self._device[key]
 
 
-def _host_ptr(a):
-    return ctypes.c_void_p(a.ctypes.data)
-
-
 def _centre_list(centres, sizes, N):
     """-> int32 numpy list of batch-wide atom indices"""
     if isinstance(centres, str):
@@ -131,39 +127,22 @@ def soap_descriptors(pos: torch.Tensor, onehot: torch.Tensor, sizes: Sequence[in
     batch, any order, repeats allowed.  Neighbours of a centre: the atoms of its graph closer than ``neighbour_cut`` (default
     r_cut + sigma sqrt(2 ln 1000)), itself included.  With return_coefficients also the orthonormalised coefficients, float64
     [C, A, n_max, (l_max+1)^2] at [l*l + l + m]."""
-    if not pos.is_cuda:
-        raise RuntimeError("soap_descriptors needs CUDA(ROCm) tensors; there is no CPU fallback")
+    batch = typed_batch(pos, onehot, sizes, "soap_descriptors", min_atoms=1, max_types=_lib.SOAP_MAX_TYPES)
+    sizes, B, N, A, dev = batch.sizes, batch.B, batch.N, batch.A, batch.dev
     basis = SoapBasis() if basis is None else basis
-    sizes = [int(s) for s in sizes]
-    B, N = len(sizes), sum(sizes)
-    if B < 1 or min(sizes) < 0 or N < 1:
-        raise ValueError("soap_descriptors needs at least one graph, at least one atom and no negative size")
-    if pos.shape != (N, 3):
-        raise ValueError("position must be [sum(sizes), 3]")
-    oh = onehot.detach().to(pos.device)
-    if oh.dim() != 2 or oh.shape[0] != N or oh.shape[1] < 1:
-        raise ValueError("onehot must be [sum(sizes), A]")
-    A = int(oh.shape[1])
-    if A > _lib.SOAP_MAX_TYPES:
-        raise ValueError(f"{A} atom types (at most {_lib.SOAP_MAX_TYPES})")
-    if not bool((((oh == 0) | (oh == 1)).all(1) & (oh.sum(1) == 1)).all()):
-        raise ValueError("every row of onehot must be exactly one-hot")
     cut = basis.neighbour_cut if neighbour_cut is None else float(neighbour_cut)
     if not (math.isfinite(cut) and cut > 0.0):
         raise ValueError("neighbour_cut must be positive and finite")
-    dev = pos.device
     c_host = _centre_list(centres, sizes, N)
     head = np.concatenate([np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32), c_host])
     blob = torch.from_numpy(head).to(dev)   # one upload: graph_ptr, then the centres
     gp, c_dev = blob[:B + 1], blob[B + 1:]
-    p = pos.detach().to(torch.float32).contiguous()
-    t = oh.argmax(1).to(torch.int32).contiguous()
     C, F = int(c_host.size), basis.features(A)
     desc = torch.empty(C, F, dtype=torch.float64, device=dev)
     coeff = torch.empty(C, A, basis.n_max, (basis.l_max + 1) ** 2, dtype=torch.float64, device=dev) if return_coefficients else None
     tables = basis.device_tables(dev)
-    _lib.check(_lib.lib().egnn_soap_descriptor(_lib.stream_ptr(), B, N, A, _lib.ptr(p), _lib.ptr(t), _lib.ptr(gp), basis.n_max, basis.l_max,
-                                               cut, _lib.ptr(tables), C, _host_ptr(c_host), _lib.ptr(c_dev), _lib.ptr(desc), _lib.ptr(coeff)))
+    _lib.check(_lib.lib().egnn_soap_descriptor(_lib.stream_ptr(), B, N, A, _lib.ptr(batch.pos), _lib.ptr(batch.type), _lib.ptr(gp), basis.n_max, basis.l_max,
+                                               cut, _lib.ptr(tables), C, _lib.host_ptr(c_host), _lib.ptr(c_dev), _lib.ptr(desc), _lib.ptr(coeff)))
     return (desc, coeff) if return_coefficients else desc
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._batch import block_index, typed_batch
 
 
 def _graph_ptr(sizes, device):
@@ -29,7 +30,7 @@ def rdf(position: torch.Tensor, sizes: Sequence[int] | None = None, sigma=5, R=5
     gp, B, N = _graph_ptr(sizes, position.device)
     if position.shape != (N, 3):
         raise ValueError("position must be [sum(sizes), 3]")
-    nbins = len(np.arange(0 + dR, R + dR, dR))
+    nbins = _nbins(R, dR)
     pos = position.detach().to(torch.float32).contiguous()
     out = torch.empty(B, nbins, device=position.device)
     _lib.check(_lib.lib().egnn_rdf(_lib.stream_ptr(), B, _lib.ptr(pos), _lib.ptr(gp), float(R), float(dR), float(sigma),
@@ -438,16 +439,10 @@ def _struct_tiles(sizes):
     32 of 512 and one of 4096 atoms all give 256 workgroups -- and bond tiles {g, c0, 0} for every block of 8 centres.
     -> (int32 [n_pair, 3], int32 [n_bond, 3])"""
     sz = np.asarray(list(sizes), dtype=np.int64)
-    g = np.arange(sz.size, dtype=np.int64)
-
-    def blocks(per_graph):
-        gi = np.repeat(g, per_graph)
-        return gi, np.arange(int(per_graph.sum()), dtype=np.int64) - np.repeat(np.cumsum(per_graph) - per_graph, per_graph)
-
     n_cb, n_jb = -(-sz // _lib.STRUCT_CENTRE_BLOCK), -(-sz // _lib.STRUCT_CHUNK)
-    gi, t = blocks(n_cb * n_jb)
+    gi, t = block_index(n_cb * n_jb)
     pair = np.stack([gi, (t // n_jb[gi]) * _lib.STRUCT_CENTRE_BLOCK, (t % n_jb[gi]) * _lib.STRUCT_CHUNK], 1)
-    gi, t = blocks(-(-sz // _lib.STRUCT_BOND_CENTRES))
+    gi, t = block_index(-(-sz // _lib.STRUCT_BOND_CENTRES))
     bond = np.stack([gi, t * _lib.STRUCT_BOND_CENTRES, np.zeros_like(t)], 1)
     return pair.astype(np.int32).reshape(-1, 3), bond.astype(np.int32).reshape(-1, 3)
 
@@ -456,27 +451,10 @@ class _StructInput:
     """positions, type indices and the work lists of a batch on the device (one upload of graph_ptr and both tile lists)"""
 
     def __init__(self, pos, onehot, sizes, what):
-        if not pos.is_cuda:
-            raise RuntimeError(f"{what} needs CUDA(ROCm) tensors; there is no CPU fallback")
-        sizes = [int(s) for s in sizes]
-        self.sizes, self.B, self.N = sizes, len(sizes), sum(sizes)
-        if self.B < 1 or min(sizes) < 0:
-            raise ValueError(f"{what} needs at least one graph and no negative size")
-        if pos.shape != (self.N, 3):
-            raise ValueError("position must be [sum(sizes), 3]")
-        oh = onehot.detach().to(pos.device)
-        if oh.dim() != 2 or oh.shape[0] != self.N or oh.shape[1] < 1:
-            raise ValueError("onehot must be [sum(sizes), A]")
-        self.A = int(oh.shape[1])
-        if self.N and not bool((((oh == 0) | (oh == 1)).all(1) & (oh.sum(1) == 1)).all()):
-            raise ValueError("every row of onehot must be exactly one-hot")
-        self.dev = pos.device
-        self.pos = pos.detach().to(torch.float32).contiguous()
-        self.type = (oh.argmax(1) if self.N else torch.zeros(0, dtype=torch.long, device=self.dev)).to(torch.int32).contiguous()
-        self.max_atoms = max(sizes)
-        pair, bond = _struct_tiles(sizes)
+        vars(self).update(vars(typed_batch(pos, onehot, sizes, what, min_atoms=0)))   # sizes, B, N, A, max_atoms, dev, pos, type
+        pair, bond = _struct_tiles(self.sizes)
         gp = np.zeros(self.B + 1, dtype=np.int64)
-        gp[1:] = np.cumsum(sizes)
+        gp[1:] = np.cumsum(self.sizes)
         blob = torch.from_numpy(np.concatenate([gp.astype(np.int32), pair.reshape(-1), bond.reshape(-1)])).to(self.dev)
         self.gp, self.pair_tiles, self.bond_tiles = blob.split([self.B + 1, pair.size, bond.size])
         self.n_pair, self.n_bond = len(pair), len(bond)
@@ -607,38 +585,16 @@ def compare_structures(original_graph_list, generated_graph_list, sigma=5, R=5.0
 COVALENT_RADII = (0.66, 1.11)   # (O, Si), Cordero et al. 2008, in the order of the one-hot columns ([1, 0] is O)
 
 
-def _host_ptr(a):
-    import ctypes
-    return ctypes.c_void_p(a.ctypes.data)
-
-
 class _TopoInput:
     """positions, type indices, graph_ptr and the bond lists of a batch on the device (egnn_topo_bonds: three launches)"""
 
     def __init__(self, pos, onehot, sizes, radii, scale, what):
-        if not pos.is_cuda:
-            raise RuntimeError(f"{what} needs CUDA(ROCm) tensors; there is no CPU fallback")
-        sizes = [int(s) for s in sizes]
-        self.sizes, self.B, self.N = sizes, len(sizes), sum(sizes)
-        if self.B < 1 or min(sizes) < 0 or self.N < 1:
-            raise ValueError(f"{what} needs at least one graph, at least one atom and no negative size")
-        if pos.shape != (self.N, 3):
-            raise ValueError("position must be [sum(sizes), 3]")
-        oh = onehot.detach().to(pos.device)
-        if oh.dim() != 2 or oh.shape[0] != self.N or oh.shape[1] < 1:
-            raise ValueError("onehot must be [sum(sizes), A]")
-        self.A = int(oh.shape[1])
-        if not bool((((oh == 0) | (oh == 1)).all(1) & (oh.sum(1) == 1)).all()):
-            raise ValueError("every row of onehot must be exactly one-hot")
+        vars(self).update(vars(typed_batch(pos, onehot, sizes, what, min_atoms=1)))   # sizes, B, N, A, max_atoms, dev, pos, type
         radii = np.asarray(radii, dtype=np.float64).reshape(-1)
         if radii.size != self.A:
             raise ValueError(f"{radii.size} radii for {self.A} atom types")
         self.thr = np.ascontiguousarray(float(scale) * (radii[:, None] + radii[None, :]))   # fp64, once per type pair
-        self.dev = pos.device
-        self.pos = pos.detach().to(torch.float32).contiguous()
-        self.type = oh.argmax(1).to(torch.int32).contiguous()
-        self.max_atoms = max(sizes)
-        sz = np.asarray(sizes, dtype=np.int64)
+        sz = np.asarray(self.sizes, dtype=np.int64)
         head = np.concatenate([[0], np.cumsum(sz), [0], np.cumsum(sz * sz)])   # graph_ptr [B+1], then dist_ptr [B+1]
         blob = torch.from_numpy(head).to(self.dev)                              # one upload
         self.gp = blob[:self.B + 1].to(torch.int32)
@@ -647,7 +603,7 @@ class _TopoInput:
         i32 = lambda n: torch.empty(n, dtype=torch.int32, device=self.dev)
         self.row_ptr, self.neighbours, self.degree, self.overflow = i32(self.N + 1), i32(_lib.TOPO_MAX_DEGREE * self.N), i32(self.N), i32(self.B)
         _lib.check(_lib.lib().egnn_topo_bonds(_lib.stream_ptr(), self.B, self.N, self.A, _lib.ptr(self.pos), _lib.ptr(self.type),
-                                              _lib.ptr(self.gp), self.max_atoms, _host_ptr(self.thr), _lib.ptr(self.row_ptr),
+                                              _lib.ptr(self.gp), self.max_atoms, _lib.host_ptr(self.thr), _lib.ptr(self.row_ptr),
                                               _lib.ptr(self.neighbours), _lib.ptr(self.degree), _lib.ptr(self.overflow)))
 
     def paths(self, max_length, dist=False, component=False, fp=True):
@@ -842,9 +798,7 @@ def _sq_tiles(sizes):
     -> (int32 [n_tiles, 3], int32 [B+1])"""
     sz = np.asarray(list(sizes), dtype=np.int64)
     n_cb, n_jb = -(-sz // _lib.SQ_ROW_BLOCK), -(-sz // _lib.SQ_CHUNK)
-    per = n_cb * n_jb
-    gi = np.repeat(np.arange(sz.size, dtype=np.int64), per)
-    t = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
+    gi, t = block_index(n_cb * n_jb)
     c0, j0 = (t // np.maximum(n_jb[gi], 1)) * _lib.SQ_ROW_BLOCK, (t % np.maximum(n_jb[gi], 1)) * _lib.SQ_CHUNK
     keep = np.minimum(j0 + _lib.SQ_CHUNK, sz[gi]) - 1 > c0   # the last j of the block lies above its first i
     tiles = np.stack([gi[keep], c0[keep], j0[keep]], 1).astype(np.int32).reshape(-1, 3)

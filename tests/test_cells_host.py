@@ -19,8 +19,6 @@ No fixture executed from the reference is possible: the cell library it builds o
 by execution")."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -28,9 +26,9 @@ import pytest
 from diffusion_model_amd import _lib
 from diffusion_model_amd.cells import lattice_from_parameters
 from tests import _cells_util as CU
+from tests._host_program import build_and_run
 
 EINVAL = -22
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @functools.lru_cache(maxsize=None)
@@ -239,14 +237,6 @@ def test_argument_errors_return_einval():
 # ---- sanitizers ---------------------------------------------------------------------------------------------------------------------
 def test_cell_env_host_under_sanitizers(tmp_path):
     """the executable links its own sanitizer runtime (statically), so nothing is preloaded"""
-    exe = str(tmp_path / "cell_env_main")
-    csrc = os.path.join(ROOT, "diffusion_model_amd", "csrc")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "host", "cell_env_main.cpp"),
-           os.path.join(csrc, "cells", "cell_host.cpp"), os.path.join(csrc, "host_logic.cpp"), "-o", exe]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=120)
+    r = build_and_run(tmp_path, "cell_env_main", ["cells/cell_host.cpp", "host_logic.cpp"])
     assert r.returncode == 0 and "CELL-ENV-OK" in r.stdout, f"rc={r.returncode}\nstdout:\n{r.stdout}\nstderr:\n{r.stderr[-4000:]}"
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]

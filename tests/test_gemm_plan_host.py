@@ -9,12 +9,10 @@ import atexit
 import functools
 import os
 import shutil
-import subprocess
 import tempfile
 
 from tests import _gemm_cases as GC
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests._host_program import build_and_run
 
 
 @functools.lru_cache(maxsize=None)
@@ -22,16 +20,10 @@ def host_program_run():
     """build and run the program once per session -> (return code, stdout, stderr)"""
     tmp = tempfile.mkdtemp(prefix="gemm_plan_")
     atexit.register(shutil.rmtree, tmp, ignore_errors=True)
-    exe, cases = os.path.join(tmp, "gemm_plan_main"), os.path.join(tmp, "cases.txt")
+    cases = os.path.join(tmp, "cases.txt")
     with open(cases, "w") as f:
         f.write(GC.host_case_lines())
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "host", "gemm_plan_main.cpp"),
-           os.path.join(ROOT, "diffusion_model_amd", "csrc", "host_logic.cpp"), "-o", exe]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, cases], env=env, capture_output=True, text=True, timeout=120)
+    r = build_and_run(tmp, "gemm_plan_main", ["host_logic.cpp"], args=[cases])
     return r.returncode, r.stdout, r.stderr
 
 

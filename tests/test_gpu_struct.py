@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import diffusion_model_amd as dma
-from diffusion_model_amd import stats
+from diffusion_model_amd import _lib, stats
 from tests import _struct_util as SU
 from tests._util import load_golden
 
@@ -251,3 +251,23 @@ def test_compare_structures():
         x, y = co.double().sum(0)[0, 1], cg.double().sum(0)[0, 1]
         assert abs(float(res["total"][key]["l2"][0, 1]) - stats.rdf_l2(x, y)) <= 1e-5 * max(1.0, stats.rdf_l2(x, y))
     assert checked >= 32 and float(res["rdf"]["l2"][0].max()) > 0.1 and float(res["rdf"]["l2"][1].max()) == 0.0
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two devices")
+def test_the_lds_limit_is_raised_on_every_device_of_a_process():
+    """both kernels at their largest dynamic LDS (A = 4 with nbins = 1024; dtheta = 0.5 with max_cn = 64: above the 64 KiB a function
+    is given by default), first on cuda:0, then on cuda:1 of the same process, each equal to the host statement: the limit belongs
+    to the function on one device, so the second device needs a raise of its own"""
+    sizes, A = [5, 1, 70], 4   # 70 crosses the 64-centre block
+    kw = dict(R=10.24, dR=0.01, cutoff=2.0, dtheta=0.5, max_cn=64)
+    pos, types = SU.random_batch(11, sizes, A)
+    assert SU.nbins_of(kw["R"], kw["dR"]) == 1024 and SU.batch_statistics(pos, types, sizes, A, **kw)[4] >= 1e-9, "ambiguous input"
+    rc, c_w, cn_w, ang_w, over_w = SU.host_counts(_lib.lib(), pos, types, sizes, A, **kw)
+    assert rc == 0 and over_w.sum() == 0 and c_w.sum() > 0 and ang_w.sum() > 0
+    for dev in ("cuda:0", "cuda:1"):
+        with torch.cuda.device(dev):
+            p, oh = torch.from_numpy(pos).to(dev), _onehot(types, A).to(dev)
+            c = stats.pair_counts(p, oh, sizes, R=kw["R"], dR=kw["dR"])
+            cn, ang = stats.bond_statistics(p, oh, sizes, cutoff=kw["cutoff"], dtheta=kw["dtheta"], max_cn=kw["max_cn"])
+        assert np.array_equal(c.cpu().numpy(), c_w), dev
+        assert np.array_equal(cn.cpu().numpy(), cn_w) and np.array_equal(ang.cpu().numpy(), ang_w), dev

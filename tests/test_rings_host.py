@@ -17,8 +17,6 @@ csrc/eval/rings_math.h), without a GPU:
   * the host statement runs clean under AddressSanitizer + UBSan as a stand-alone program (tests/host/rings_main.cpp)."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -27,9 +25,9 @@ from diffusion_model_amd import _lib
 from tests import _cells_util as CU
 from tests import _ring_util as RU
 from tests import _topo_util as TU
+from tests._host_program import build_and_run
 
 EINVAL = -22
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @functools.lru_cache(maxsize=None)
@@ -221,14 +219,6 @@ def test_argument_errors_return_einval():
 # ---- sanitizers ---------------------------------------------------------------------------------------------------------------------
 def test_rings_host_under_sanitizers(tmp_path):
     """the executable links its own sanitizer runtime (statically), so nothing is preloaded"""
-    exe = str(tmp_path / "rings_main")
-    csrc = os.path.join(ROOT, "diffusion_model_amd", "csrc")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "host", "rings_main.cpp"),
-           os.path.join(csrc, "eval", "rings_host.cpp"), os.path.join(csrc, "host_logic.cpp"), "-o", exe]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=120)
+    r = build_and_run(tmp_path, "rings_main", ["eval/rings_host.cpp", "host_logic.cpp"])
     assert r.returncode == 0 and "RINGS-OK" in r.stdout, f"rc={r.returncode}\nstdout:\n{r.stdout}\nstderr:\n{r.stderr[-4000:]}"
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]

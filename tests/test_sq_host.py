@@ -12,8 +12,6 @@ compile through sq_math.h) against
 Every input first passes the gap checks of tests/_sq_util.py (asserted, never skipped).
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,9 +19,9 @@ import pytest
 from diffusion_model_amd import _lib
 from tests import _cells_util as CU
 from tests import _sq_util as SU
+from tests._host_program import build_and_run
 
 EINVAL = -22
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = SU.golden()
 Q = G["q"]
 CLUSTERS = ("ragged", "coincident", "lorch")
@@ -282,14 +280,6 @@ def test_the_tile_list_visits_every_pair_block_once():
 # ---- sanitizers ----------------------------------------------------------------------------------------------------------------------
 def test_sq_host_under_sanitizers(tmp_path):
     """the executable links its own sanitizer runtime (statically), so nothing is preloaded"""
-    exe = str(tmp_path / "sq_main")
-    csrc = os.path.join(ROOT, "diffusion_model_amd", "csrc")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "host", "sq_main.cpp"),
-           os.path.join(csrc, "eval", "sq_host.cpp"), os.path.join(csrc, "host_logic.cpp"), "-o", exe]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=120)
+    r = build_and_run(tmp_path, "sq_main", ["eval/sq_host.cpp", "host_logic.cpp"])
     assert r.returncode == 0 and "SQ-OK" in r.stdout, f"rc={r.returncode}\nstdout:\n{r.stdout}\nstderr:\n{r.stderr[-4000:]}"
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]

@@ -58,7 +58,7 @@ def edge_kernel_sources_sha256() -> str:
     of the packing that writes the streams they read (pack.hip), and the compiler flags: what a PMC measurement of those kernels
     (profiles/traffic.json) is valid for.  A hash of the .so itself would not survive a rebuild in another directory (hipcc
     derives its per-TU symbol ids from the path)."""
-    return _sources_sha256(("edge_x_m16.hip", "edge_bf16_v4.hip", "pack.hip", "edge_tile.h", "kernels.h", "common.h", "layer_pack.h",
+    return _sources_sha256(("edge_x_m16.hip", "edge_bf16_v4.hip", "pack.hip", "edge_tile.h", "kernels.h", "x_walk.h", "common.h", "layer_pack.h",
                             "diag.h"))
 
 
@@ -68,7 +68,7 @@ def forward_sources_sha256() -> str:
     valid for."""
     return _sources_sha256(("egnn_forward.hip", "host_logic.h", "host_logic.cpp", "pack.hip", "edge_x_m16.hip", "edge_bf16_v4.hip", "edge_bf16_v3.hip", "edge_small.hip",
                             "edge_bf16x3.hip", "edge_f16c8w.hip", "edge_f16c8w_mphase2.inc", "edge_f16c8w_mphasek.inc", "node_bf16.hip",
-                            "edge_tile.h", "kernels.h", "common.h", "layer_pack.h", "diag.h"))
+                            "edge_tile.h", "kernels.h", "x_walk.h", "common.h", "layer_pack.h", "diag.h"))
 
 
 def training_sources_sha256() -> str:

@@ -40,6 +40,13 @@ constexpr size_t kA1 = (size_t)8 * kR * 16;   // one activation chunk: [8 k-grou
 __host__ __device__ constexpr size_t x16_smem_bytes(int KP) { return kOffLoop + 2 * kA1 + (size_t)KP * 4; }
 static_assert(x16_smem_bytes(256) == 48192 && x16_smem_bytes(512) == 49216 && x16_smem_bytes(1024) == 51264,
               "LDS allocation of the 16x16x32 coordinate kernels");
+// The persistent form at two column shares keeps the first kKept activation chunks of a tile in LDS behind s_wd: share 0 builds them
+// there, share 1 of the same tile (same workgroup, next step: x_walk.h) multiplies from there and builds only chunks kKept .. 15.
+// (6 with the per-tile arrays as they are; a 7th would fit only with L.part aliased onto the loop buffers.)
+constexpr int kKept = 6;
+__host__ __device__ constexpr size_t x16_persist_smem_bytes(int KP) { return x16_smem_bytes(KP) + (KP == 1024 ? kKept * kA1 : 0); }
+static_assert(x16_persist_smem_bytes(512) == 49216 && x16_persist_smem_bytes(1024) == 149568 && x16_persist_smem_bytes(1024) <= 160 * 1024,
+              "LDS allocation of the persistent 16x16x32 coordinate kernel");
 
 typedef __attribute__((ext_vector_type(4))) float f32x4v;
 
@@ -49,7 +56,8 @@ typedef __attribute__((ext_vector_type(4))) float f32x4v;
 // leaves, so that egcl_backward_heads_saved / the wgrad GEMMs find the same buffers.
 // V8 = the MFMA operand type: bf16x8 (precision bf16) or f16x8 (precision fp16: v_mfma_f32_16x16x32_f16, same rate, 11
 // significant bits; weights packed x 2^8, kernels.h "MFMA operand type").
-// PERSIST = true (inference): one workgroup per CU walks over its share of the (tile, column share) units, and the NEXT unit's edge
+// PERSIST = true (inference): one workgroup per CU walks over its share of the (tile, column share) units (x_walk.h: whole tiles, share 0
+// then share 1, with the first kKept activation chunks kept in LDS between the two; the remainder as single units), and the NEXT unit's edge
 // indices, coordinates, first table rows and first weight fragments are requested under the CURRENT unit's epilogue (4 us of vector
 // arithmetic, the matrix pipe idle): the three dependent memory round trips of the prologue (2.2 us of a 26 us workgroup,
 // profiles/r03t_fwd_wg_stamps.txt) and the dispatch gap between workgroups (0.3 us) leave the critical path.
@@ -73,52 +81,56 @@ __global__ __launch_bounds__(kTileThreads, 2) void edge_x_m16_kernel(const EdgeP
   const rsrc_t rs_w = make_rsrc(p.w2x, diag::drop_weight_loads(p.dbg) ? 0u : (unsigned)((size_t)p.WxP * KP * 2));
   const unsigned offP = 0u, offQ = (unsigned)p.WxP * 2u;   // fp16 table: {Px | Qx | Pm | Qm}
   const unsigned lane16 = lane * 16u;
-  const int nunits = PERSIST ? ((p.E + kR - 1) / kR) * nsplit : (int)gridDim.x;
+  const int ntiles = (p.E + kR - 1) / kR;
+  const rsrc_t rs_tab0 = make_rsrc(p.table, 0u);   // every load out of range: zeros, no memory traffic
   UnitH uc0, uc1;   // table pieces of chunk 0
   V8 bq[2][4];      // weight fragments of the 2 k-steps of the current chunk
   // PERSIST: what the prologue of the next unit needs, requested under the epilogue of the current one
   int pf_d0, pf_s0, pf_d1, pf_s1, pf_d, pf_s, pf_r0, pf_r1;   // (pf_r0/1: row_ptr[dst], row_ptr[dst + 1] of row tid: the segment modes)
   float pf_x[6];
-  auto unit_of = [&](const int bv, int& tile_o, int& half_o) {
-    const int jj = xcd_tile(bv, nunits);
-    tile_o = jj / nsplit;
-    half_o = jj - tile_o * nsplit;
-  };
   // (tq: the caller's copy of the thread index -- an opaque one inside the unit loop, so that brow / kg are re-derived there instead of
   // living across the K loop)
-  auto prefetch_indices = [&](const int bv, const int tq) {   // this thread's two build rows (all threads) and row tid (threads 0-127)
-    int t, h;
-    unit_of(bv, t, h);
+  auto prefetch_indices = [&](const int t, const int tq) {   // this thread's two build rows (all threads) and row tid (threads 0-127) of tile t
     const int ne0 = t * kR, nnv = min(kR, p.E - ne0), br = tq >> 3;
     const bool r0 = br < nnv, r1 = br + 64 < nnv, rt = tq < nnv && tq < kR;
     pf_d0 = r0 ? p.edge_dst[ne0 + br] : 0; pf_s0 = r0 ? p.edge_src[ne0 + br] : 0;
     pf_d1 = r1 ? p.edge_dst[ne0 + br + 64] : 0; pf_s1 = r1 ? p.edge_src[ne0 + br + 64] : 0;
     pf_d = rt ? p.edge_dst[ne0 + tq] : 0; pf_s = rt ? p.edge_src[ne0 + tq] : 0;
   };
-  auto prefetch_data = [&](const int bv, const int tq) {      // coordinates of row tid, table pieces of chunk 0, first weight fragments
-    int t, h;
-    unit_of(bv, t, h);
+  // coordinates of row tid, table pieces of chunk 0, first weight fragments of column share h.  (tab = rs_tab0 in front of a share 1
+  // that finds chunk 0 in LDS: the same instructions, so that every prefetch register is written on every path, but no table rows)
+  auto prefetch_data = [&](const int h, const rsrc_t tab, const int tq) {
     const unsigned k16 = (unsigned)(tq & 7) * 16u, l16 = (unsigned)(tq & 63) * 16u;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { pf_x[k] = p.x[3 * pf_d + k]; pf_x[3 + k] = p.x[3 * pf_s + k]; }   // (threads >= 128: node 0, unused; written by every thread so that nothing is carried around the K loop)
     pf_r0 = p.row_ptr[pf_d]; pf_r1 = p.row_ptr[pf_d + 1];
-    unith_load(uc0, rs_tab, (unsigned)pf_d0 * (unsigned)p.TC * 2u + k16, (unsigned)pf_s0 * (unsigned)p.TC * 2u + k16, offP, offQ);
-    unith_load(uc1, rs_tab, (unsigned)pf_d1 * (unsigned)p.TC * 2u + k16, (unsigned)pf_s1 * (unsigned)p.TC * 2u + k16, offP, offQ);
+    unith_load(uc0, tab, (unsigned)pf_d0 * (unsigned)p.TC * 2u + k16, (unsigned)pf_s0 * (unsigned)p.TC * 2u + k16, offP, offQ);
+    unith_load(uc1, tab, (unsigned)pf_d1 * (unsigned)p.TC * 2u + k16, (unsigned)pf_s1 * (unsigned)p.TC * 2u + k16, offP, offQ);
     const unsigned nw0 = (unsigned)(h * 32 + wave * 4) * KS * 1024u;
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) bq[s][cb] = ldbuf_v8<V8>(rs_w, l16, nw0 + ((unsigned)cb * KS + s) * 1024u);
   };
+  XUnit cur{0, 0, false, true};
+  int kstep = 0;
   if constexpr (PERSIST) {
+    cur = x_walk(blockIdx.x, gridDim.x, ntiles, nsplit, 0);
+    if (!cur.valid) return;   // (uniform; cannot happen above the persistent threshold of plan_forward)
     for (int i = tid; i < KP; i += kTileThreads) s_wd[i] = p.wdx[i];   // (ordered by the first unit's row barrier)
-    prefetch_indices(blockIdx.x, tid);
-    prefetch_data(blockIdx.x, tid);
+    prefetch_indices(cur.tile, tid);
+    prefetch_data(cur.share, rs_tab, tid);
   }
-  int bv = blockIdx.x;
   do {
-  const int j = xcd_tile(bv, nunits);
-  const int tile = j / nsplit, half = j - tile * nsplit;
+  const int j = PERSIST ? 0 : xcd_tile(blockIdx.x, gridDim.x);
+  const int tile = PERSIST ? cur.tile : j / nsplit, half = PERSIST ? cur.share : j - tile * nsplit;
+  // kept: chunks < kKept live in their own LDS buffers (share 0 builds them there); skip: share 1 behind its share 0 -- the tile's rows,
+  // geometry, segments and first kKept chunks are in LDS already (all uniform)
+  const bool kept = PERSIST && cur.kept, skip = kept && half == 1;
+  const unsigned kept_off = 2u * (unsigned)kA1 + (unsigned)KP * 4u;   // kept buffer 0, from s_a1 (behind the loop buffers and s_wd)
+  auto chunk_off = [&](const int c) -> unsigned {   // byte offset of chunk c's buffer from s_a1: a wave-uniform scalar
+    return (kept && c < kKept) ? kept_off + (unsigned)c * (unsigned)kA1 : (unsigned)(c & 1) * (unsigned)kA1;
+  };
   const int e0 = tile * kR;
   const int nvalid = min(kR, p.E - e0);
 
@@ -133,7 +145,7 @@ __global__ __launch_bounds__(kTileThreads, 2) void edge_x_m16_kernel(const EdgeP
   const int lane_p = tid_p & 63;
   if constexpr (!PERSIST) {
     prologue_rows(p, L, e0, nvalid, p.wdx, KP, s_wd, tid);
-  } else {   // prologue_rows of edge_tile.h from the prefetched registers
+  } else if (!skip) {   // prologue_rows of edge_tile.h from the prefetched registers
     const int tid = tid_p;
     if (tid < kR) {
       const float dx = pf_x[0] - pf_x[3], dy = pf_x[1] - pf_x[4], dz = pf_x[2] - pf_x[5];   // (rows past the list: index 0 twice = 0)
@@ -196,18 +208,20 @@ __global__ __launch_bounds__(kTileThreads, 2) void edge_x_m16_kernel(const EdgeP
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) bq[s][cb] = ldbuf_v8<V8>(rs_w, lane16, w0 + ((unsigned)cb * KS + s) * 1024u);
   }
-  const int S = prologue_segments<false>(p, L, e0, nvalid, tid_p, lane_p, wave);   // seg_mode: under the first matrix phase, below
+  int S;
+  if (!skip) S = prologue_segments<false>(p, L, e0, nvalid, tid_p, lane_p, wave);   // seg_mode: under the first matrix phase, below
+  else S = L.misc[0];
   if constexpr (PERSIST) {   // segment_mode of edge_tile.h from the prefetched row_ptr words of the segment's first row (read in the epilogue)
-    if (tid_p < S) {
+    if (!skip && tid_p < S) {
       const int* rp = reinterpret_cast<const int*>(L.gseg);
       const int r0 = L.seg_rs[tid_p];
       const bool first = (e0 + r0) == rp[r0], last = (e0 + L.seg_re[tid_p] + 1) == rp[kR + r0];
       L.seg_mode[tid_p] = (first && last) ? 2 : (first ? 1 : 0);
     }
   }
-  {
-    const V8 o0 = unith_finish<V8>(uc0, s_wd + b.kg * 8, b.d2r0, slot0);
-    const V8 o1 = unith_finish<V8>(uc1, s_wd + b.kg * 8, b.d2r1, slot1);
+  if (!skip) {
+    const V8 o0 = unith_finish<V8>(uc0, s_wd + b.kg * 8, b.d2r0, slot0 + chunk_off(0));
+    const V8 o1 = unith_finish<V8>(uc1, s_wd + b.kg * 8, b.d2r1, slot1 + chunk_off(0));
     if constexpr (SAVE) s1_store(o0, o1, 0);
   }
   __syncthreads();
@@ -218,7 +232,7 @@ __global__ __launch_bounds__(kTileThreads, 2) void edge_x_m16_kernel(const EdgeP
   // so lgkmcnt(2) before a use means "all but the 2 younger reads have landed".  The weight fragments of k-step s of chunk c + 1 are requested after the MFMAs of
   // k-step s of chunk c (a whole chunk of distance).
   auto mphase = [&](const int c, const bool last) {
-    const unsigned boff = (unsigned)(c & 1) * (unsigned)kA1;
+    const unsigned boff = chunk_off(c);
     const unsigned ab0 = abase0 + boff, ab1 = abase1 + boff;
     V8 a[3];   // ring of 3 operand pieces: use u = 8 s + rb takes a[u % 3], which is refilled for use u + 3 right after
                    // (a fourth set costs the 4 registers that made hipcc spill around the K loop: 63 MB of scratch traffic per launch)
@@ -260,7 +274,7 @@ __global__ __launch_bounds__(kTileThreads, 2) void edge_x_m16_kernel(const EdgeP
     unith_load(ua1, b.tab, b.vdst1, b.vsrc1, b.offP + kb, b.offQ + kb);
   };
   auto vfinish = [&](const int c) {  // SiLU + bf16 pack of chunk c into its LDS buffer
-    const size_t nbuf = (size_t)(c & 1) * kA1;
+    const size_t nbuf = chunk_off(c);
     __builtin_amdgcn_s_setprio(3);   // vector work wins issue arbitration over the partner wave's MFMAs
     const V8 o0 = unith_finish<V8>(ua0, s_wd + c * kChunkK + b.kg * 8, b.d2r0, slot0 + nbuf);
     const V8 o1 = unith_finish<V8>(ua1, s_wd + c * kChunkK + b.kg * 8, b.d2r1, slot1 + nbuf);
@@ -274,11 +288,17 @@ __global__ __launch_bounds__(kTileThreads, 2) void edge_x_m16_kernel(const EdgeP
   DIAG_STAMP(30, 2);   // chunk 0 built, first weights requested
   WG_STAMP(2);
   DIAG_RSTAMP(31, 1);
-  vload(1);
+  // skip: chunks 0 .. kKept - 1 are multiplied only (no build, no barrier: nothing is written), then the loop as ever from chunk
+  // kKept - 1, whose matrix phase runs beside the build of chunk kKept.  The multiply-only loop and the first table request are written
+  // into both arms of the wave branch: with the loop in front of the branch hipcc spills 896 bytes per lane, with the request in front of
+  // it 8 bytes inside the K loop; this way the kernel has no scratch at all (40 bytes before, profiles/x_pair_bound.txt).
+  const int istart = skip ? kKept - 1 : 0;
   if (wave < 4) {
     // row_ptr loads of the segment modes (needed by the epilogue only) ride under the first matrix phase of wave 0
     const int my_mode = (!PERSIST && tid_p < S) ? segment_mode(p, L, e0, tid_p) : 0;
-    for (int i = 0; i < NC - 1; ++i) {
+    if constexpr (PERSIST) for (int i = 0; i < istart; ++i) mphase(i, false);
+    vload(istart + 1);
+    for (int i = istart; i < NC - 1; ++i) {
       mphase(i, false);
       if (!PERSIST && i == 0 && tid_p < S) L.seg_mode[tid_p] = my_mode;
       vfinish(i + 1);
@@ -286,7 +306,11 @@ __global__ __launch_bounds__(kTileThreads, 2) void edge_x_m16_kernel(const EdgeP
       __syncthreads();
     }
   } else {
-    for (int i = 0; i < NC - 1; ++i) {
+    // (this arm builds first: the rows of chunk kKept are requested one multiply-only chunk earlier)
+    if constexpr (PERSIST) for (int i = 0; i < istart - 1; ++i) mphase(i, false);
+    vload(istart + 1);
+    if constexpr (PERSIST) { if (skip) mphase(istart - 1, false); }
+    for (int i = istart; i < NC - 1; ++i) {
       vfinish(i + 1);
       vload(i + 2);
       __builtin_amdgcn_sched_barrier(0);
@@ -305,10 +329,15 @@ __global__ __launch_bounds__(kTileThreads, 2) void edge_x_m16_kernel(const EdgeP
   if constexpr (PERSIST) asm volatile("" : "+v"(tid_e));
   const int lane_e = tid_e & 63, r15_e = lane_e & 15, q4_e = lane_e >> 4;
   // accumulator layout of the 16x16 tile: column = lane_e & 15, row = 4 (lane_e >> 4) + register
-  const bool more = PERSIST && bv + (int)gridDim.x < nunits;   // (uniform)
   // (the last unit requests itself again: unconditional writes, so that no old value of the prefetch registers is carried around the K loop)
-  const int bnext = more ? bv + (int)gridDim.x : bv;
-  if constexpr (PERSIST) prefetch_indices(bnext, tid_e);
+  XUnit nxt = cur;
+  bool more = false;   // (uniform)
+  if constexpr (PERSIST) {
+    const XUnit n2 = x_walk(blockIdx.x, gridDim.x, ntiles, nsplit, kstep + 1);
+    more = n2.valid;
+    if (more) nxt = n2;
+    prefetch_indices(nxt.tile, tid_e);
+  }
   float part[32];
 #pragma unroll
   for (int v = 0; v < 32; ++v) part[v] = 0.f;
@@ -387,7 +416,9 @@ __global__ __launch_bounds__(kTileThreads, 2) void edge_x_m16_kernel(const EdgeP
       }
   }
   WG_STAMP(6);   // second-layer SiLU + w3 products done
-  if constexpr (PERSIST) prefetch_data(bnext, tid_e);   // (the accumulators are dead: registers to spare)
+  // (the accumulators are dead: registers to spare.  In front of the share 1 that follows its share 0 only the weight fragments are
+  // new: the table rows are dropped, the indices and coordinates are the tile's own again)
+  if constexpr (PERSIST) prefetch_data(nxt.share, more && nxt.kept && nxt.share == 1 ? rs_tab0 : rs_tab, tid_e);
   {
     float t0, t1;
     butterfly16(part, lane_e, t0, t1);   // value indices 2 m, 2 m + 1 (m = lane_e & 15): row block m >> 1, register 2 (m & 1) + {0, 1}
@@ -416,7 +447,8 @@ __global__ __launch_bounds__(kTileThreads, 2) void edge_x_m16_kernel(const EdgeP
   WG_STAMP_HW();
   if constexpr (!PERSIST) break;
   if (!more) break;
-  bv += (int)gridDim.x;
+  cur = nxt;
+  ++kstep;
   __syncthreads();   // the row / segment arrays of this unit have been read
   } while (true);
 }
@@ -438,7 +470,7 @@ int init_edge_x_m16_attributes() {
 }
 
 bool edge_x_m16_supported(const EdgeParams& p) {
-  return (p.WxP == 512 || p.WxP == 1024) && p.w2x16 != nullptr && x16_smem_bytes(p.WxP) <= 160 * 1024 &&
+  return (p.WxP == 512 || p.WxP == 1024) && p.w2x16 != nullptr && x16_persist_smem_bytes(p.WxP) <= 160 * 1024 &&
          (size_t)p.N * p.TC * 2 < ((size_t)1 << 32);
 }
 
@@ -447,7 +479,7 @@ bool edge_x_m16_supported(const EdgeParams& p) {
 // p.s_half_out receive what the backward needs (see the kernel's SAVE mode; instantiated for bf16 only)
 int launch_edge_x_m16(const EdgeParams& p, hipStream_t st, bool f16, XForm form, int grid) {
   const int units = (p.E + kR - 1) / kR * (p.WxP / 512);
-  const size_t sm = x16_smem_bytes(p.WxP);
+  const size_t sm = x16_smem_bytes(p.WxP), smp = x16_persist_smem_bytes(p.WxP);
   EdgeParams q = p;
   q.w2x = p.w2x16;
   switch (form) {
@@ -456,8 +488,8 @@ int launch_edge_x_m16(const EdgeParams& p, hipStream_t st, bool f16, XForm form,
       hipLaunchKernelGGL(edge_x_m16_kernel<true>, dim3(units), dim3(kTileThreads), sm, st, q);
       break;
     case XForm::kPersistent:
-      if (f16) hipLaunchKernelGGL((edge_x_m16_kernel<false, f16x8, true>), dim3(grid), dim3(kTileThreads), sm, st, q);
-      else hipLaunchKernelGGL((edge_x_m16_kernel<false, bf16x8, true>), dim3(grid), dim3(kTileThreads), sm, st, q);
+      if (f16) hipLaunchKernelGGL((edge_x_m16_kernel<false, f16x8, true>), dim3(grid), dim3(kTileThreads), smp, st, q);
+      else hipLaunchKernelGGL((edge_x_m16_kernel<false, bf16x8, true>), dim3(grid), dim3(kTileThreads), smp, st, q);
       break;
     case XForm::kPerUnit:
       if (f16) hipLaunchKernelGGL((edge_x_m16_kernel<false, f16x8>), dim3(units), dim3(kTileThreads), sm, st, q);

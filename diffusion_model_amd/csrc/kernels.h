@@ -22,13 +22,13 @@ __device__ __forceinline__ float sigmoid_f(float v) { return __builtin_amdgcn_rc
 __device__ __forceinline__ int acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 
 
-// XCD-aware workgroup -> tile map: workgroups b and b+8 share an XCD (round-robin dispatch), so give
-// each XCD a contiguous range of tiles; tiles of one graph then share an L2 (table rows are re-read
-// by every tile of the graph).  Bijective for any grid size; affects speed only.
-__device__ __forceinline__ int xcd_tile(int b, int nwg) {
-  const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
+// XCD-aware workgroup -> tile map xcd_tile(b, nwg): workgroups b and b+8 share an XCD (round-robin dispatch), so each XCD gets a
+// contiguous range of tiles; tiles of one graph then share an L2.  It lives in x_walk.h with the walk of the persistent coordinate
+// kernel that is built on it: plain integer arithmetic for host and device, enumerated on the host by tests/host/x_walk_main.cpp.
+}  // namespace egnn
+#include "x_walk.h"
+namespace egnn {
+
 
 struct EdgeParams {
   int N, E;

@@ -9,11 +9,12 @@ GPU tests and by tools/cells_time.py (test infrastructure):
         one lattice diagonal, minimum-image distances in the TRIPLED lattice, return_index_within_2ang nested to 2 / 3 / 4 levels,
         positions float32(X_site) - float32(X_centre), plus a flag raised when a bond it used wraps round the supercell
         (``reference_environment``);
-  (iii) seeded cell generators (chain, beta-cristobalite, its triclinic distortion, random cells, the one-atom cell), each
-        asserting the gap condition: no pair distance within 1e-9 A of the cutoff, so that the float64 comparison is unambiguous
-        on every side.
+  (iii) seeded cell generators (chain, beta-cristobalite, its triclinic distortion, random cells, the one-atom cell; the dense
+        jittered grids, the ladder that reaches shift +-4 and the 60-degree zincblende cell), each asserting the gap condition: no
+        pair distance within 1e-9 A of the cutoff, so that the float64 comparison is unambiguous on every side.
 """
 import ctypes as C
+import functools
 import itertools
 
 import numpy as np
@@ -163,7 +164,7 @@ def reference_environment(L, frac, centre, levels, cutoff=CUTOFF, rows=None):
 def _cell(lattice, frac, types, name, cutoff=CUTOFF, check=True):
     """``check=False`` (tools/cells_time.py, cells too large for the numpy bond list) leaves out the restated bond list and its gap"""
     cell = dict(lattice=np.asarray(lattice, dtype=np.float64), frac=np.asarray(frac, dtype=np.float64).reshape(-1, 3),
-                types=np.asarray(types, dtype=np.int32), A=2, name=name)
+                types=np.asarray(types, dtype=np.int32), A=2, name=name, cutoff=float(cutoff))
     assert np.all(widths(cell["lattice"]) >= cutoff), name
     if not check:
         return cell
@@ -221,6 +222,90 @@ def random_cell(n, seed, spread=0.0, check=True):
         w = np.concatenate([w, f[None, :]])
     frac = w + (np.floor(rng.uniform(-spread, spread + 1.0, w.shape)) if spread else 0.0)
     return _cell(L, frac, rng.integers(0, 2, n), f"random-{n}", check=check)
+
+
+def grid_cell(nx, ny, nz, a, cutoff, seed=1, jitter=0.02, drop=0, skew=False):
+    """a jittered simple-cubic block of nx x ny x nz atoms, spacing a: fractions g / dims + jitter N(0, 1) / dims (g ascending in
+    (x, y, z)), types drawn after the jitter; ``skew`` tilts b by 0.3 A along x and c by -0.2 A along y; ``drop`` removes the
+    first ``drop`` atoms (vacancies).  With a well below the cutoff this is the dense regime: two dozen bonds per atom and several
+    hundred sites at 4 shells"""
+    dims = np.array([nx, ny, nz], dtype=np.float64)
+    g = np.array(list(itertools.product(range(nx), range(ny), range(nz))), dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    frac = g / dims + jitter * rng.standard_normal(g.shape) / dims
+    types = rng.integers(0, 2, len(g))
+    L = np.diag(dims * a)
+    if skew:
+        L[1, 0], L[2, 1] = 0.3, -0.2
+    name = f"grid-{nx}x{ny}x{nz}-{a}" + ("-skew" if skew else "") + (f"-drop{drop}" if drop else "")
+    return _cell(L, frac[drop:], types[drop:], name, cutoff=cutoff)
+
+
+def ladder_cell():
+    """cubic a = 2.05 A, five atoms 0.41 A apart along x: 8 bonds per atom, all along x (the images in y and z are 2.05 A away), so
+    that four hops from atom 0 reach shift -4 and from atom 4 shift +4: the ends of the shift code's range"""
+    return _cell(2.05 * np.eye(3), [[x, 0.3, 0.3] for x in (0.0, 0.2, 0.4, 0.6, 0.8)], [0, 1, 0, 1, 0], "ladder")
+
+
+def zincblende_cell():
+    """the primitive fcc cell of zincblende, a_conv = 2.6 A: 60 degree angles, perpendicular widths 2.123 A just above the cutoff,
+    one coordinate below 0"""
+    L = 2.6 / np.sqrt(2.0) * np.array([[0.0, 1.0, 1.0], [1.0, 0.0, 1.0], [1.0, 1.0, 0.0]])
+    return _cell(L, [[0.02, 0.01, -0.03], [0.25, 0.25, 0.25]], [1, 0], "zincblende")
+
+
+def cscl_cell():
+    """cubic a = 2.05 A, atoms near (0, 0, 0) and at (1/2, 1/2, 1/2), 1.78 A apart: each atom is bonded to EIGHT images of the
+    other and to nothing else -- the most images of one atom a cell whose widths reach the cutoff can bond, so one lane of the
+    bond kernel sets eight bits of its mask"""
+    return _cell(2.05 * np.eye(3), [[0.01, 0.02, -0.01], [0.5, 0.5, 0.5]], [0, 1], "cscl")
+
+
+def frontier_sizes(bond, centre, shells):
+    """(i) -> the number of sites first reached at hop 0 (the centre: 1), 1, .., shells - 1: the frontiers a breadth-first search
+    of ``shells`` hops expands"""
+    row_ptr, b_atom, b_code, _ = bond
+    b_shift = shift_decode(b_code)
+    start = (int(centre), 0, 0, 0)
+    seen, frontier, out = {start}, [start], []
+    for _ in range(shells):
+        out.append(len(frontier))
+        nxt = []
+        for (a, sx, sy, sz) in frontier:
+            for e in range(row_ptr[a], row_ptr[a + 1]):
+                site = (int(b_atom[e]), sx + int(b_shift[e, 0]), sy + int(b_shift[e, 1]), sz + int(b_shift[e, 2]))
+                if site not in seen:
+                    seen.add(site)
+                    nxt.append(site)
+        frontier = nxt
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def dense_cells():
+    """the cells of the dense regime, by name -- environments of several hundred sites, frontiers of several wavefronts, bond rows
+    at the ring search's degree limit: the 80-atom skewed grid (24-26 bonds per atom), the 27-atom grid at cutoff 1.6 (32 bonds per
+    atom, more than 1024 sites at 4 shells), the same grid with 5 vacancies, the ladder, the zincblende and the CsCl cell"""
+    return dict(g80=grid_cell(5, 4, 4, 1.1, 2.0, skew=True), g22=grid_cell(3, 3, 3, 0.75, 1.6, drop=5), g27=grid_cell(3, 3, 3, 0.75, 1.6),
+                ladder=ladder_cell(), zincblende=zincblende_cell(), cscl=cscl_cell())
+
+
+def dense_centres(name):
+    """the centres the restatement is run on (pure Python, 10 ms per centre of 700-1,000 sites): every third atom of a grid, every
+    atom of the two small cells"""
+    n = len(dense_cells()[name]["frac"])
+    return np.arange(0, n, 3 if n > 5 else 1)
+
+
+@functools.lru_cache(maxsize=None)
+def dense_reach(name, shells):
+    """what restatement (i) says a search of ``shells`` hops about dense_centres(name) meets: dict(env = restated_environments of
+    those centres, sizes, frontier = the largest frontier expanded per centre, max_shift = the largest |s| in an environment)"""
+    c = dense_cells()[name]
+    ctr = dense_centres(name)
+    env = restated_environments([c], centres=ctr, shells=shells)
+    return dict(env=env, sizes=env["size"].astype(np.int64), frontier=np.array([max(frontier_sizes(c["bonds"], i, shells)) for i in ctr]),
+                max_shift=int(np.abs(shift_decode(env["shift"])).max()))
 
 
 def host_environments(lib, cells, centres=None, shells=2, cutoff=CUTOFF, max_atoms=256, A=None, centre_cell=None, raw=None, caps=None):

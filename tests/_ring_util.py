@@ -11,7 +11,8 @@ the CPU and GPU tests and by tools/rings_time.py (test infrastructure):
         from j is at most min(i, size - 2 - i) + 1 <= max_size // 2 bonds from the centre;
   (iii) ctypes wrappers of egnn_rings_host (``host``) and egnn_rings (``device``) over raw CSR arrays;
   and the bond lists the tests use, as dicts ``csr`` = (N, row_ptr, atom, shift | None, types, A, ptr): periodic cells of
-  tests/_cells_util.py at any cutoff, clusters of tests/_topo_util.py at any scale, and the hand-made saturation graph."""
+  tests/_cells_util.py at any cutoff, clusters of tests/_topo_util.py at any scale, the hand-made saturation graph and the fan
+  graph whose one search labels 2,594 sites through levels of 1,024."""
 import ctypes as C
 
 import numpy as np
@@ -76,6 +77,97 @@ def layered_csr(layers=12, width=8):
     csr = dict(N=N, row_ptr=rp, atom=np.concatenate([nb[a] for a in range(N)]).astype(np.int32), shift=None,
                types=(np.arange(N) % 2).astype(np.int32), A=2, ptr=np.array([0, N]))
     return csr, true, layers + 3
+
+
+def fan_csr(widths=(16, 256, 1024, 1024, 256, 16), extra=3):
+    """centre 0 - j = 1 - layers of ``widths`` atoms - k = 2, in the style of layered_csr but wide: j is bonded to the whole first
+    layer and k to the whole last.  Where the next layer is r times as wide (r >= 1), node i is bonded to nodes (i r + t) mod w' for
+    t < r + extra; where it is r times narrower, to node i // r and, unless r divides i, to node (i // r + 1) mod w'.  One search
+    from j labels every atom but the centre, level by level: a frontier of max(widths) sites, a table load of a third, and a node of
+    the last layer carries 2 r bonds.  -> (csr, the layers as index arrays); every degree is asserted <= 32"""
+    first, layer = 3, []
+    for w in widths:
+        layer.append(np.arange(first, first + w))
+        first += w
+    nb = {a: set() for a in range(first)}
+
+    def bond(a, b):
+        nb[int(a)].add(int(b))
+        nb[int(b)].add(int(a))
+
+    bond(0, 1), bond(0, 2)
+    for a in layer[0]:
+        bond(1, a)
+    for a in layer[-1]:
+        bond(2, a)
+    for lo, hi in zip(layer[:-1], layer[1:]):
+        w, w2 = len(lo), len(hi)
+        if w2 >= w:
+            assert w2 % w == 0
+            r = w2 // w
+            for i in range(w):
+                for t in range(r + extra):
+                    bond(lo[i], hi[(i * r + t) % w2])
+        else:
+            assert w % w2 == 0
+            r = w // w2
+            for i in range(w):
+                bond(lo[i], hi[i // r])
+                if i % r:
+                    bond(lo[i], hi[(i // r + 1) % w2])
+    deg = np.array([len(nb[a]) for a in range(first)])
+    assert deg.max() <= MAX_DEGREE, (int(deg.max()), int(np.argmax(deg)))
+    csr = dict(N=first, row_ptr=np.concatenate([[0], np.cumsum(deg)]).astype(np.int32),
+               atom=np.concatenate([sorted(nb[a]) for a in range(first)]).astype(np.int32), shift=None,
+               types=(np.arange(first) % 2).astype(np.int32), A=2, ptr=np.array([0, first]))
+    return csr, layer
+
+
+def fan_centres(layer):
+    """centres of the fan graph beside atom 0: j, k and atoms inside every layer, the wide ones included"""
+    return np.array([0, 1, 2, layer[0][7], layer[1][100], layer[2][5], layer[2][1023], layer[3][700], layer[4][17], layer[5][3]], dtype=np.int32)
+
+
+def dense_ring_centres(name):
+    """six centres of a dense cell of tests/_cells_util.py (the pure-Python restatement takes 0.1-0.2 s per centre there)"""
+    n = len(CU.dense_cells()[name]["frac"])
+    return np.arange(0, n, n // 6, dtype=np.int32)[:6]
+
+
+def home_slots(atoms, slots):
+    """the slot a cluster site (atom, shift 0) hashes to in a table of ``slots`` entries (csrc/eval/rings_math.h: ring_key, ring_hash
+    = the finaliser of splitmix64), restated in Python integers.  Two sites with one home slot make a probe chain whatever the
+    order of insertion"""
+    m64 = (1 << 64) - 1
+    out = []
+    for a in atoms:
+        k = (int(a) << 18) | (32 << 12) | (32 << 6) | 32
+        k ^= k >> 30
+        k = (k * 0xbf58476d1ce4e5b9) & m64
+        k ^= k >> 27
+        k = (k * 0x94d049bb133111eb) & m64
+        k ^= k >> 31
+        out.append((k & 0xFFFFFFFF) & (slots - 1))
+    return np.array(out)
+
+
+def level_widths(csr, c, p):
+    """the number of sites a search from row position p of centre c labels at level 0, 1, ..: plain breadth-first over the CSR
+    with the centre removed (clusters: no shifts), to the end"""
+    assert csr["shift"] is None
+    rp, at = csr["row_ptr"], csr["atom"]
+    source = int(at[rp[c] + p])
+    seen, frontier, out = {int(c), source}, [source], []
+    while frontier:
+        out.append(len(frontier))
+        nxt = []
+        for a in frontier:
+            for b in at[rp[a]:rp[a + 1]].tolist():
+                if b not in seen:
+                    seen.add(b)
+                    nxt.append(b)
+        frontier = nxt
+    return out
 
 
 def angle_ptr(csr, centres):

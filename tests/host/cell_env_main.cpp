@@ -2,7 +2,10 @@
 // tests/test_cells_host.py.  Every output array is allocated at EXACTLY the size the first call reports, so that ASan sees a write
 // past the bond list or past an environment: the two-atom chain cell (3 / 5 / 7 / 9 sites for 1-4 shells, shifts up to 2),
 // ideal beta-cristobalite (24 atoms, 4 bonds per Si and 2 per O, 9 sites at 2 shells, 33 at 4), both in one batch, and the overflow
-// case (max_atoms = 8 where every environment holds 9: sentinel sizes, no row written).
+// case (max_atoms = 8 where every environment holds 9: sentinel sizes, no row written).  The dense regime: the exact 2 x 2 x 2
+// simple-cubic cell of spacing 1.1 A (26 bonds per atom, 27 / 125 / 343 / 729 sites for 1-4 shells) at max_atoms = 729, which fits,
+// and 728, where the two scratch lists of max_atoms + 2 keys are at their fullest before the sentinel; and the ladder (five atoms
+// 0.41 A apart in a 2.05 A cell: 33 sites at 4 shells, shifts up to +-4, the ends of the code range).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -58,6 +61,20 @@ void add_cristobalite(Batch& b) {
     }
   b.add(7.16, f, t);
 }
+
+void add_cubic_block(Batch& b) {   // 2 x 2 x 2 atoms, 1.1 A apart: neighbours at 1.1, 1.556 and 1.905 A, the next at 2.2 A
+  std::vector<double> f;
+  std::vector<int32_t> t;
+  for (int x = 0; x < 2; ++x)
+    for (int y = 0; y < 2; ++y)
+      for (int z = 0; z < 2; ++z) {
+        f.push_back(0.5 * x); f.push_back(0.5 * y); f.push_back(0.5 * z);
+        t.push_back((x + y + z) & 1);
+      }
+  b.add(2.2, f, t);
+}
+
+void add_ladder(Batch& b) { b.add(2.05, {0.0, 0.3, 0.3, 0.2, 0.3, 0.3, 0.4, 0.3, 0.3, 0.6, 0.3, 0.3, 0.8, 0.3, 0.3}, {0, 1, 0, 1, 0}); }
 
 struct Result {
   std::vector<int32_t> bond_ptr, bond_atom, bond_shift, size, atom, shift, type;
@@ -122,6 +139,40 @@ int main() {
     CHECK(r.size[0] == 5 && r.atom.size() == 10u, "the chain's two environments are the only rows (%zu)", r.atom.size());
     Result ok = run(b, centre_cell, centre, 2, 9);
     CHECK(ok.atom.size() == 10u + 24u * 9u, "max_atoms = 9 holds them (%zu)", ok.atom.size());
+  }
+  {   // the dense regime: 729 sites per centre, and the ladder's shifts of +-4
+    Batch d;
+    add_cubic_block(d);
+    add_ladder(d);
+    std::vector<int32_t> cc, ct;
+    for (int c = 0; c < 2; ++c)
+      for (int i = d.cell_ptr[c]; i < d.cell_ptr[c + 1]; ++i) { cc.push_back(c); ct.push_back(i); }
+    const int block_sites[5] = {0, 27, 125, 343, 729};
+    for (int shells = 1; shells <= 4; ++shells) {
+      Result r = run(d, cc, ct, shells, 729);
+      for (int i = 0; i < 8; ++i) {
+        CHECK(r.bond_ptr[i + 1] - r.bond_ptr[i] == 26, "cubic block: %d bonds at atom %d", r.bond_ptr[i + 1] - r.bond_ptr[i], i);
+        CHECK(r.size[i] == block_sites[shells], "cubic block: %d sites at %d shells", r.size[i], shells);
+      }
+      for (int i = 8; i < 13; ++i) {
+        CHECK(r.bond_ptr[i + 1] - r.bond_ptr[i] == 8, "ladder: %d bonds at atom %d", r.bond_ptr[i + 1] - r.bond_ptr[i], i);
+        CHECK(r.size[i] == 1 + 8 * shells, "ladder: %d sites at %d shells", r.size[i], shells);
+      }
+      if (shells < 4) continue;
+      CHECK(r.atom.size() == 8u * 729u + 5u * 33u, "%zu rows", r.atom.size());
+      int at = 8 * 729, low = 0, high = 0;
+      for (int i = 8; i < 13; ++i)
+        for (int k = 0; k < 33; ++k, ++at) {
+          int s[3];
+          cell_shift_decode(r.shift[at], s);
+          CHECK(s[1] == 0 && s[2] == 0, "the ladder runs along x");
+          if (i == 8 || i == 12) { low = s[0] < low ? s[0] : low; high = s[0] > high ? s[0] : high; }
+        }
+      CHECK(low == -4 && high == 4, "ladder: shifts from %d to %d", low, high);
+    }
+    Result full = run(d, cc, ct, 4, 728);   // one below: keys and seen hold max_atoms + 1 entries when the search stops
+    for (int i = 0; i < 8; ++i) CHECK(full.size[i] == 729, "sentinel %d", full.size[i]);
+    CHECK(full.size[8] == 33 && full.atom.size() == 5u * 33u, "the ladder's environments are the only rows (%zu)", full.atom.size());
   }
   {   // refused arguments leave every output alone
     Batch bad;

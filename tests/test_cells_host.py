@@ -10,7 +10,9 @@ compile, csrc/cells/cell_math.h), without a GPU:
   * positions agree with the reference's spelling float32(X_site) - float32(X_centre) within 2^-22 max|X|: two input roundings of
     2^-24 |X|, the subtraction's rounding and our own (each at most 2^-24 of a value below max|X|);
   * egnn_cell_env_host equals restatement (i) EXACTLY in every integer output and within 1 float32 ulp per position component, on
-    every input and on mixed batches, fractional coordinates outside [0, 1) included;
+    every input and on mixed batches, fractional coordinates outside [0, 1) included; so it does in the dense regime the device
+    tests rest on (dense_cells of tests/_cells_util.py: 700-1,000-site environments, frontiers of several hundred sites, 32 bonds
+    per atom, shifts of +-4, the sentinel at a size of 729 / 993 / 1,233 sites), whose reach is asserted from the restatement;
   * bad arguments return EGNN_EINVAL with a message naming the cause, from the host statement and -- before anything is launched
     -- from the device entries;
   * the host statement runs clean under AddressSanitizer + UBSan as a stand-alone program (tests/host/cell_env_main.cpp).
@@ -112,10 +114,17 @@ def test_chain_cell_is_the_documented_deviation():
 
 
 # ---- the host statement against the restatement ----------------------------------------------------------------------------------
-def _assert_host_equals_restatement(cells, centres=None, shells=2):
-    rc, got = CU.host_environments(_lib.lib(), cells, centres=centres, shells=shells)
+def _assert_host_equals_restatement(cells, centres=None, shells=2, cutoff=CU.CUTOFF, max_atoms=256, want=None):
+    """a centre whose restated environment exceeds ``max_atoms`` must show the sentinel max_atoms + 1 and no row; ``want``: the
+    restatement of these centres where the caller has it already"""
+    rc, got = CU.host_environments(_lib.lib(), cells, centres=centres, shells=shells, cutoff=cutoff, max_atoms=max_atoms)
     assert rc == 0, _lib.lib().egnn_last_error()
-    want = CU.restated_environments(cells, centres=centres, shells=shells)
+    want = dict(CU.restated_environments(cells, centres=centres, shells=shells) if want is None else want)
+    assert all(c["cutoff"] == cutoff for c in cells)                       # the restated bond lists are those of this cutoff
+    fits = np.repeat(want["size"] <= max_atoms, want["size"])
+    want["size"] = np.where(want["size"] <= max_atoms, want["size"], max_atoms + 1).astype(np.int32)
+    for k in ("atom", "shift", "type", "pos"):
+        want[k] = want[k][fits]
     for k in ("bond_ptr", "bond_atom", "bond_shift", "size", "atom", "shift", "type"):
         assert got[k].dtype == np.int32 and np.array_equal(got[k], want[k]), k
     assert np.all(np.isfinite(got["pos"])) and CU.ulp_distance(got["pos"], want["pos"]).max(initial=0) <= 1
@@ -157,6 +166,95 @@ def test_host_statement_overflow_sentinel():
     assert rc == 0 and np.all(got["size"] == 9) and len(got["atom"]) == 0          # sizes are 9: every centre exceeds 8
     rc, got = CU.host_environments(_lib.lib(), [c], shells=2, max_atoms=9)
     assert rc == 0 and np.all(got["size"] == 9) and len(got["atom"]) == 9 * 24
+
+
+# ---- the dense regime: environments, frontiers and bond rows beyond one wavefront ---------------------------------------------------
+def test_dense_cells_reach_the_regime():
+    """what the device tests of this regime rest on, from restatement (i) alone: an input that stops reaching it fails here"""
+    cs = CU.dense_cells()
+    deg = {k: np.diff(c["bonds"][0]) for k, c in cs.items()}
+    assert len(cs["g80"]["frac"]) == 80 and deg["g80"].min() >= 24 and deg["g80"].max() <= 32      # past the 64-centre tile and the 64-lane block
+    assert len(cs["g22"]["frac"]) == 22 and deg["g22"].min() >= 24 and deg["g22"].max() <= 32
+    assert len(cs["g27"]["frac"]) == 27 and np.all(deg["g27"] == 32)                               # the ring search's degree limit, not beyond
+    assert np.all(deg["ladder"] == 8) and np.all(deg["zincblende"] == 4)
+    assert np.all(np.abs(CU.widths(cs["zincblende"]["lattice"]) - 2.6 * np.sqrt(2.0 / 3.0)) < 1e-12) and cs["zincblende"]["frac"].min() < 0.0
+    # bond rows: the 80-atom cell's rows hold atoms of both 64-lane blocks; in the 27-atom cell one atom bonds through several images
+    rp, at, _, _ = cs["g80"]["bonds"]
+    both = [i for i in range(80) if np.sum(at[rp[i]:rp[i + 1]] < 64) >= 8 and np.sum(at[rp[i]:rp[i + 1]] >= 64) >= 8]
+    assert len(both) >= 32 and min(both) < 64 <= max(both)                  # rows carried across the lane blocks, in both centre tiles
+    rp, at, _, _ = cs["g27"]["bonds"]
+    assert max(np.bincount(at[rp[i]:rp[i + 1]]).max() for i in range(27)) >= 2
+    rp, at, _, _ = cs["cscl"]["bonds"]
+    assert at.tolist() == [1] * 8 + [0] * 8 and rp.tolist() == [0, 8, 16]                    # eight images of ONE atom: eight bits in one lane
+    reach = {k: CU.dense_reach(k, 4) for k in cs}
+    assert reach["g80"]["sizes"].min() > 512 and reach["g80"]["sizes"].max() <= 1024 and reach["g80"]["frontier"].min() > 64
+    assert reach["g22"]["sizes"].min() > 960 and reach["g22"]["sizes"].max() <= 1024 and reach["g22"]["frontier"].min() > 256
+    assert np.all(reach["g27"]["sizes"] == reach["g27"]["sizes"][0]) and reach["g27"]["sizes"][0] > 1024
+    assert reach["g80"]["max_shift"] == 2 and reach["g22"]["max_shift"] == 3 and reach["g27"]["max_shift"] == 3
+    assert reach["ladder"]["sizes"].tolist() == [33] * 5 and reach["ladder"]["max_shift"] == 4 and reach["zincblende"]["sizes"].tolist() == [83] * 2
+    env = reach["ladder"]["env"]
+    sx = CU.shift_decode(env["shift"])[:, 0].reshape(5, 33)
+    assert sx[0].min() == -4 and sx[0].max() == 3 and sx[4].min() == -3 and sx[4].max() == 4          # the two ends of the code range
+    three = {k: CU.dense_reach(k, 3)["sizes"] for k in ("g80", "g27")}
+    assert 256 < three["g80"].min() and three["g80"].max() <= 448 and np.all(three["g27"] == three["g27"][0]) and 512 < three["g27"][0] <= 960
+
+
+@pytest.mark.parametrize("name", ["g80", "g22", "g27", "ladder", "zincblende", "cscl"])
+@pytest.mark.parametrize("shells", [1, 2, 3, 4])
+def test_host_statement_equals_the_restatement_on_dense_cells(name, shells):
+    """max_atoms = 1024; the 27-atom cell at 4 shells holds more: there the sentinel and no row"""
+    c = CU.dense_cells()[name]
+    reach = CU.dense_reach(name, shells)
+    got = _assert_host_equals_restatement([c], centres=CU.dense_centres(name), shells=shells, cutoff=c["cutoff"], max_atoms=1024, want=reach["env"])
+    assert (got["size"].max() == 1025) == (name == "g27" and shells == 4)
+
+
+def _dense_mixed():
+    cs = CU.dense_cells()
+    batch = [cs["ladder"], cs["g80"], cs["zincblende"], CU.one_atom_cell()]
+    centres = np.concatenate([np.arange(5), 5 + np.arange(1, 80, 3), [85, 86, 87]])              # centres in every cell
+    return batch, centres
+
+
+def test_host_statement_equals_the_restatement_on_the_dense_mixed_batch():
+    batch, centres = _dense_mixed()
+    got = _assert_host_equals_restatement(batch, centres=centres, shells=3, max_atoms=1024)
+    assert got["size"][:5].tolist() == [25] * 5 and got["size"][5:-3].min() > 256 and got["size"][-3:].tolist() == [41, 41, 1]
+    _assert_host_equals_restatement(batch, centres=centres[::-1], shells=3, max_atoms=1024)
+
+
+@pytest.mark.parametrize("name", ["g80", "g22"])
+def test_host_statement_sentinel_at_the_largest_dense_environment(name):
+    """max_atoms = the largest size fits; one less gives exactly the largest centres the sentinel and no row.  keys and seen of the
+    host statement (max_atoms + 2 entries) are then at their fullest"""
+    c = CU.dense_cells()[name]
+    rc, full = CU.host_environments(_lib.lib(), [c], shells=4, cutoff=c["cutoff"], max_atoms=1024)
+    assert rc == 0
+    big = int(full["size"].max())
+    largest = np.nonzero(full["size"] == big)[0]
+    centres = np.concatenate([largest[:3], np.nonzero(full["size"] < big)[0][:2]])
+    assert big > 704 and len(centres) >= 4
+    want = CU.restated_environments([c], centres=centres, shells=4)
+    assert want["size"].max() == big == want["size"][0]                                       # the restatement agrees on the size
+    fit = _assert_host_equals_restatement([c], centres=centres, shells=4, cutoff=c["cutoff"], max_atoms=big, want=want)
+    assert fit["size"].max() == big
+    short = _assert_host_equals_restatement([c], centres=centres, shells=4, cutoff=c["cutoff"], max_atoms=big - 1, want=want)
+    assert len(short["atom"]) == int(want["size"][want["size"] < big].sum()) > 0
+    for g in (int(largest[0]), int(np.argmin(full["size"]))):                                 # one centre at its own size and one below
+        one = CU.restated_environments([c], centres=[g], shells=4)
+        s = int(one["size"][0])
+        assert s == full["size"][g] > 704
+        fit = _assert_host_equals_restatement([c], centres=[g], shells=4, cutoff=c["cutoff"], max_atoms=s, want=one)
+        assert fit["size"].tolist() == [s] and len(fit["atom"]) == s
+        short = _assert_host_equals_restatement([c], centres=[g], shells=4, cutoff=c["cutoff"], max_atoms=s - 1, want=one)
+        assert short["size"].tolist() == [s] and len(short["atom"]) == 0                      # max_atoms + 1 = s: the sentinel
+
+
+def test_host_statement_sentinel_beyond_1024_sites():
+    c = CU.dense_cells()["g27"]
+    assert np.all(CU.dense_reach("g27", 4)["sizes"] > 1024)
+    rc, got = CU.host_environments(_lib.lib(), [c], shells=4, cutoff=1.6, max_atoms=1024)
+    assert rc == 0 and np.all(got["size"] == 1025) and len(got["atom"]) == 0 and len(got["bond_atom"]) == 27 * 32
 
 
 # ---- argument errors --------------------------------------------------------------------------------------------------------------

@@ -5,7 +5,13 @@
     size, count, overflow and histogram: on the mixed cell batch at cutoff 2.0, on the random 65- and 160-atom cells at 2.8 with
     max_size 12, on the clouds of 1 .. 257 atoms at scale 1.5 (sizes on either side of 64 lanes and 128 / 256 rows), on the
     1,100-atom cell (atoms on either side of the 1024-atom chunk of the bond kernels), at the site limit L and L - 1 (the
-    overflow path), on the saturating layered graph, and on the crowd (33 bonds per atom);
+    overflow path), on the saturating layered graph, and on the crowd (33 bonds per atom).  None of these labels more than 589
+    sites in a search, has a frontier above the 256 threads or a centre above 12 bonds;
+  * beyond one workgroup of sites, the reach asserted from the restatement first: the fan graph (tests/_ring_util.py: fan_csr) --
+    levels of 1,024 sites, 2,594 sites labelled in 8,192 slots with shared home slots (probe chains) and slot numbers above 2^12 in
+    the uint16 lists, max_sites = 2,594 (fits), 2,593 (overflow) and 4,096, centres inside the wide layers -- equals the host
+    statement and the restatement; the dense cells with 24-26 and with exactly 32 bonds per atom (the limit, searched) equal the
+    host statement on every centre and the restatement on six, and cells.ring_statistics accepts the 32-bond cell;
   * two runs of one call are bitwise equal;
   * the Python functions return the known answers of cristobalite and of ring(6), select centres by type, compare a list with
     itself at L1 = 0 and cosine = 1, raise on the crowd and refuse CPU tensors."""
@@ -106,6 +112,71 @@ def test_device_saturates_and_reports_the_crowd():
     crowd = RU.clusters_csr(pos, types, [34], 2)
     got = _assert_device_equals_host(crowd, max_size=16)
     assert np.all(got["overflow"] == 1) and np.all(got["size"] == -1) and not got["hist"].any()
+
+
+# ---- beyond one workgroup of sites -----------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _fan():
+    """the fan graph and what the restatement says of the search from its centre (tests/test_rings_host.py holds the host
+    statement to it)"""
+    csr, layer = RU.fan_csr()
+    want = RU.restated(csr, centres=[0], max_size=16)
+    return csr, layer, want, int(want["labelled"][0])
+
+
+def test_device_equals_host_on_the_fan_graph():
+    """frontiers of 1,024 sites for 256 threads, 2,594 labelled sites in 8,192 slots (probe chains; slot numbers above 2^12 in the
+    uint16 lists), the site limit at exactly the number labelled and one below"""
+    csr, layer, want, labelled = _fan()
+    assert 2048 < labelled <= 4096 and max(RU.level_widths(csr, 0, 0)) > 256                 # preconditions, from the restatement
+    assert 1 < want["count"][0] < RU.COUNT_MAX and want["size"].tolist() == [len(layer) + 3] and np.diff(csr["row_ptr"]).max() == 32
+    home = RU.home_slots(range(1, csr["N"]), 8192)
+    assert np.sum(np.bincount(home, minlength=8192) > 1) >= 100 and home.max() >= 4096        # probe chains; slots beyond 12 bits
+    for max_sites in (labelled, 4096):
+        got = _assert_device_equals_host(csr, centres=[0], max_size=16, max_sites=max_sites)
+        RU.assert_equal(got, want)
+    short = _assert_device_equals_host(csr, centres=[0], max_size=16, max_sites=labelled - 1)
+    RU.assert_equal(short, RU.restated(csr, centres=[0], max_size=16, max_sites=labelled - 1))
+    assert short["overflow"].tolist() == [1] and short["size"].tolist() == [-1] and short["count"].tolist() == [0]
+    centres = RU.fan_centres(layer)
+    inside = RU.restated(csr, centres=centres, max_size=16)
+    assert inside["labelled"].max() > 2048 and inside["count"].max() > 1
+    got = _assert_device_equals_host(csr, centres=centres, max_size=16)
+    RU.assert_equal(got, inside)
+    again = RU.device(_lib.lib(), csr, centres=centres, max_size=16, mirrors=False)[1]
+    for k in ("size", "count", "overflow", "hist"):
+        assert np.array_equal(got[k], again[k]), k                                             # two runs, bitwise
+    spread = _assert_device_equals_host(csr, centres=np.arange(0, csr["N"], 16), max_size=12)    # 163 centres over every layer
+    assert not spread["overflow"].any() and len(set(spread["size"].tolist())) >= 4
+
+
+@pytest.mark.parametrize("name", ["g80", "g27"])
+def test_device_equals_host_at_the_degree_limit(name):
+    """the dense cells: 24-26 bonds per atom (up to 325 angles a centre), and exactly 32 bonds -- the limit, searched, not the
+    overflow -- about every atom"""
+    c = CU.dense_cells()[name]
+    csr = RU.cells_csr([c], cutoff=c["cutoff"])
+    deg = np.diff(csr["row_ptr"])
+    assert (deg.min() >= 24 and deg.max() <= 32) if name == "g80" else np.all(deg == 32)
+    got = _assert_device_equals_host(csr, max_size=16)                                         # all centres
+    assert not got["overflow"].any() and got["size"].min() >= 3 and got["count"].max() > 1
+    centres = RU.dense_ring_centres(name)
+    want = RU.restated(csr, centres=centres, max_size=16)
+    assert want["labelled"].min() > 256
+    RU.assert_equal(_assert_device_equals_host(csr, centres=centres, max_size=16), want)
+
+
+def test_cells_ring_statistics_at_the_degree_limit():
+    c = CU.dense_cells()["g27"]
+    csr = RU.cells_csr([c], cutoff=1.6)
+    assert np.all(np.diff(csr["row_ptr"]) == 32)
+    centres = RU.dense_ring_centres("g27")
+    want = RU.restated(csr, centres=centres, max_size=16)
+    rs = dma.cells.ring_statistics(_pcell(c), centres=torch.from_numpy(centres.astype(np.int64)), cutoff=1.6, device=DEV)      # does not raise
+    assert np.array_equal(rs.size.cpu().numpy(), want["size"]) and np.array_equal(rs.count.cpu().numpy(), want["count"])
+    ap = want["angle_ptr"]
+    smallest = [int(want["size"][ap[m]:ap[m + 1]][want["size"][ap[m]:ap[m + 1]] > 0].min()) for m in range(len(centres))]
+    assert rs.per_centre_smallest.tolist() == smallest and rs.angle_ptr.tolist() == ap.tolist() and ap[1] == 496
 
 
 # ---- the Python surface ---------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,8 @@ csrc/eval/rings_math.h), without a GPU:
     centre list with duplicates and at max_size 3, 4, 12, 32;
   * the site limit: max_sites = L (the largest number of sites a search of a Si centre of cristobalite labels, taken from (i))
     succeeds, L - 1 marks those centres overflowed with size -1; the count saturates at 2^31 - 1 on a layered graph with 8^12 paths;
+    the fan graph (2,594 sites labelled through levels of 1,024, the limit at 2,594 / 2,593) and the dense cells with 24-26 and
+    exactly 32 bonds per atom equal (i) as well;
   * bad arguments return EGNN_EINVAL with a message naming the cause, from the host statement and -- before a GPU is touched --
     from the device entry;
   * the host statement runs clean under AddressSanitizer + UBSan as a stand-alone program (tests/host/rings_main.cpp)."""
@@ -161,6 +163,43 @@ def test_count_saturates():
     assert want["size"].tolist() == [size] and want["count"].tolist() == [2 ** 31 - 1]
     RU.assert_equal(_host(csr, centres=[0], max_size=16), want)
     RU.assert_equal(_host(csr, max_size=16), RU.restated(csr, max_size=16))
+
+
+# ---- beyond one workgroup of sites: the fan graph, and bond rows at the degree limit --------------------------------------------------
+def test_fan_graph_labels_more_than_2048_sites():
+    """one search labels 2,594 sites through levels of 1,024 -- a frontier four times the device's workgroup, slot numbers above
+    2^12, a table a third full -- and fits exactly at max_sites = the number labelled"""
+    csr, layer = RU.fan_csr()
+    deg = np.diff(csr["row_ptr"])
+    assert deg.max() == 32 and np.all(deg[layer[-1]] == 32)                                # passed sites at the degree limit
+    want = RU.restated(csr, centres=[0], max_size=16)
+    labelled = int(want["labelled"][0])
+    assert 2048 < labelled <= 4096 and labelled == csr["N"] - 1 and max(RU.level_widths(csr, 0, 0)) > 256
+    home = RU.home_slots(range(1, csr["N"]), 8192)                                          # the table at max_sites > 2048
+    assert np.sum(np.bincount(home, minlength=8192) > 1) >= 100 and home.max() >= 4096      # probe chains; slots beyond 12 bits
+    assert want["size"].tolist() == [len(layer) + 3] and 1 < want["count"][0] < RU.COUNT_MAX and not want["overflow"].any()
+    for max_sites in (labelled, 4096):
+        RU.assert_equal(_host(csr, centres=[0], max_size=16, max_sites=max_sites), want)
+    short = RU.restated(csr, centres=[0], max_size=16, max_sites=labelled - 1)
+    assert short["overflow"].tolist() == [1] and short["size"].tolist() == [-1]
+    RU.assert_equal(_host(csr, centres=[0], max_size=16, max_sites=labelled - 1), short)
+    centres = RU.fan_centres(layer)
+    inside = RU.restated(csr, centres=centres, max_size=16)
+    assert inside["labelled"].max() > 2048 and inside["count"].max() > 1 and len(set(inside["size"].tolist()) - {0}) >= 4
+    RU.assert_equal(_host(csr, centres=centres, max_size=16), inside)
+
+
+@pytest.mark.parametrize("name", ["g80", "g27"])
+def test_host_statement_equals_the_restatement_at_the_degree_limit(name):
+    """the dense cells of tests/_cells_util.py: 24-26 bonds per atom, and exactly 32 -- the limit, not the overflow"""
+    c = CU.dense_cells()[name]
+    csr = RU.cells_csr([c], cutoff=c["cutoff"])
+    deg = np.diff(csr["row_ptr"])
+    assert (deg.min() >= 24 and deg.max() <= 32) if name == "g80" else np.all(deg == 32)
+    centres = RU.dense_ring_centres(name)
+    want = RU.restated(csr, centres=centres, max_size=16)
+    assert not want["overflow"].any() and want["labelled"].min() > 256 and want["size"].min() >= 3 and want["count"].max() > 1
+    RU.assert_equal(_host(csr, centres=centres, max_size=16), want)
 
 
 # ---- argument errors --------------------------------------------------------------------------------------------------------------

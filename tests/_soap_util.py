@@ -8,8 +8,11 @@ fixtures both use, and the ctypes wrapper of the host statement egnn_soap_host.
     the golden's exact tables, so it is as good as the host statement, not better;
   * row sums (dot products, norms, squared spectrum differences) in the one order of soap_math.h: element f to partial f % 64,
     partials ascending, then the butterfly 32, 16, .., 1 -- numpy rounds every operation, so they are BITWISE the library's.
+  * the basis limits and the degenerate bases (LIMIT_CONFIGS, each with its own A up to 4): their truth is
+    tests/golden/soap_limits_golden.npz (make_soap_limits_golden.py), atom 0 of the listed fixture graphs.
 Gap conditions (asserted by every test for its inputs): no pair distance within 1e-9 (relative) of the neighbour cut; for every
-target no two candidate MSEs within 1e-9 (relative) of each other.
+target no two candidate MSEs within 1e-9 (relative) of each other -- or, where the tie rule is the subject
+(mse_gap_ok_with_ties), no two DISTINCT ones.
 """
 import ctypes as C
 import functools
@@ -23,6 +26,22 @@ CONFIGS = {"default": dict(r_cut=8.0, n_max=15, l_max=10, sigma=0.1), "small": d
 GOLDEN_GRAPHS = {"default": 3, "small": len(SIZES)}       # the default configuration's truth covers the three smallest graphs
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "soap_golden.npz")
 POSITION_SEED = 11
+# The basis limits and the degenerate bases, each with ITS number of types A (a table of its own: CONFIGS x TYPES keep their
+# meaning).  "graphs": the fixture graphs whose atom 0 the truth covers (tests/golden/soap_limits_golden.npz); the 17-atom graph is
+# the first that holds all four species.  limit: kSoapMaxTypes, kSoapMaxN, kSoapMaxL of soap_math.h and the largest LDS request.
+LIMIT_CONFIGS = {
+    "limit": dict(r_cut=8.0, n_max=16, l_max=10, sigma=0.1, A=4, graphs=4),
+    "n16l0": dict(r_cut=8.0, n_max=16, l_max=0, sigma=0.1, A=2, graphs=5),       # LM = 1, L1 = 1: task / L1 and o / LM degenerate
+    "n1l0": dict(r_cut=4.0, n_max=1, l_max=0, sigma=0.1, A=4, graphs=7),         # a 1 x 1 beta on r = [1]
+    "n1l10": dict(r_cut=4.0, n_max=1, l_max=10, sigma=0.1, A=3, graphs=5),
+    "n7l5": dict(r_cut=6.0, n_max=7, l_max=5, sigma=0.1, A=4, graphs=4),         # odd, mid-size: nL = 42, LM = 36
+}
+LIMITS_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "soap_limits_golden.npz")
+
+
+def basis_of(cfg):
+    """the four parameters of SoapBasis / Basis out of an entry of CONFIGS or LIMIT_CONFIGS"""
+    return {k: cfg[k] for k in ("r_cut", "n_max", "l_max", "sigma")}
 
 
 def neighbour_cut(cfg):
@@ -198,11 +217,63 @@ def mse_gap_ok(m, rel=1e-9):
     return True
 
 
+def mse_gap_ok_with_ties(m, rel=1e-9):
+    """mse_gap_ok where exact duplicates are allowed: the DISTINCT finite values of a row stay rel apart, so the only ambiguity left
+    is the one the tie rule (the lower reference index first) decides"""
+    for row in m:
+        v = np.unique(row[np.isfinite(row)])
+        if len(v) > 1 and np.any(np.diff(v) <= rel * v[1:]):
+            return False
+    return True
+
+
 def spectra(seed, T, R, S):
     rng = np.random.default_rng(seed)
     base = rng.uniform(0.0, 1.5, (8, S))
     pick = lambda n: (base[rng.integers(0, 8, n)] + 0.2 * rng.standard_normal((n, S))).astype(np.float32)
     return pick(T), pick(R)
+
+
+TIE_ROWS, TIE_PAIR = (3, 17, 18, 40), (5, 6)
+
+
+def tie_spectra(S=200):
+    """5 targets, 70 references with exact duplicates: rows TIE_ROWS are one row, a float32 neighbour of target 0 (so the four-fold
+    tie takes the first places of target 0 and straddles the k-th place for k = 1, 2, 3), rows TIE_PAIR another, near target 1.  No
+    target equals a reference."""
+    t, r = spectra(77, 5, 70, S)
+    r = r.copy()
+    r[list(TIE_ROWS)] = t[0] + np.float32(0.015625) * np.cos(np.arange(S, dtype=np.float32))
+    r[list(TIE_PAIR)] = t[1] - np.float32(0.03125) * np.sin(1 + np.arange(S, dtype=np.float32))
+    assert not np.array_equal(r[3], t[0]) and not np.array_equal(r[5], t[1])
+    return t, r
+
+
+def nonfinite_spectra(S=65):
+    """4 targets, 12 references: reference 2 holds a NaN, reference 7 a +inf, target 1 a NaN"""
+    t, r = spectra(78, 4, 12, S)
+    t, r = t.copy(), r.copy()
+    r[2, S // 2], r[7, S - 1], t[1, 0] = np.nan, np.inf, np.nan
+    return t, r
+
+
+def cosine_rows(seed, rows, F):
+    """float64 rows with entries of either sign and magnitudes 1e-8 .. 1e3"""
+    rng = np.random.default_rng(seed)
+    return rng.choice([-1.0, 1.0], (rows, F)) * 10.0 ** rng.uniform(-8.0, 3.0, (rows, F))
+
+
+COSINE_F = (1, 63, 64, 65, 128, 129)
+COSINE_SHAPES = ((1, 1), (3, 7), (4, 8), (5, 9), (9, 17))
+
+
+def cosine_pairs(P, rows_a, rows_b):
+    """P listed pairs with a repeat where P allows one"""
+    rng = np.random.default_rng(P)
+    pairs = np.stack([rng.integers(0, rows_a, P), rng.integers(0, rows_b, P)], 1)
+    if P > 2:
+        pairs[P - 1] = pairs[0]
+    return pairs.astype(np.int32)
 
 
 # ---- the host statement -------------------------------------------------------------------------------------------------------------
@@ -285,3 +356,44 @@ def e_host(name):
     """E_host of one configuration: the host statement against the truth, the largest over A = 1, 2, 3"""
     G = golden()
     return max(descriptor_error(host_on_golden(name, A)[0], G[f"{name}_A{A}_desc"]) for A in TYPES)
+
+
+# ---- the limits: their truth and the host statement on it -----------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def limits_golden():
+    return np.load(LIMITS_GOLDEN)
+
+
+@functools.lru_cache(maxsize=None)
+def limit_tables(name):
+    return tables_of(limits_golden(), name)
+
+
+@functools.lru_cache(maxsize=None)
+def limit_fixture(name):
+    """the fixture graphs the truth of one limit configuration covers, at its A, checked against what the truth was computed on
+    -> (pos, types, sizes)"""
+    G, cfg = limits_golden(), LIMIT_CONFIGS[name]
+    pos, types, sizes = fixture(cfg["A"], cfg["graphs"])
+    assert np.array_equal(pos, G[f"{name}_pos"]) and np.array_equal(types, G[f"{name}_types"]), "the fixture moved"
+    assert np.array_equal(G[f"{name}_centres"], first_centres(sizes))
+    assert gap_ok(pos, sizes, neighbour_cut(cfg)), "ambiguous input: a distance on the neighbour cut"
+    return pos, types, sizes
+
+
+@functools.lru_cache(maxsize=None)
+def host_on_limit(name):
+    """the host statement on EVERY atom of limit_fixture(name) -> (desc, coeff)"""
+    from diffusion_model_amd import _lib
+    cfg = LIMIT_CONFIGS[name]
+    pos, types, sizes = limit_fixture(name)
+    rc, desc, coeff = host_descriptors(_lib.lib(), pos, types, sizes, cfg["A"], np.arange(len(types)), cfg, limit_tables(name)[1])
+    assert rc == 0, _lib.lib().egnn_last_error()
+    return desc, coeff
+
+
+@functools.lru_cache(maxsize=None)
+def e_host_limit(name):
+    """E_host of one limit configuration: the host statement against the truth on the golden's centres"""
+    G = limits_golden()
+    return descriptor_error(host_on_limit(name)[0][G[f"{name}_centres"]], G[f"{name}_desc"])

@@ -3,8 +3,8 @@
 // cosine matrix or a list of nearest spectra.  The tables here are float64 stand-ins (K, gamma, the norms and the weights from their
 // formulas, beta = identity): the program checks memory and argument handling, the accuracy is test_soap_host.py's business.
 // Cases: a seeded batch of clouds (1, 2, 5, 65 and 130 atoms, three types) at the small configuration, the same at the limits
-// (A = 4, n_max = 16, l_max = 10), cosines with and without a pair list, the matrix, nearest spectra with groups and with k above
-// the candidates, and every bad-argument case.
+// (A = 4, n_max = 16, l_max = 10) and at the smallest basis (n_max = 1, l_max = 0), cosines with and without a pair list, the matrix,
+// nearest spectra with groups, with k above the candidates and with exactly equal distances, and every bad-argument case.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -120,6 +120,12 @@ int main() {
     const std::vector<int32_t> first = {0, 1, 3, 8, 73};
     const std::vector<double> big = descriptors(b4, 4, 8.0, 16, 10, first, true);
     CHECK((int)(big.size() / first.size()) == 4 * 136 * 11 + 6 * 256 * 11, "F at the limits: %zu", big.size() / first.size());
+    // the other end: one radial function, l = 0 only (a 1 x 1 beta, one harmonic, F = 4 + 6)
+    const std::vector<double> tiny = descriptors(b4, 4, 4.0, 1, 0, first, true);
+    CHECK(tiny.size() == first.size() * 10, "F of the smallest basis: %zu", tiny.size() / first.size());
+    int nonzero = 0;
+    for (int f = 0; f < 10; ++f) nonzero += tiny[f] != 0.0;
+    CHECK(nonzero == 1, "lone atom, smallest basis: %d non-zero entries", nonzero);
   }
   {   // cosines: the diagonal, a pair list, the matrix
     const int n_a = 70, n_b = 33;
@@ -170,6 +176,24 @@ int main() {
       rc = egnn_soap_host(0, 0, 0, nullptr, nullptr, nullptr, 0, 0, 0.0, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0,
                           nullptr, nullptr, nullptr, 1, 3, S, 8, t.data(), r.data(), nullptr, nullptr, idx.data(), mse.data());
       CHECK(rc == 0 && idx[2] >= 0 && idx[3] == -1 && isinf(mse[7]), "k above the candidates: %d", idx[3]);
+      // exact ties go to the lower index: references 3, 17, 18 and 40 are one row next to target 0, references 5 and 6 one next to
+      // target 1
+      for (int s = 0; s < S; ++s) {
+        for (int q : {3, 17, 18, 40}) r[(size_t)q * S + s] = t[s] + 0.015625f;
+        for (int q : {5, 6}) r[(size_t)q * S + s] = t[(size_t)S + s] - 0.03125f;
+      }
+      std::vector<int32_t> tie_idx((size_t)T * 8, -7);
+      std::vector<double> tie_mse((size_t)T * 8, -7.0);
+      rc = egnn_soap_host(0, 0, 0, nullptr, nullptr, nullptr, 0, 0, 0.0, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0,
+                          nullptr, nullptr, nullptr, T, R, S, 8, t.data(), r.data(), nullptr, nullptr, tie_idx.data(), tie_mse.data());
+      CHECK(rc == 0, "rc %d: %s", rc, egnn_last_error());
+      CHECK(tie_idx[0] == 3 && tie_idx[1] == 17 && tie_idx[2] == 18 && tie_idx[3] == 40 && tie_mse[0] == tie_mse[3], "a four-fold tie: %d %d %d %d",
+            tie_idx[0], tie_idx[1], tie_idx[2], tie_idx[3]);
+      CHECK(tie_idx[8] == 5 && tie_idx[9] == 6 && tie_mse[8] == tie_mse[9], "a tie of two: %d %d", tie_idx[8], tie_idx[9]);
+      for (int q = 0; q < T; ++q)
+        for (int j = 1; j < 8; ++j)
+          CHECK(tie_mse[(size_t)q * 8 + j] > tie_mse[(size_t)q * 8 + j - 1] || tie_idx[(size_t)q * 8 + j] > tie_idx[(size_t)q * 8 + j - 1],
+                "target %d: equal distances out of index order at place %d", q, j);
     }
   }
   {   // bad arguments

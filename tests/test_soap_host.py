@@ -8,6 +8,9 @@ csrc/eval/soap_math.h), without a GPU:
     proper and improper; a translation of positions on a 2^-10 grid) and neighbour permutation within 8 E_host, and exact
     properties: species relabelling, the cut, centre lists, the solid harmonics against scipy.special.sph_harm_y;
   * cosines and nearest spectra against the restatement (tests/_soap_util.py), bitwise where the order is fixed;
+  * the basis limits (A = 4, n_max = 16, l_max = 10) and the degenerate bases (l_max = 0, n_max = 1, an odd one) against
+    tests/golden/soap_limits_golden.npz; exact ties of the nearest spectra (the lower index first), non-finite rows, and the
+    cosines at F, row and pair counts around a wavefront, the 4 x 8 tile and the 4 wavefronts of a workgroup;
   * bad arguments return EGNN_EINVAL, from the host statement and -- before anything is launched -- from the device entries;
   * a stand-alone program runs egnn_soap_host under the address and undefined-behaviour sanitizers.
 
@@ -36,19 +39,25 @@ def _ulps(a, b):
     return np.abs(a - b) / np.spacing(np.maximum(np.abs(a), np.abs(b)))
 
 
-@pytest.mark.parametrize("name", list(SU.CONFIGS))
+def _config(name):
+    """-> (the four basis parameters, (parts, flat) of the golden that holds the configuration)"""
+    if name in SU.CONFIGS:
+        return SU.CONFIGS[name], _tables(name)
+    return SU.basis_of(SU.LIMIT_CONFIGS[name]), SU.limit_tables(name)
+
+
+@pytest.mark.parametrize("name", list(SU.CONFIGS) + list(SU.LIMIT_CONFIGS))
 def test_basis_tables_equal_the_golden_within_one_ulp(name):
-    cfg = SU.CONFIGS[name]
+    cfg, (parts, flat) = _config(name)
     basis = SoapBasis(**cfg)
     assert SoapBasis(**cfg) is basis, "the basis is cached per process"
-    parts, flat = _tables(name)
     assert basis.tables.shape == flat.shape == (_lib.lib().egnn_soap_table_doubles(cfg["n_max"], cfg["l_max"]),)
     for got, want in zip((basis.K, basis.gamma, basis.beta, basis.norm, basis.weight), parts):
         assert got.shape == want.shape and float(_ulps(got, want).max()) <= 1.0
     assert float(_ulps(basis.tables, flat).max()) <= 1.0
     assert basis.neighbour_cut == pytest.approx(SU.neighbour_cut(cfg), rel=1e-15)
     # the overlap matrix is so ill-conditioned that beta has entries above 1e6 which cancel to O(1) coefficients
-    if name == "default":
+    if name in ("default", "limit"):
         assert np.abs(basis.beta).max() > 1e6
 
 
@@ -85,6 +94,36 @@ def test_host_statement_against_the_truth(name):
     pos, types, sizes = SU.fixture(2, SU.GOLDEN_GRAPHS[name])
     d2, c2 = SU.descriptors(pos, types, sizes, 2, G[f"{name}_A2_centres"], _tables(name)[0], SU.neighbour_cut(SU.CONFIGS[name]))
     assert SU.descriptor_error(d2, G[f"{name}_A2_desc"]) <= 8 * E and SU.descriptor_error(d2, _host(name, 2)[0]) <= 8 * E
+
+
+@pytest.mark.parametrize("name", list(SU.LIMIT_CONFIGS))
+def test_host_statement_against_the_truth_at_the_limits(name):
+    """the basis limits (A = 4, n_max = 16, l_max = 10) and the degenerate bases (l_max = 0, n_max = 1, an odd mid-size one): atom 0
+    of the fixture graphs against tests/golden/soap_limits_golden.npz"""
+    L, LG, cfg = _lib.lib(), SU.limits_golden(), SU.LIMIT_CONFIGS[name]
+    A, n_max, l_max = cfg["A"], cfg["n_max"], cfg["l_max"]
+    pos, types, sizes = SU.limit_fixture(name)
+    cs, truth = LG[f"{name}_centres"], LG[f"{name}_desc"]
+    desc, coeff = SU.host_on_limit(name)
+    E = SU.e_host_limit(name)
+    F = SU.features(A, n_max, l_max)
+    assert L.egnn_soap_features(A, n_max, l_max) == F == SU.feature_index(A, n_max, l_max).shape[1] == truth.shape[1]
+    assert L.egnn_soap_table_doubles(n_max, l_max) == SU.limit_tables(name)[1].size == 2 * n_max * (l_max + 1) + (l_max + 1) * n_max ** 2 + (l_max + 1) ** 2 + l_max + 1
+    rest, rest_coeff = SU.descriptors(pos, types, sizes, A, cs, SU.limit_tables(name)[0], SU.neighbour_cut(cfg))
+    E_rest = SU.descriptor_error(rest, truth)
+    print(f"E_host[{name}] = {E:.3e}, the float64 restatement {E_rest:.3e}")
+    assert desc.shape == (len(types), F) and E <= CAP and E_rest <= CAP
+    if name == "limit":
+        assert coeff[cs].shape == LG["limit_coeff"].shape and SU.descriptor_error(coeff[cs], LG["limit_coeff"]) <= CAP
+        assert SU.descriptor_error(rest_coeff, LG["limit_coeff"]) <= CAP
+    # a lone atom (graph 0): the l = 0 entries of its own species' block and nothing else; every species present in the 17-atom graph
+    assert sizes[0] == 1 and np.count_nonzero(desc[0]) == n_max * (n_max + 1) // 2
+    z1, z2, _, _, ll = SU.feature_index(A, n_max, l_max)
+    assert np.array_equal(desc[0] != 0.0, (z1 == types[0]) & (z2 == types[0]) & (ll == 0))
+    assert set(types[cs[3]:cs[3] + 17].tolist()) == set(range(A))
+    # the list of centres, and no coefficient output: the same rows, bitwise
+    rc, listed, none = SU.host_descriptors(L, pos, types, sizes, A, cs[::-1], cfg, SU.limit_tables(name)[1], coeff=False)
+    assert rc == 0 and none is None and np.array_equal(listed, desc[cs[::-1]])
 
 
 def _describe(name, pos, types, sizes, A, centres, cut=None, flat=None):
@@ -237,6 +276,98 @@ def test_nearest_spectra_against_the_restatement(S):
     assert rc == 0 and gi[0, first + 1] == 4 and gm[0, first] == gm[0, first + 1] and gi[0, 5:].tolist() == [-1] * 3 and np.isinf(gm[0, 5:]).all()
     rc, gi, gm = SU.host_nearest(L, t, r, 3, np.zeros(5, np.int32), np.zeros(70, np.int32))
     assert rc == 0 and (gi == -1).all() and np.isinf(gm).all()
+
+
+def test_nearest_spectra_with_exact_ties_go_to_the_lower_index():
+    """the one rule without a numerical symptom: rows 3, 17, 18, 40 of the references are one row, rows 5, 6 another"""
+    L = _lib.lib()
+    t, r = SU.tie_spectra()
+    tg, rg = np.array([0, 1, -1, 2, 70], np.int32), (np.arange(70) % 3).astype(np.int32)   # rows 3, 18 in group 0: excluded for target 0
+    straddles = []
+    for groups in ((None, None), (tg, rg)):
+        for k in range(1, 9):
+            idx, mse, m = SU.nearest(t, r, k, *groups)
+            assert SU.mse_gap_ok_with_ties(m) and not SU.mse_gap_ok(m)
+            for rows in (SU.TIE_ROWS, SU.TIE_PAIR):                                         # the tie is really there, bitwise
+                assert all(len({m[q, j].tobytes() for j in rows if np.isfinite(m[q, j])}) <= 1 for q in range(5))
+            rc, gi, gm = SU.host_nearest(L, t, r, k, *groups)
+            assert rc == 0 and np.array_equal(gi, idx) and np.array_equal(gm.view(np.int64), mse.view(np.int64))
+            order = np.argsort(m, axis=1, kind="stable")
+            if k < 70:
+                straddles += [(groups[0] is not None, k, q) for q in range(5) if m[q, order[q, k - 1]] == m[q, order[q, k]] and np.isfinite(m[q, order[q, k]])]
+    assert straddles, "no tie straddles a k-th place"
+    idx, _, m = SU.nearest(t, r, 8)
+    assert m[0, 17].tobytes() == m[0, 18].tobytes() and idx[0, :4].tolist() == [3, 17, 18, 40] and idx[1, :2].tolist() == [5, 6]
+    assert SU.nearest(t, r, 8, tg, rg)[0][0, :2].tolist() == [17, 40]                       # 3 and 18 share target 0's group
+
+
+def test_nearest_spectra_at_the_wavefront_and_workgroup_edges_and_non_finite_rows():
+    L = _lib.lib()
+    for S in (1, 63, 64, 65):
+        for T in (1, 3, 4, 5):
+            for R in (1, 2, 9):
+                t, r = SU.spectra(1000 * S + 10 * T + R, T, R, S)
+                idx, mse, m = SU.nearest(t, r, 8)
+                assert SU.mse_gap_ok(m)
+                rc, gi, gm = SU.host_nearest(L, t, r, 8)
+                assert rc == 0 and np.array_equal(gi, idx) and np.array_equal(gm.view(np.int64), mse.view(np.int64))
+                assert (gi[:, min(R, 8):] == -1).all() and (gi[:, :min(R, 8)] >= 0).all()
+    t, r = SU.nonfinite_spectra()
+    for k in (1, 8):
+        with np.errstate(invalid="ignore"):
+            idx, mse, m = SU.nearest(t, r, k)
+        assert SU.mse_gap_ok(m)
+        rc, gi, gm = SU.host_nearest(L, t, r, k)
+        assert rc == 0 and np.array_equal(gi, idx) and np.array_equal(gm.view(np.int64), mse.view(np.int64))
+        assert not np.isin(gi, (2, 7)).any() and (gi[1] == -1).all() and np.isposinf(gm[1]).all()
+        assert (gi[[0, 2, 3]] >= 0).all() and np.isfinite(gm[[0, 2, 3]]).all()
+
+
+@pytest.mark.parametrize("F", SU.COSINE_F)
+def test_cosines_at_the_row_pair_and_column_edges(F):
+    """F around the 64 lanes of a row sum, row counts around the 4 x 8 tile of the matrix, pair counts around the 4 wavefronts of a
+    workgroup; entries of magnitude 1e-8 .. 1e3"""
+    L = _lib.lib()
+    eps = np.finfo(float).eps
+    for rows_a, rows_b in SU.COSINE_SHAPES:
+        a, b = SU.cosine_rows(F, rows_a, F), SU.cosine_rows(F + 1000, rows_b, F)
+        want = SU.cosine_matrix(a, b)
+        rc, _, gram = SU.host_cosines(L, a, b, gram=True)
+        assert rc == 0 and float(np.abs(gram - want).max()) <= 4 * eps
+        for P in (1, 3, 4, 5):
+            pairs = SU.cosine_pairs(P, rows_a, rows_b)
+            rc, cos, _ = SU.host_cosines(L, a, b, pairs=pairs)
+            assert rc == 0 and float(np.abs(cos - SU.cosine(a[pairs[:, 0]], b[pairs[:, 1]])).max()) <= 4 * eps
+            assert np.array_equal(cos.view(np.int64), gram[pairs[:, 0], pairs[:, 1]].view(np.int64))       # one order: bitwise
+        if rows_a >= 3:
+            a[1] = 0.0                                                                     # a zero row: NaN in its row, nowhere else
+            rc, _, gram = SU.host_cosines(L, a, b, gram=True)
+            with np.errstate(invalid="ignore"):
+                want = SU.cosine_matrix(a, b)
+            assert rc == 0 and np.array_equal(np.isnan(gram), np.isnan(want)) and np.isnan(gram[1]).all() and np.isnan(gram).sum() == rows_b
+            rc, _, gram = SU.host_cosines(L, b, a, gram=True)                              # ... and in its column
+            assert rc == 0 and np.isnan(gram[:, 1]).all() and np.isnan(gram).sum() == rows_b
+
+
+def test_row_sums_bitwise_through_unit_rows():
+    """cosine(a, e) with e = (1, 0, .., 0) scaled by 4 has norm_b exactly 16 and dot exactly 4 a_0, so cos = 4 a_0 / (sqrt(sum a^2) * 4):
+    the host statement's squared norm is the restatement's bitwise exactly when these quotients are"""
+    L = _lib.lib()
+    for F in SU.COSINE_F:
+        a = SU.cosine_rows(7 * F, 9, F)
+        e = np.zeros((1, F))
+        e[0, 0] = 4.0
+        rc, _, gram = SU.host_cosines(L, a, e, gram=True)
+        want = (4.0 * a[:, 0]) / (np.sqrt(SU.row_sum(a * a)) * 4.0)
+        assert rc == 0 and np.array_equal(gram[:, 0].view(np.int64), want.view(np.int64))
+
+
+def test_empty_graphs_first_in_the_middle_and_last():
+    pos, types, sizes = SU.fixture(3, 4)
+    want, _ = _describe("small", pos, types, sizes, 3, np.arange(len(types)))
+    holes = [0, 1, 2, 0, 0, 5, 17, 0]
+    got, _ = _describe("small", pos, types, holes, 3, np.arange(len(types)))
+    assert np.array_equal(got, want)
 
 
 # ---- errors ---------------------------------------------------------------------------------------------------------------------------------

@@ -5,6 +5,8 @@ bars: E = max |p - p_truth| / max |p_truth| per configuration, the largest over 
            float64 ones: those land between 4e-5 and 2e-2);
   device   egnn_soap_descriptor on the same centres, where a GPU is visible: its bar is 8 E_host.  Without a GPU the device
            entries of an existing record are kept as they are.
+  limits   the same two numbers for the basis limits and the degenerate bases (tests/_soap_util.py: LIMIT_CONFIGS, each at its
+           own number of types) against tests/golden/soap_limits_golden.npz; their device bar is 8 max(E_host, 2^-52).
 
   python tools/soap_accuracy.py                   # -> profiles/soap_accuracy.json
 """
@@ -49,6 +51,30 @@ def main():
         if gpu:
             rec.update(device_error_by_types=device, device_error=max(device), device_coefficient_error_A2=coeff_device,
                        gcn_arch=torch.cuda.get_device_properties(0).gcnArchName)
+        else:
+            rec.update({k: v for k, v in old.get("configurations", {}).get(name, {}).items() if k.startswith("device_e") or k.startswith("device_c") or k == "gcn_arch"})
+        assert rec["host_error"] <= CAP
+        record["configurations"][name] = rec
+        print(name, json.dumps(rec))
+    # the basis limits and the degenerate bases, each at its own number of types: atom 0 of the listed graphs
+    LG = SU.limits_golden()
+    record["limits_truth"] = "tests/golden/soap_limits_golden.npz (mpmath, 60 digits)"
+    for name, cfg in SU.LIMIT_CONFIGS.items():
+        A, cs, truth = cfg["A"], LG[f"{name}_centres"], LG[f"{name}_desc"]
+        pos, types, sizes = SU.limit_fixture(name)
+        rec = dict(SU.basis_of(cfg), types=A, features=int(truth.shape[1]), graphs=sizes, centres="atom 0 of every graph")
+        host = SU.e_host_limit(name)
+        rec.update(host_error=host, device_bar=8 * max(host, 2.0 ** -52))
+        if name == "limit":
+            rec["host_coefficient_error"] = SU.descriptor_error(SU.host_on_limit(name)[1][cs], LG["limit_coeff"])
+        if gpu:
+            got = soap.soap_descriptors(torch.from_numpy(pos).cuda(), torch.eye(A, dtype=torch.int64)[torch.from_numpy(types).long()].cuda(), sizes,
+                                        "all", soap.SoapBasis(**SU.basis_of(cfg)), return_coefficients=True)
+            rec.update(device_error=SU.descriptor_error(got[0].cpu().numpy()[cs], truth),
+                       device_error_against_host_every_atom=SU.descriptor_error(got[0].cpu().numpy(), SU.host_on_limit(name)[0]),
+                       gcn_arch=torch.cuda.get_device_properties(0).gcnArchName)
+            if name == "limit":
+                rec["device_coefficient_error"] = SU.descriptor_error(got[1].cpu().numpy()[cs], LG["limit_coeff"])
         else:
             rec.update({k: v for k, v in old.get("configurations", {}).get(name, {}).items() if k.startswith("device_e") or k.startswith("device_c") or k == "gcn_arch"})
         assert rec["host_error"] <= CAP

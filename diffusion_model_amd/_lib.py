@@ -25,6 +25,8 @@ SQ_MAX_TYPES, SQ_MAX_Q, SQ_MAX_BINS, SQ_MAX_ATOMS, SQ_MAX_VECTORS = 4, 4096, 409
 SQ_ROW_BLOCK, SQ_CHUNK, SQ_VECTOR_BLOCK = 64, 256, 256   # the tiles of egnn_sq_debye and egnn_sq_cell_rho
 SQ_WINDOWS = {None: 0, "none": 0, "lorch": 1}
 CELL_CENTRE_BLOCK = 64    # kCellCentreBlock: the centres of one tile of egnn_cell_bonds_count / _fill
+# kCellStat* of csrc/cells/cell_stats_math.h: the tiles of egnn_cell_pair_counts / egnn_cell_bond_stats and their limits
+CELL_STAT_CENTRE_BLOCK, CELL_STAT_CHUNK, CELL_STAT_BOND_CENTRES, CELL_STAT_MAX_IMAGES, CELL_STAT_MAX_HIST = 64, 1024, 8, 16, 16384
 PREALIGN_MIN_ATOMS = 5    # kPrealignMinAtoms of csrc/eval/assign_host.h: atom 0 and its four nearest neighbours
 
 
@@ -188,6 +190,9 @@ SIGNATURES = {
     "egnn_cell_env_count": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "egnn_cell_env_fill": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i] + [_vp] * 4),
     "egnn_cell_env_host": (_i, [_i, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, _vp, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64] + [_vp] * 4),
+    "egnn_cell_pair_counts": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, _i, _vp]),
+    "egnn_cell_bond_stats": (_i, [_vp, _i, _i, _i] + [_vp] * 7 + [_i, _vp, _vp, C.c_double, _i, _i, _i, _vp, _i] + [_vp] * 6),
+    "egnn_cell_stats_host": (_i, [_i, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, C.c_double, C.c_double, _i, _i, _i] + [_vp] * 6),
     "egnn_sq_debye": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _vp, _i, _vp, _vp, _vp]),
     "egnn_sq_cell_plan": (_i, [_i, _vp, C.c_double, _vp, _vp]),
     "egnn_sq_cell_count": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),

@@ -10,7 +10,10 @@ of a batch of cells (or every atom of one type, or any list of atoms), by ``csrc
   (``.batch()``), the samplers and ``stats.compare_structures`` (``.to_data_list()``).
 
 ``structure_factor`` (``csrc/eval/sq.hip``) is the reciprocal-space statistic of whole cells: rho_a on the reciprocal lattice and
-its shell averages, finished to partial and total S(q); no file of the reference computes it.
+its shell averages, finished to partial and total S(q); no file of the reference computes it.  ``pair_counts``, ``partial_rdf``,
+``bond_statistics``, ``structure_profile`` and ``compare_structures`` (``csrc/cells/cell_stats.hip``) are its real-space
+counterpart: g_ab(r) and the running coordination numbers over every image, CN histograms, bond angles and Q^n speciation of whole
+cells; the reference has them about atom 0 of one cluster only.
 
 The definitions (``csrc/cells/cell_math.h``) are those of the INFINITE lattice: a site is (atom, integer shift), a bond joins
 sites closer than the cutoff, an environment is what ``shells`` bonds reach.  Wherever the reference's search uses no bond that
@@ -451,3 +454,233 @@ def structure_factor(cells, q_max: float = 15.0, dq: float = 0.05, weights=None,
     if vectors:
         out.hkl, out.k, out.bin, out.rho, out.vec_ptr = hkl, kabs, bins, torch.view_as_complex(rho), vec_ptr64
     return out
+
+
+# ---- real-space statistics of periodic cells (csrc/cells/cell_stats.hip) -------------------------------------------------------
+_PAIR_TILES_WANTED = 512   # two workgroups per CU: below that the values of the first shift component are dealt over several tiles
+
+
+def _pair_tiles(sizes, boxes) -> np.ndarray:
+    """the work list of egnn_cell_pair_counts (include/egnn_amd.h): {cell, first centre, first neighbour, piece, pieces} for every
+    (64-centre block, 1024-atom chunk) of every cell, times ``pieces`` pieces of the 2 S_0 + 1 values of the first shift component
+    (``boxes`` int [C]: S_0 per cell).  A batch that fills the device as it is (256 cells of 24 atoms: 256 blocks) is cut in two at
+    the most; one 3,000-atom cell (141 blocks) in three, 423 tiles.  No tile is empty: a cell contributes its own blocks only, and
+    never more pieces than it has shift values."""
+    sz = np.asarray(sizes, dtype=np.int64)
+    n_cb, n_jb = -(-sz // _lib.CELL_STAT_CENTRE_BLOCK), -(-sz // _lib.CELL_STAT_CHUNK)
+    blocks = n_cb * n_jb
+    want = -(-_PAIR_TILES_WANTED // max(int(blocks.sum()), 1))
+    pieces = np.minimum(2 * np.asarray(boxes, dtype=np.int64) + 1, want)
+    ci, t = block_index(blocks * pieces)
+    p, b = t % pieces[ci], t // pieces[ci]
+    tiles = np.stack([ci, (b // n_jb[ci]) * _lib.CELL_STAT_CENTRE_BLOCK, (b % n_jb[ci]) * _lib.CELL_STAT_CHUNK, p, pieces[ci]], 1)
+    return tiles.astype(np.int32).reshape(-1, 5)
+
+
+def _stat_bond_tiles(sizes) -> np.ndarray:
+    """the work list of egnn_cell_bond_stats: {cell, first centre} for every block of 8 centres"""
+    sz = np.asarray(sizes, dtype=np.int64)
+    ci, t = block_index(-(-sz // _lib.CELL_STAT_BOND_CENTRES))
+    return np.stack([ci, t * _lib.CELL_STAT_BOND_CENTRES], 1).astype(np.int32).reshape(-1, 2)
+
+
+def _pair_nbins(R: float, dR: float) -> int:
+    R, dR = float(R), float(dR)
+    if not (dR > 0 and math.isfinite(dR) and R > 0 and math.isfinite(R)):
+        raise ValueError("R and dR must be positive and finite")
+    return int(math.floor(R / dR + 0.5))
+
+
+def _image_boxes(cb: _CellBatch, dR: float, nbins: int) -> np.ndarray:
+    """S_0 = ceil(nbins dR / w_0) per cell, for the work list only (the library takes the box from its own arithmetic and refuses
+    a cell it finds too wide or singular): clipped to [0, 16]"""
+    L = cb.lattice_h.numpy().reshape(-1, 3, 3)
+    bc = np.cross(L[:, 1], L[:, 2])
+    det = np.abs(np.einsum("ck,ck->c", L[:, 0], bc))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s = np.ceil(nbins * dR * np.linalg.norm(bc, axis=1) / det)
+    return np.clip(np.nan_to_num(s, nan=0.0, posinf=_lib.CELL_STAT_MAX_IMAGES), 0, _lib.CELL_STAT_MAX_IMAGES).astype(np.int64)
+
+
+def _pair_counts(cb: _CellBatch, dR: float, nbins: int, tiles: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> int64 [C, A, A, nbins]: the raw output of egnn_cell_pair_counts; ``tiles``: the work list where the caller has it on the
+    device already"""
+    if tiles is None:
+        tiles = torch.from_numpy(_pair_tiles(cb.sizes, _image_boxes(cb, dR, nbins))).to(cb.dev)
+    counts = torch.empty(cb.C, cb.A, cb.A, max(nbins, 1), dtype=torch.int64, device=cb.dev)
+    _lib.check(_lib.lib().egnn_cell_pair_counts(_lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h),
+                                                _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice), _lib.ptr(cb.frac) if cb.N else None,
+                                                _lib.ptr(cb.types) if cb.N else None, float(dR), int(nbins),
+                                                _lib.ptr(tiles) if len(tiles) else None, len(tiles), _lib.ptr(counts)))
+    return counts
+
+
+def _bond_stats(cb: _CellBatch, bonds: BondList, dtheta: float, max_cn: int, former: int, bridge: int, tiles: Optional[torch.Tensor] = None):
+    """-> (coordination int32 [N, A], cn, angles int64, qn int32 [N], qn_hist int64, overflow int32 [C]): the raw outputs of
+    egnn_cell_bond_stats; ``tiles``: the work list where the caller has it on the device already"""
+    dtheta, max_cn = float(dtheta), int(max_cn)
+    nth = int(np.floor(180.0 / dtheta + 0.5)) + 1 if dtheta > 0 else 1
+    A, C, N, E, ncn = cb.A, cb.C, cb.N, bonds.num_bonds, max(max_cn, 0) + 1
+    if tiles is None:
+        tiles = torch.from_numpy(_stat_bond_tiles(cb.sizes)).to(cb.dev)
+    coordination = torch.empty(max(N, 1), A, dtype=torch.int32, device=cb.dev)[:N]
+    qn = torch.empty(max(N, 1), dtype=torch.int32, device=cb.dev)[:N]
+    cn = torch.empty(C, A, A, ncn, dtype=torch.int64, device=cb.dev)
+    ang = torch.empty(C, A, A * (A + 1) // 2, max(nth, 1), dtype=torch.int64, device=cb.dev)
+    qn_hist = torch.empty(C, ncn, dtype=torch.int64, device=cb.dev)
+    over = torch.empty(C, dtype=torch.int32, device=cb.dev)
+    _lib.check(_lib.lib().egnn_cell_bond_stats(
+        _lib.stream_ptr(), C, N, A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice),
+        _lib.ptr(cb.frac) if N else None, _lib.ptr(cb.types) if N else None, _lib.ptr(bonds.row_ptr), E, _lib.ptr(bonds.atom) if E else None,
+        _lib.ptr(bonds.shift_code) if E else None, dtheta, max_cn, int(former), int(bridge), _lib.ptr(tiles) if len(tiles) else None,
+        len(tiles), _lib.ptr(coordination) if N else None, _lib.ptr(cn), _lib.ptr(ang), _lib.ptr(qn) if N else None, _lib.ptr(qn_hist),
+        _lib.ptr(over)))
+    return coordination, cn, ang, qn, qn_hist, over
+
+
+def _raise_on_cell_overflow(over: torch.Tensor):
+    bad = torch.nonzero(over > 0)
+    if bad.numel():
+        c = int(bad[0])
+        raise RuntimeError(f"cell {c}: {int(over[c])} centre(s) with more than 64 bonds; their angles are not taken (lower the cutoff)")
+
+
+def _smooth(g: torch.Tensor, sigma: float) -> torch.Tensor:
+    """the filter of struct_smooth_* (csrc/eval/structure_math.h) along the last axis in fp64: reflect boundary, truncation at
+    4 sigma, the taps added in ascending order"""
+    nbins = g.shape[-1]
+    lw = int(4.0 * sigma + 0.5)
+    taps = torch.arange(-lw, lw + 1, dtype=torch.float64)
+    w = torch.exp(-0.5 * taps * taps / (sigma * sigma)).tolist()
+    k = torch.arange(nbins, device=g.device)
+    acc, wsum = torch.zeros_like(g), 0.0
+    for t, wt in zip(range(-lw, lw + 1), w):
+        idx = torch.remainder(k + t, 2 * nbins)
+        idx = torch.where(idx >= nbins, 2 * nbins - 1 - idx, idx)
+        acc = acc + g[..., idx] * wt
+        wsum = wsum + wt
+    return acc / wsum
+
+
+def _n_type(cb: _CellBatch) -> torch.Tensor:
+    return torch.stack([torch.bincount(c.types.long(), minlength=cb.A)[:cb.A] for c in cb.cells]).to(cb.dev)
+
+
+def _rdf_weights(cb: _CellBatch, weights) -> torch.Tensor:
+    """float64 [A] on the device; a bad shape fails before the launch"""
+    from .stats import NEUTRON_LENGTHS
+    if weights is None:
+        weights = NEUTRON_LENGTHS if cb.A == 2 else (1.0,) * cb.A
+    wt = torch.as_tensor(weights, dtype=torch.float64).detach().cpu().reshape(-1)
+    if wt.numel() != cb.A:
+        raise ValueError(f"weights must hold one value per atom type ({cb.A})")
+    return wt.to(cb.dev)
+
+
+def _rdf_finish(cb: _CellBatch, counts: torch.Tensor, dR: float, sigma: float, wt: torch.Tensor):
+    from types import SimpleNamespace
+    nbins = int(counts.shape[-1])
+    n_type = _n_type(cb)
+    nt = n_type.to(torch.float64)
+    Lh = cb.lattice_h.view(-1, 3, 3)
+    volume = (Lh[:, 0] * torch.linalg.cross(Lh[:, 1], Lh[:, 2])).sum(1).abs().to(cb.dev)
+    k = torch.arange(nbins, dtype=torch.float64, device=cb.dev)
+    shell = (4.0 * math.pi / 3.0) * ((k + 1.0) ** 3 - k ** 3) * dR ** 3
+    denom = nt[:, :, None, None] * nt[:, None, :, None] * shell
+    c64 = counts.to(torch.float64)
+    g = torch.where(denom > 0, volume[:, None, None, None] * c64 / denom.clamp(min=1e-300), torch.zeros_like(c64))
+    n = torch.where(nt[:, :, None, None] > 0, torch.cumsum(c64, -1) / nt[:, :, None, None].clamp(min=1.0), torch.zeros_like(c64))
+    if sigma > 0:
+        g = _smooth(g, float(sigma))
+    conc = nt / nt.sum(1, keepdim=True).clamp(min=1.0)
+    cw = conc * wt
+    total = (cw[:, :, None, None] * cw[:, None, :, None] * g).sum((1, 2)) / (cw.sum(1) ** 2)[:, None]
+    return SimpleNamespace(r=(k + 0.5) * dR, counts=counts, g=g, n=n, total=total, n_type=n_type, volume=volume, sizes=list(cb.sizes))
+
+
+def pair_counts(cells: Union[PeriodicCell, Sequence[PeriodicCell]], R: float = 10.0, dR: float = 0.01, device=None) -> torch.Tensor:
+    """Ordered-pair counts by type over every centre AND every image of the infinite lattice: int64 [C, A, A, nbins],
+    c[cell, a, b, k] = pairs (i, (j, s)), s in Z^3, (j, s) != (i, 0), with type(i) = a, type(j) = b and
+    floor(|(w_j - w_i + s) L| / dR) = k in fp64 (csrc/cells/cell_stats_math.h).  An atom pairs with its own images, and
+    c[a, b] == c[b, a] bitwise.  nbins = floor(R / dR + 0.5) and bin k is [k dR, (k + 1) dR): NOT the reference's open bins
+    (dR + k dR, dR + (k + 1) dR) that ``stats.rdf`` and ``stats.pair_counts`` keep for clusters.  An extension: the reference counts
+    about atom 0 of one cluster (evaluate_RDF.py:39-60).  Refused (``EgnnError``, naming the cell): a singular lattice, a cell that
+    needs more than 16 images along an axis to reach R, A A nbins > 16384."""
+    cb = _CellBatch(_as_cells(cells), device)
+    return _pair_counts(cb, float(dR), _pair_nbins(R, dR))
+
+
+def partial_rdf(cells: Union[PeriodicCell, Sequence[PeriodicCell]], R: float = 10.0, dR: float = 0.01, sigma: float = 0.0, weights=None,
+                device=None):
+    """Partial pair distributions of periodic cells, the real-space counterpart of ``structure_factor``.  -> a namespace with
+    r float64 [nbins] (bin centres, the bins of ``pair_counts``, not the reference's); counts int64 [C, A, A, nbins];
+    g float64 [C, A, A, nbins] = V c_ab(k) / (N_a N_b (4 pi / 3) ((k + 1)^3 - k^3) dR^3) with V = |det L| -- the TRUE density of the
+    cell, not the reference's sphere n / (4/3 pi R^3) -- so g_ab -> 1 at large r; an absent type gives zeros; n float64, the running
+    coordination cumsum_k c_ab / N_a; total float64 [C, nbins] = sum_ab c_a c_b w_a w_b g_ab / (sum_a c_a w_a)^2 with the
+    concentrations c_a = N_a / N and ``weights`` [A] (default ``stats.NEUTRON_LENGTHS`` for A = 2, ones otherwise); n_type int64
+    [C, A], volume float64 [C], sizes.  ``sigma > 0`` smooths g (and total through it) along k with the filter of ``stats.rdf``
+    (reflect boundary, truncated at 4 sigma bins); counts and n stay raw."""
+    cb = _CellBatch(_as_cells(cells), device)
+    nbins, wt = _pair_nbins(R, dR), _rdf_weights(cb, weights)
+    return _rdf_finish(cb, _pair_counts(cb, float(dR), nbins), float(dR), float(sigma), wt)
+
+
+def _bond_statistics(cb: _CellBatch, bonds: BondList, dtheta, max_cn, former, bridge):
+    from types import SimpleNamespace
+    coordination, cn, ang, qn, qn_hist, over = _bond_stats(cb, bonds, dtheta, max_cn, former, bridge)
+    _raise_on_cell_overflow(over)
+    return SimpleNamespace(coordination=coordination, cn=cn, angles=ang, qn=qn, qn_hist=qn_hist, bonds=bonds)
+
+
+def bond_statistics(cells: Union[PeriodicCell, Sequence[PeriodicCell]], cutoff: float = 2.0, dtheta: float = 1.0, max_cn: int = 16,
+                    former: int = 1, bridge: int = 0, device=None):
+    """Coordination numbers, bond angles and Q^n speciation of periodic cells over the periodic bond list (``bond_list``: image
+    (j, s) is bonded to i iff closer than ``cutoff`` in fp64).  -> a namespace with coordination int32 [N, A] (bonds of every atom
+    by neighbour type; its row sums are the degrees of ``bonds``); cn int64 [C, A, A, max_cn + 1] and angles int64
+    [C, A, A(A+1)/2, ntheta] in the layout of ``stats.bond_statistics`` (cn[c, a, b, m] = atoms of type a with m bonds to type b, the
+    last bin max_cn or more; angles[c, a, p, k] = bonded pairs about centres of type a with neighbour types (b <= c),
+    p = b A - b(b-1)/2 + c - b, in the bin centred on k dtheta degrees, ntheta = floor(180 / dtheta + 0.5) + 1); qn int32 [N] = for an
+    atom of type ``former`` (default 1 = Si) its bonds to atoms of type ``bridge`` (default 0 = O) that are bonded to two or more
+    formers, -1 for every other atom; qn_hist int64 [C, max_cn + 1], the last bin saturating; bonds, the ``BondList``.  Raises
+    RuntimeError, naming the first such cell, if a centre has more than 64 bonds."""
+    cb = _CellBatch(_as_cells(cells), device)
+    return _bond_statistics(cb, _bond_list(cb, cutoff), dtheta, max_cn, former, bridge)
+
+
+def structure_profile(cells: Union[PeriodicCell, Sequence[PeriodicCell]], R: float = 10.0, dR: float = 0.01, sigma: float = 0.0,
+                      weights=None, cutoff: float = 2.0, dtheta: float = 1.0, max_cn: int = 16, former: int = 1, bridge: int = 0,
+                      device=None):
+    """``partial_rdf`` and ``bond_statistics`` of one batch from one upload and one bond list: a namespace with every field of
+    both."""
+    from types import SimpleNamespace
+    cb = _CellBatch(_as_cells(cells), device)
+    nbins, wt = _pair_nbins(R, dR), _rdf_weights(cb, weights)
+    rdf = _rdf_finish(cb, _pair_counts(cb, float(dR), nbins), float(dR), float(sigma), wt)
+    bs = _bond_statistics(cb, _bond_list(cb, cutoff), dtheta, max_cn, former, bridge)
+    return SimpleNamespace(**vars(rdf), **vars(bs))
+
+
+def compare_structures(cells_a, cells_b, R: float = 10.0, dR: float = 0.01, sigma: float = 0.0, weights=None, cutoff: float = 2.0,
+                       dtheta: float = 1.0, max_cn: int = 16, former: int = 1, bridge: int = 0, device=None):
+    """Cell-by-cell comparison of two batches (paired by index; atom counts may differ): both sides are profiled
+    (``structure_profile``) and ``stats``' curve metrics {cos, l2, mse, wasserstein} are taken of every g_ab ('g' [C, A, A]), of the
+    total g(r) ('total' [C]) and of the angle, CN and Q^n histograms, each normalised to sum 1 per curve the way
+    ``stats.compare_rings`` normalises ('angles' [C, A, A(A+1)/2], 'cn' [C, A, A], 'qn' [C]); cos is NaN where a curve is all zero.
+    -> dict with those, 'r', 'sizes_a', 'sizes_b' and the two profiles 'a', 'b'."""
+    from .stats import _curve_metrics
+    a_cells, b_cells = _as_cells(cells_a), _as_cells(cells_b)
+    if len(a_cells) != len(b_cells):
+        raise ValueError("the two batches must hold the same number of cells")
+    kw = dict(R=R, dR=dR, sigma=sigma, weights=weights, cutoff=cutoff, dtheta=dtheta, max_cn=max_cn, former=former, bridge=bridge, device=device)
+    a, b = structure_profile(a_cells, **kw), structure_profile(b_cells, **kw)
+    if a.g.shape != b.g.shape:
+        raise ValueError("the two batches differ in the number of atom types")
+
+    def unit(h):
+        h = h.double()
+        total = h.sum(-1, keepdim=True)
+        return torch.where(total > 0, h / total.clamp(min=1.0), h)
+
+    return dict(r=a.r, sizes_a=a.sizes, sizes_b=b.sizes, g=_curve_metrics(a.g, b.g), total=_curve_metrics(a.total, b.total),
+                angles=_curve_metrics(unit(a.angles), unit(b.angles)), cn=_curve_metrics(unit(a.cn), unit(b.cn)),
+                qn=_curve_metrics(unit(a.qn_hist), unit(b.qn_hist)), a=a, b=b)

@@ -694,6 +694,49 @@ int egnn_cell_env_host(int C, int A, const int32_t* cell_ptr, const double* latt
                        int32_t* bond_ptr, int64_t bond_cap, int32_t* bond_atom, int32_t* bond_shift, int32_t* env_size,
                        int64_t env_cap, int32_t* env_atom, int32_t* env_shift, int32_t* env_type, float* env_pos);
 
+/* ---- real-space statistics of periodic cells (csrc/cells/cell_stats.hip; definitions in csrc/cells/cell_stats_math.h) ----------
+ * The real-space counterpart of egnn_sq_cell_*: partial pair counts (-> g_ab(r), running coordination numbers), coordination
+ * numbers, bond angles and the Q^n speciation of whole cells, on the infinite lattice.  An extension: the reference has these
+ * statistics for one cluster about atom 0 only, and all three entries extend evaluate_RDF.py:39-60, evaluate_Si-O-Si.py:23-41 and
+ * CN2_evaluate.py:12-16 to periodic cells.  Cells as in egnn_cell_bonds_* (cell_ptr and lattice given twice, HOST copies for
+ * the checks); every accumulator is an integer and the results are bitwise reproducible, a cell giving the same bits in any batch.
+ * Bad arguments return EGNN_EINVAL with a message, naming the cell where one is at fault, before anything is launched: dR <= 0,
+ * nbins < 1, A > 4, A A nbins > 16384 (the LDS histogram), dtheta outside [0.5, 180], max_cn outside [1, 64], former or bridge
+ * outside [0, A) or equal, a singular lattice, a cell that needs more than 16 images along an axis.
+ *
+ * egnn_cell_pair_counts extends the counting loop of evaluate_RDF.py:39-60 to periodic cells, about every centre: d_counts int64
+ * [C, A, A, nbins], c[cell, a, b, k] = ordered pairs (i, (j, s)), s in Z^3, (j, s) != (i, 0), type(i) = a, type(j) = b, with
+ * floor(|(frac_j - frac_i + s) L| / dR) = k < nbins in fp64 (bin k is [k dR, (k + 1) dR): NOT the open bins (dR + k dR, dR +
+ * (k + 1) dR) of egnn_rdf and egnn_struct_pair_counts).  An atom pairs with its own images; c[a][b] == c[b][a] bitwise.  The image
+ * box |s_k| <= ceil(nbins dR / w_k) (w: the perpendicular widths) holds every such pair.  d_tiles int32 [n_tiles, 5] = {cell, first
+ * centre, first neighbour, piece, pieces}: 64 centres against 1024 neighbour atoms of a cell (local indices, every pair of
+ * multiples once) and piece `piece` of `pieces` (1 <= pieces <= 33, each piece once) of the values of s_0; one workgroup each. */
+int egnn_cell_pair_counts(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                          const double* d_lattice, const double* d_frac, const int32_t* d_type, double dR, int nbins,
+                          const int32_t* d_tiles, int n_tiles, int64_t* d_counts);
+/* egnn_cell_bond_stats extends the bond rule of evaluate_Si-O-Si.py:23-41 and the angle of CN2_evaluate.py:12-16 to periodic
+ * cells, about every centre, over the bond list of egnn_cell_bonds_fill: d_coordination int32 [N, A] = bonds of each atom by
+ * neighbour type; d_cn int64 [C, A, A, max_cn + 1] (the last bin: max_cn or more); d_angles int64 [C, A, A(A+1)/2, ntheta], bonded
+ * pairs p < q of a row about centres of type a with neighbour types (b <= c) at index b A - b(b-1)/2 + c - b, angle in fp64 from
+ * the site vectors, bin floor(theta / dtheta + 0.5), ntheta = floor(180 / dtheta + 0.5) + 1; d_qn int32 [N] = for an atom of type
+ * `former` its bonds to atoms of type `bridge` that have two or more bonds to formers, -1 for every other atom; d_qn_hist int64
+ * [C, max_cn + 1] (the last bin saturates); d_overflow int32 [C] = centres with more than 64 bonds: they count in d_coordination
+ * and d_cn and give no angle.  d_tiles int32 [n_tiles, 2] = {cell, first centre}: 8 centres (local index, every multiple of 8 below
+ * the cell's size once), one wavefront per centre. */
+int egnn_cell_bond_stats(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                         const double* d_lattice, const double* d_frac, const int32_t* d_type, const int32_t* d_row_ptr, int n_bonds,
+                         const int32_t* d_bond_atom, const int32_t* d_bond_shift, double dtheta, int max_cn, int former, int bridge,
+                         const int32_t* d_tiles, int n_tiles, int32_t* d_coordination, int64_t* d_cn, int64_t* d_angles, int32_t* d_qn,
+                         int64_t* d_qn_hist, int32_t* d_overflow);
+/* Host statement of the two entries above (evaluate_RDF.py:39-60, evaluate_Si-O-Si.py:23-41 and CN2_evaluate.py:12-16 extended
+ * to periodic cells): HOST pointers, no GPU, no tiles, the same definitions in plain C++; it builds the bond list of `cutoff`
+ * itself (egnn_cell_env_host's).  The pair part runs where counts is given, the bond part where coordination is given (then all six
+ * of its outputs are).  Also EGNN_EINVAL: a type outside [0, A), a coordinate that is not finite, a perpendicular width below the
+ * cutoff (bond part). */
+int egnn_cell_stats_host(int C, int A, const int32_t* cell_ptr, const double* lattice, const double* frac, const int32_t* type,
+                         double dR, int nbins, int64_t* counts, double cutoff, double dtheta, int max_cn, int former, int bridge,
+                         int32_t* coordination, int64_t* cn, int64_t* angles, int32_t* qn, int64_t* qn_hist, int32_t* overflow);
+
 /* ---- structure factors (csrc/eval/sq.hip; definitions in csrc/eval/sq_math.h) -----------------------------------------------
  * Reciprocal-space statistics: Debye sums of clusters and reciprocal-lattice sums of periodic cells.  No file of the reference
  * computes them (an extension, like the rings).  All sums are fp64 in one fixed order, no floating-point atomic: results are

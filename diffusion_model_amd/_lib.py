@@ -27,6 +27,8 @@ SQ_WINDOWS = {None: 0, "none": 0, "lorch": 1}
 CELL_CENTRE_BLOCK = 64    # kCellCentreBlock: the centres of one tile of egnn_cell_bonds_count / _fill
 # kCellStat* of csrc/cells/cell_stats_math.h: the tiles of egnn_cell_pair_counts / egnn_cell_bond_stats and their limits
 CELL_STAT_CENTRE_BLOCK, CELL_STAT_CHUNK, CELL_STAT_BOND_CENTRES, CELL_STAT_MAX_IMAGES, CELL_STAT_MAX_HIST = 64, 1024, 8, 16, 16384
+# kCellGrid* of csrc/cells/cell_grid_math.h: bins per axis, the reach, and the keys of a bond row staged per wavefront
+CELL_GRID_MAX_BINS, CELL_GRID_MAX_REACH, CELL_GRID_ROW_KEYS = 256, 3, 128
 PREALIGN_MIN_ATOMS = 5    # kPrealignMinAtoms of csrc/eval/assign_host.h: atom 0 and its four nearest neighbours
 
 
@@ -193,6 +195,14 @@ SIGNATURES = {
     "egnn_cell_pair_counts": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, _i, _vp]),
     "egnn_cell_bond_stats": (_i, [_vp, _i, _i, _i] + [_vp] * 7 + [_i, _vp, _vp, C.c_double, _i, _i, _i, _vp, _i] + [_vp] * 6),
     "egnn_cell_stats_host": (_i, [_i, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, C.c_double, C.c_double, _i, _i, _i] + [_vp] * 6),
+    "egnn_cell_grid_dims": (_i, [_i, _vp, C.c_double, _i, C.c_double, _vp]),
+    "egnn_cell_grid_count": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_double, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "egnn_cell_grid_fill": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_double, _i] + [_vp] * 5 + [_i] + [_vp] * 6),
+    "egnn_cell_bonds_grid_count": (_i, [_vp, _i, _i] + [_vp] * 8 + [_i, _vp, _vp, _vp, C.c_double, _i, _vp, _i, _vp]),
+    "egnn_cell_bonds_grid_fill": (_i, [_vp, _i, _i] + [_vp] * 8 + [_i, _vp, _vp, _vp, C.c_double, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "egnn_cell_pair_counts_grid": (_i, [_vp, _i, _i, _i] + [_vp] * 8 + [_i, _vp, _vp, _vp, C.c_double, _i, _i, _vp, _i, _vp]),
+    "egnn_cell_grid_host": (_i, [_i, _i, _vp, _vp, _vp, _vp, C.c_double, _i, C.c_double, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int64,
+                                 _vp, _vp, C.c_double, _i, _vp]),
     "egnn_sq_debye": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _vp, _i, _vp, _vp, _vp]),
     "egnn_sq_cell_plan": (_i, [_i, _vp, C.c_double, _vp, _vp]),
     "egnn_sq_cell_count": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),

@@ -15,6 +15,10 @@ its shell averages, finished to partial and total S(q); no file of the reference
 counterpart: g_ab(r) and the running coordination numbers over every image, CN histograms, bond angles and Q^n speciation of whole
 cells; the reference has them about atom 0 of one cluster only.
 
+The bond list and the pair counts come from kernels that test every atom of a cell against every centre, or -- ``method="grid"``,
+and ``"auto"`` for large cells -- from ``csrc/cells/cell_grid.hip``, which bins the atoms on a grid and searches the neighbouring
+bins only: O(n) instead of O(n^2), and bitwise the same outputs (``csrc/cells/cell_grid_math.h``).
+
 The definitions (``csrc/cells/cell_math.h``) are those of the INFINITE lattice: a site is (atom, integer shift), a bond joins
 sites closer than the cutoff, an environment is what ``shells`` bonds reach.  Wherever the reference's search uses no bond that
 wraps round its 3x3x3 supercell the two site sets are identical; where it does, the reference aliases an image onto a site on the
@@ -137,6 +141,96 @@ class _CellBatch:
         self.tiles = torch.from_numpy(tiles).to(dev)
 
 
+# ---- linked-cell search (csrc/cells/cell_grid.hip) ---------------------------------------------------------------------------------
+# "auto" sends a cell to the grid kernels when it is griddable and holds at least this many atoms; the results are bitwise the same
+# either way.  Measured by tools/cell_grid_time.py (profiles/cell_grid_time.json, README "Periodic cells") on one cell of 3,000 /
+# 24,000 / 192,000 atoms, whole calls: the bond list wins from 3,000 atoms (0.33 against 0.74 ms; 0.35 against 5.1 ms at 24,000), the
+# pair counts lose at 3,000 (0.37 against 0.30 ms) and win at 24,000 (0.40 against 1.41 ms).  24,000 is the smallest measured size at
+# which both win by more than the spread of the rounds; rounded up to a power of two.  Never below 2,048.
+_GRID_MIN_ATOMS = 32768
+_GRID_BOND_MIN_WIDTH = 0.0    # bond list: bins at least this thick (A); 0 = as fine as the cutoff allows (fastest of 0 / 3 / 4 A at 24,000 atoms)
+_GRID_PAIR_REACH = 2          # pair counts: bins of R / 2 walked two to each side (fastest of reach 1 / 2 / 3 at every measured size)
+_GRID_PAIR_MIN_WIDTH = 0.0
+_METHODS = ("auto", "direct", "grid")
+
+
+def _check_method(method: str) -> str:
+    if method not in _METHODS:
+        raise ValueError(f"method must be one of {_METHODS}, not {method!r}")
+    return method
+
+
+def _widths(lattice) -> np.ndarray:
+    """perpendicular widths of one cell, for messages"""
+    a, b, c = np.asarray(lattice, dtype=np.float64).reshape(3, 3)
+    det = abs(float(np.dot(a, np.cross(b, c))))
+    return np.array([det / np.linalg.norm(np.cross(b, c)), det / np.linalg.norm(np.cross(c, a)), det / np.linalg.norm(np.cross(a, b))])
+
+
+def _grid_cells(cb: "_CellBatch", method: str, radius: float, reach: int, min_width: float) -> Optional[np.ndarray]:
+    """the grids of the cells that take the grid path: int32 [C, 3], rows of zeros for the cells left to the direct kernels; None
+    where no cell takes it.  "grid" raises ValueError for a cell that is not griddable; "auto" takes a cell that is griddable and
+    holds at least _GRID_MIN_ATOMS atoms."""
+    if _check_method(method) == "direct":
+        return None
+    nb = torch.zeros(cb.C, 3, dtype=torch.int32)
+    _lib.check(_lib.lib().egnn_cell_grid_dims(cb.C, _lib.ptr(cb.lattice_h), float(radius), int(reach), float(min_width), _lib.ptr(nb)))
+    nb = nb.numpy()
+    ok = nb[:, 0] > 0
+    if method == "grid":
+        if not ok.all():
+            c = int(np.nonzero(~ok)[0][0])
+            w = _widths(cb.lattice_h[c].numpy())
+            raise ValueError(f"cell {c}: perpendicular widths {w[0]:.6g}, {w[1]:.6g}, {w[2]:.6g} A hold fewer than {2 * int(reach) + 1} bins of "
+                             f"{max(float(radius) / int(reach), float(min_width)):.6g} A on an axis: not griddable at radius {float(radius):.6g} "
+                             f"and reach {int(reach)} (use method='direct' or 'auto')")
+    else:
+        ok = ok & (np.asarray(cb.sizes, dtype=np.int64) >= _GRID_MIN_ATOMS)
+    if not ok.any():
+        return None
+    return np.where(ok[:, None], nb, 0).astype(np.int32)
+
+
+class _CellGrid:
+    """the cells of a batch that take the grid path, binned and sorted on the device (egnn_cell_grid_count, the prefix sum over all
+    bins, egnn_cell_grid_fill), and their {cell, first sorted centre} tiles"""
+
+    def __init__(self, cb: "_CellBatch", nb: np.ndarray, radius: float, reach: int):
+        lib, dev, N = _lib.lib(), cb.dev, cb.N
+        self.mask = nb[:, 0] > 0
+        self.radius, self.reach = float(radius), int(reach)
+        self.nb_h = torch.from_numpy(np.ascontiguousarray(nb, dtype=np.int32))
+        bin_ptr = np.zeros(cb.C + 1, dtype=np.int64)
+        bin_ptr[1:] = np.cumsum(np.prod(nb.astype(np.int64), axis=1))
+        if bin_ptr[-1] >= 2 ** 31 - 1:
+            raise ValueError("more than 2^31 - 2 bins in the batch (fewer cells per call)")
+        self.n_bins = B = int(bin_ptr[-1])
+        self.nb, self.bin_ptr = self.nb_h.to(dev), torch.from_numpy(bin_ptr.astype(np.int32)).to(dev)
+        atom_bin = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+        bin_count = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
+        head = (_lib.stream_ptr(), cb.C, N, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(self.nb_h), self.radius, self.reach,
+                _lib.ptr(cb.cell_ptr), _lib.ptr(self.nb), _lib.ptr(self.bin_ptr), _lib.ptr(cb.frac) if N else None)
+        _lib.check(lib.egnn_cell_grid_count(*head, B, _lib.ptr(atom_bin) if N else None, _lib.ptr(bin_count) if B else None))
+        self.bin_start = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+        if B:
+            self.bin_start[1:] = torch.cumsum(bin_count[:B].long(), 0).to(torch.int32)
+        work = torch.empty(max(B + N, 1), dtype=torch.int32, device=dev)
+        self.sorted_atom = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+        self.sorted_frac = torch.empty(max(N, 1), 3, dtype=torch.float64, device=dev)
+        self.sorted_type = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+        _lib.check(lib.egnn_cell_grid_fill(*head, _lib.ptr(cb.types) if N else None, B, _lib.ptr(self.bin_start), _lib.ptr(atom_bin) if N else None,
+                                           _lib.ptr(work), *((_lib.ptr(t) if N else None) for t in (self.sorted_atom, self.sorted_frac, self.sorted_type))))
+        self.atom_bin = atom_bin[:N]
+        self.tiles_h = torch.from_numpy(_bond_tiles(np.where(self.mask, np.asarray(cb.sizes, dtype=np.int64), 0)))
+        self.n_tiles, self.tiles = len(self.tiles_h), self.tiles_h.to(dev)
+
+    def args(self, cb: "_CellBatch"):
+        """the arguments the walking entries share after (stream, C, N[, A]): the HOST copies, then the device arrays up to n_bins
+        and bin_start"""
+        return (_lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(self.nb_h), _lib.ptr(self.tiles_h) if self.n_tiles else None,
+                _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice), _lib.ptr(self.nb), _lib.ptr(self.bin_ptr), self.n_bins, _lib.ptr(self.bin_start))
+
+
 class BondList:
     """CSR of the periodic bonds of a batch of cells: ``row_ptr`` int32 [N+1]; ``atom`` int32 [E], the neighbour as an index into
     the concatenated atoms of the batch; ``shift`` int32 [E, 3], the lattice shift of the neighbour's image relative to the wrapped
@@ -160,9 +254,15 @@ def decode_shift(code: torch.Tensor) -> torch.Tensor:
     return torch.stack((c // 81 - 4, c // 9 % 9 - 4, c % 9 - 4), -1)
 
 
-def _bond_args(cb: _CellBatch, cutoff: float):
+def _bond_args(cb: _CellBatch, cutoff: float, tiles: Optional[torch.Tensor] = None):
+    tiles = cb.tiles if tiles is None else tiles
     return (_lib.stream_ptr(), cb.C, cb.N, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice),
-            _lib.ptr(cb.frac), float(cutoff), _lib.ptr(cb.tiles), cb.n_tiles)
+            _lib.ptr(cb.frac), float(cutoff), _lib.ptr(tiles) if len(tiles) else None, len(tiles))
+
+
+def _grid_bond_args(cb: _CellBatch, grid: _CellGrid, cutoff: float):
+    return (_lib.stream_ptr(), cb.C, cb.N, *grid.args(cb), _lib.ptr(grid.sorted_atom), _lib.ptr(grid.sorted_frac), float(cutoff), grid.reach,
+            _lib.ptr(grid.tiles) if grid.n_tiles else None, grid.n_tiles)
 
 
 def _bonds_count(cb: _CellBatch, cutoff: float) -> torch.Tensor:
@@ -179,15 +279,40 @@ def _bonds_fill(cb: _CellBatch, cutoff: float, row_ptr: torch.Tensor, E: int):
     return atom, code
 
 
-def _bond_list(cb: _CellBatch, cutoff: float) -> BondList:
-    deg = _bonds_count(cb, cutoff)
+def _row_ptr(cb: _CellBatch, deg: torch.Tensor):
     row_ptr = torch.zeros(cb.N + 1, dtype=torch.int32, device=cb.dev)
     total = torch.cumsum(deg.long(), 0)
     E = int(total[-1]) if cb.N else 0
     if E >= 2 ** 31:
         raise ValueError("more than 2^31 - 1 bonds")
     row_ptr[1:] = total.to(torch.int32)
-    atom, code = _bonds_fill(cb, cutoff, row_ptr, E)
+    return row_ptr, E
+
+
+def _bond_list(cb: _CellBatch, cutoff: float, method: str = "direct", reach: int = 1, min_width: Optional[float] = None) -> BondList:
+    """``method`` chooses per cell between the direct kernels and the linked-cell ones (the same bits either way); ``reach`` and
+    ``min_width`` are the knobs of the grid (private: tests and tools/cell_grid_time.py pin every branch with them)"""
+    nb = _grid_cells(cb, method, cutoff, reach, _GRID_BOND_MIN_WIDTH if min_width is None else min_width)
+    if nb is None:
+        deg = _bonds_count(cb, cutoff)
+        row_ptr, E = _row_ptr(cb, deg)
+        atom, code = _bonds_fill(cb, cutoff, row_ptr, E)
+        return BondList(row_ptr, atom, code, cb.cell_ptr_h)
+    # a mixed batch: two launches into the same degrees, two into the same lists
+    lib = _lib.lib()
+    grid = _CellGrid(cb, nb, cutoff, reach)
+    direct = torch.from_numpy(_bond_tiles(np.where(grid.mask, 0, np.asarray(cb.sizes, dtype=np.int64)))).to(cb.dev)
+    deg = torch.zeros(max(cb.N, 1), dtype=torch.int32, device=cb.dev)[:cb.N]
+    if len(direct):
+        _lib.check(lib.egnn_cell_bonds_count(*_bond_args(cb, cutoff, direct), _lib.ptr(deg)))   # zeroes every degree, then its own centres
+    _lib.check(lib.egnn_cell_bonds_grid_count(*_grid_bond_args(cb, grid, cutoff), _lib.ptr(deg)))
+    row_ptr, E = _row_ptr(cb, deg)
+    atom = torch.empty(max(E, 1), dtype=torch.int32, device=cb.dev)[:E]
+    code = torch.empty(max(E, 1), dtype=torch.int32, device=cb.dev)[:E]
+    lists = (_lib.ptr(row_ptr), E, _lib.ptr(atom) if E else None, _lib.ptr(code) if E else None)
+    if len(direct):
+        _lib.check(lib.egnn_cell_bonds_fill(*_bond_args(cb, cutoff, direct), *lists))
+    _lib.check(lib.egnn_cell_bonds_grid_fill(*_grid_bond_args(cb, grid, cutoff), *lists))
     return BondList(row_ptr, atom, code, cb.cell_ptr_h)
 
 
@@ -218,12 +343,18 @@ def _env_fill(cb: _CellBatch, bonds: BondList, cc: torch.Tensor, shells: int, ma
     return e_atom, e_code, e_type, pos
 
 
-def bond_list(cells: Union[PeriodicCell, Sequence[PeriodicCell]], cutoff: float = 2.0, device=None) -> BondList:
+def bond_list(cells: Union[PeriodicCell, Sequence[PeriodicCell]], cutoff: float = 2.0, device=None, method: str = "auto") -> BondList:
     """The periodic bond list of every atom of a batch of cells (``return_index_within_2ang`` over the distance matrix of
     ``make_dataset.py:50-57,99``, without the matrix): image (j, s), s in {-1, 0, 1}^3, of atom j is bonded to atom i iff it is
     closer than ``cutoff`` in fp64 and is not i itself.  A cell with a perpendicular width below ``cutoff`` (27 images would not
-    hold every bond) or a singular lattice is refused (``EgnnError``, naming the cell)."""
-    return _bond_list(_CellBatch(_as_cells(cells), device), cutoff)
+    hold every bond) or a singular lattice is refused (``EgnnError``, naming the cell).
+
+    ``method``: "direct" tests every atom of a cell against every centre; "grid" bins the atoms and searches the neighbouring bins
+    (csrc/cells/cell_grid.hip; O(n), and ValueError naming the cell and its widths where a cell is too thin to be gridded); "auto"
+    (the default) chooses per cell -- the grid for a griddable cell of at least ``_GRID_MIN_ATOMS`` atoms.  The outputs are bitwise
+    the same whichever way a cell goes."""
+    _check_method(method)
+    return _bond_list(_CellBatch(_as_cells(cells), device), cutoff, method)
 
 
 def _centres(cb: _CellBatch, centres):
@@ -285,7 +416,7 @@ class EnvironmentBatch:
 
 
 def local_environments(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centres=None, shells: int = 2, cutoff: float = 2.0,
-                       max_atoms: int = 256, device=None) -> EnvironmentBatch:
+                       max_atoms: int = 256, device=None, method: str = "auto") -> EnvironmentBatch:
     """The environment of every requested centre: the centre plus the sites (atom, lattice shift) reachable from it in at most
     ``shells`` (1..4) bonds of the infinite lattice -- ``make_dataset.py:101-107`` (2NN), ``:177-188`` (3NN), ``:258-272`` (4NN)
     -- with positions ``float32((frac_j - frac_i + shift) L)`` relative to the centre (``:111``).
@@ -293,10 +424,12 @@ def local_environments(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centr
     ``centres``: None = every atom of every cell; an int = every atom of that type index (0 = O in the reference's one-hot);
     or an index tensor into the concatenated atoms of ``cells`` -- any order, duplicates allowed; the outputs follow its order.
     A centre without a bond yields a one-atom environment (the reference's drivers skip those; filter on ``sizes``).  A centre
-    whose environment exceeds ``max_atoms`` (<= 1024) raises ValueError naming cell and atom."""
+    whose environment exceeds ``max_atoms`` (<= 1024) raises ValueError naming cell and atom.  ``method`` chooses how the bond list
+    is built (``bond_list``)."""
+    _check_method(method)
     cb = _CellBatch(_as_cells(cells), device)
     shells, max_atoms = int(shells), int(max_atoms)
-    bonds = _bond_list(cb, cutoff)
+    bonds = _bond_list(cb, cutoff, method)
     idx_h, cell_h = _centres(cb, centres)
     M = int(idx_h.numel())
     cc = torch.stack((cell_h, idx_h)).to(torch.int32).to(cb.dev)
@@ -326,17 +459,18 @@ def local_environments(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centr
 
 
 def ring_statistics(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centres=None, cutoff: float = 2.0, max_size: int = 16,
-                    max_sites: int = 4096, device=None):
+                    max_sites: int = 4096, device=None, method: str = "auto"):
     """Shortest-path ring statistics on the infinite lattice of every cell (``stats.ring_statistics`` states the definition; not in
     the reference): the bond list is ``bond_list``'s, a site is (atom, lattice shift), and a ring closes only where the very same
     site is reached -- an image is never folded onto its atom, so a cell smaller than its rings gives the rings of the crystal,
     not of the torus (ideal beta-cristobalite in its 24-atom cell: size 12 through every angle).  ``centres`` as in
     ``local_environments``: None, a type index, or an index tensor into the concatenated atoms.  -> ``RingStatistics``.  Raises
     ValueError naming cell and atom where an atom has more than 32 bonds or a search labels more than ``max_sites`` (<= 4096)
-    sites."""
+    sites.  ``method`` chooses how the bond list is built (``bond_list``)."""
     from . import _rings
+    _check_method(method)
     cb = _CellBatch(_as_cells(cells), device)
-    bonds = _bond_list(cb, cutoff)
+    bonds = _bond_list(cb, cutoff, method)
     idx_h, cell_h = _centres(cb, centres)
     local_h = idx_h - cb.cell_ptr_h.long()[cell_h]
 
@@ -502,16 +636,30 @@ def _image_boxes(cb: _CellBatch, dR: float, nbins: int) -> np.ndarray:
     return np.clip(np.nan_to_num(s, nan=0.0, posinf=_lib.CELL_STAT_MAX_IMAGES), 0, _lib.CELL_STAT_MAX_IMAGES).astype(np.int64)
 
 
-def _pair_counts(cb: _CellBatch, dR: float, nbins: int, tiles: Optional[torch.Tensor] = None) -> torch.Tensor:
+def _pair_counts(cb: _CellBatch, dR: float, nbins: int, tiles: Optional[torch.Tensor] = None, method: str = "direct",
+                 reach: Optional[int] = None, min_width: Optional[float] = None) -> torch.Tensor:
     """-> int64 [C, A, A, nbins]: the raw output of egnn_cell_pair_counts; ``tiles``: the work list where the caller has it on the
-    device already"""
+    device already.  ``method`` chooses per cell between that entry and egnn_cell_pair_counts_grid, which adds the cells it is given
+    into the same array (the same integers either way); ``reach`` and ``min_width`` are the knobs of the grid (private)."""
+    reach = _GRID_PAIR_REACH if reach is None else int(reach)
+    nb = None if nbins < 1 else _grid_cells(cb, method, nbins * float(dR), reach, _GRID_PAIR_MIN_WIDTH if min_width is None else min_width)
+    sizes = np.asarray(cb.sizes, dtype=np.int64)
     if tiles is None:
-        tiles = torch.from_numpy(_pair_tiles(cb.sizes, _image_boxes(cb, dR, nbins))).to(cb.dev)
+        direct_sizes = sizes if nb is None else np.where(nb[:, 0] > 0, 0, sizes)
+        tiles = torch.from_numpy(_pair_tiles(direct_sizes, _image_boxes(cb, dR, nbins))).to(cb.dev)
     counts = torch.empty(cb.C, cb.A, cb.A, max(nbins, 1), dtype=torch.int64, device=cb.dev)
-    _lib.check(_lib.lib().egnn_cell_pair_counts(_lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h),
-                                                _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice), _lib.ptr(cb.frac) if cb.N else None,
-                                                _lib.ptr(cb.types) if cb.N else None, float(dR), int(nbins),
-                                                _lib.ptr(tiles) if len(tiles) else None, len(tiles), _lib.ptr(counts)))
+    if nb is None or len(tiles):
+        _lib.check(_lib.lib().egnn_cell_pair_counts(_lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h),
+                                                    _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice), _lib.ptr(cb.frac) if cb.N else None,
+                                                    _lib.ptr(cb.types) if cb.N else None, float(dR), int(nbins),
+                                                    _lib.ptr(tiles) if len(tiles) else None, len(tiles), _lib.ptr(counts)))
+    else:
+        counts.zero_()
+    if nb is not None:
+        grid = _CellGrid(cb, nb, nbins * float(dR), reach)
+        _lib.check(_lib.lib().egnn_cell_pair_counts_grid(_lib.stream_ptr(), cb.C, cb.N, cb.A, *grid.args(cb), _lib.ptr(grid.sorted_frac),
+                                                         _lib.ptr(grid.sorted_type), float(dR), int(nbins), grid.reach,
+                                                         _lib.ptr(grid.tiles) if grid.n_tiles else None, grid.n_tiles, _lib.ptr(counts)))
     return counts
 
 
@@ -598,20 +746,27 @@ def _rdf_finish(cb: _CellBatch, counts: torch.Tensor, dR: float, sigma: float, w
     return SimpleNamespace(r=(k + 0.5) * dR, counts=counts, g=g, n=n, total=total, n_type=n_type, volume=volume, sizes=list(cb.sizes))
 
 
-def pair_counts(cells: Union[PeriodicCell, Sequence[PeriodicCell]], R: float = 10.0, dR: float = 0.01, device=None) -> torch.Tensor:
+def pair_counts(cells: Union[PeriodicCell, Sequence[PeriodicCell]], R: float = 10.0, dR: float = 0.01, device=None,
+                method: str = "auto") -> torch.Tensor:
     """Ordered-pair counts by type over every centre AND every image of the infinite lattice: int64 [C, A, A, nbins],
     c[cell, a, b, k] = pairs (i, (j, s)), s in Z^3, (j, s) != (i, 0), with type(i) = a, type(j) = b and
     floor(|(w_j - w_i + s) L| / dR) = k in fp64 (csrc/cells/cell_stats_math.h).  An atom pairs with its own images, and
     c[a, b] == c[b, a] bitwise.  nbins = floor(R / dR + 0.5) and bin k is [k dR, (k + 1) dR): NOT the reference's open bins
     (dR + k dR, dR + (k + 1) dR) that ``stats.rdf`` and ``stats.pair_counts`` keep for clusters.  An extension: the reference counts
     about atom 0 of one cluster (evaluate_RDF.py:39-60).  Refused (``EgnnError``, naming the cell): a singular lattice, a cell that
-    needs more than 16 images along an axis to reach R, A A nbins > 16384."""
+    needs more than 16 images along an axis to reach R, A A nbins > 16384.
+
+    ``method``: "direct" tests every atom of a cell against every centre; "grid" bins the atoms and searches the neighbouring bins
+    (csrc/cells/cell_grid.hip; O(n), and ValueError naming the cell and its widths where a cell is too thin to be gridded); "auto"
+    (the default) chooses per cell -- the grid for a griddable cell of at least ``_GRID_MIN_ATOMS`` atoms.  The outputs are bitwise
+    the same whichever way a cell goes."""
+    _check_method(method)
     cb = _CellBatch(_as_cells(cells), device)
-    return _pair_counts(cb, float(dR), _pair_nbins(R, dR))
+    return _pair_counts(cb, float(dR), _pair_nbins(R, dR), method=method)
 
 
 def partial_rdf(cells: Union[PeriodicCell, Sequence[PeriodicCell]], R: float = 10.0, dR: float = 0.01, sigma: float = 0.0, weights=None,
-                device=None):
+                device=None, method: str = "auto"):
     """Partial pair distributions of periodic cells, the real-space counterpart of ``structure_factor``.  -> a namespace with
     r float64 [nbins] (bin centres, the bins of ``pair_counts``, not the reference's); counts int64 [C, A, A, nbins];
     g float64 [C, A, A, nbins] = V c_ab(k) / (N_a N_b (4 pi / 3) ((k + 1)^3 - k^3) dR^3) with V = |det L| -- the TRUE density of the
@@ -619,10 +774,12 @@ def partial_rdf(cells: Union[PeriodicCell, Sequence[PeriodicCell]], R: float = 1
     coordination cumsum_k c_ab / N_a; total float64 [C, nbins] = sum_ab c_a c_b w_a w_b g_ab / (sum_a c_a w_a)^2 with the
     concentrations c_a = N_a / N and ``weights`` [A] (default ``stats.NEUTRON_LENGTHS`` for A = 2, ones otherwise); n_type int64
     [C, A], volume float64 [C], sizes.  ``sigma > 0`` smooths g (and total through it) along k with the filter of ``stats.rdf``
-    (reflect boundary, truncated at 4 sigma bins); counts and n stay raw."""
+    (reflect boundary, truncated at 4 sigma bins); counts and n stay raw.  ``method`` chooses how the pairs are counted
+    (``pair_counts``)."""
+    _check_method(method)
     cb = _CellBatch(_as_cells(cells), device)
     nbins, wt = _pair_nbins(R, dR), _rdf_weights(cb, weights)
-    return _rdf_finish(cb, _pair_counts(cb, float(dR), nbins), float(dR), float(sigma), wt)
+    return _rdf_finish(cb, _pair_counts(cb, float(dR), nbins, method=method), float(dR), float(sigma), wt)
 
 
 def _bond_statistics(cb: _CellBatch, bonds: BondList, dtheta, max_cn, former, bridge):
@@ -633,7 +790,7 @@ def _bond_statistics(cb: _CellBatch, bonds: BondList, dtheta, max_cn, former, br
 
 
 def bond_statistics(cells: Union[PeriodicCell, Sequence[PeriodicCell]], cutoff: float = 2.0, dtheta: float = 1.0, max_cn: int = 16,
-                    former: int = 1, bridge: int = 0, device=None):
+                    former: int = 1, bridge: int = 0, device=None, method: str = "auto"):
     """Coordination numbers, bond angles and Q^n speciation of periodic cells over the periodic bond list (``bond_list``: image
     (j, s) is bonded to i iff closer than ``cutoff`` in fp64).  -> a namespace with coordination int32 [N, A] (bonds of every atom
     by neighbour type; its row sums are the degrees of ``bonds``); cn int64 [C, A, A, max_cn + 1] and angles int64
@@ -642,36 +799,40 @@ def bond_statistics(cells: Union[PeriodicCell, Sequence[PeriodicCell]], cutoff: 
     p = b A - b(b-1)/2 + c - b, in the bin centred on k dtheta degrees, ntheta = floor(180 / dtheta + 0.5) + 1); qn int32 [N] = for an
     atom of type ``former`` (default 1 = Si) its bonds to atoms of type ``bridge`` (default 0 = O) that are bonded to two or more
     formers, -1 for every other atom; qn_hist int64 [C, max_cn + 1], the last bin saturating; bonds, the ``BondList``.  Raises
-    RuntimeError, naming the first such cell, if a centre has more than 64 bonds."""
+    RuntimeError, naming the first such cell, if a centre has more than 64 bonds.  ``method`` chooses how the bond list is built
+    (``bond_list``)."""
+    _check_method(method)
     cb = _CellBatch(_as_cells(cells), device)
-    return _bond_statistics(cb, _bond_list(cb, cutoff), dtheta, max_cn, former, bridge)
+    return _bond_statistics(cb, _bond_list(cb, cutoff, method), dtheta, max_cn, former, bridge)
 
 
 def structure_profile(cells: Union[PeriodicCell, Sequence[PeriodicCell]], R: float = 10.0, dR: float = 0.01, sigma: float = 0.0,
                       weights=None, cutoff: float = 2.0, dtheta: float = 1.0, max_cn: int = 16, former: int = 1, bridge: int = 0,
-                      device=None):
+                      device=None, method: str = "auto"):
     """``partial_rdf`` and ``bond_statistics`` of one batch from one upload and one bond list: a namespace with every field of
-    both."""
+    both.  ``method`` as in ``pair_counts`` and ``bond_list``, chosen per cell and per statistic."""
     from types import SimpleNamespace
+    _check_method(method)
     cb = _CellBatch(_as_cells(cells), device)
     nbins, wt = _pair_nbins(R, dR), _rdf_weights(cb, weights)
-    rdf = _rdf_finish(cb, _pair_counts(cb, float(dR), nbins), float(dR), float(sigma), wt)
-    bs = _bond_statistics(cb, _bond_list(cb, cutoff), dtheta, max_cn, former, bridge)
+    rdf = _rdf_finish(cb, _pair_counts(cb, float(dR), nbins, method=method), float(dR), float(sigma), wt)
+    bs = _bond_statistics(cb, _bond_list(cb, cutoff, method), dtheta, max_cn, former, bridge)
     return SimpleNamespace(**vars(rdf), **vars(bs))
 
 
 def compare_structures(cells_a, cells_b, R: float = 10.0, dR: float = 0.01, sigma: float = 0.0, weights=None, cutoff: float = 2.0,
-                       dtheta: float = 1.0, max_cn: int = 16, former: int = 1, bridge: int = 0, device=None):
+                       dtheta: float = 1.0, max_cn: int = 16, former: int = 1, bridge: int = 0, device=None, method: str = "auto"):
     """Cell-by-cell comparison of two batches (paired by index; atom counts may differ): both sides are profiled
     (``structure_profile``) and ``stats``' curve metrics {cos, l2, mse, wasserstein} are taken of every g_ab ('g' [C, A, A]), of the
     total g(r) ('total' [C]) and of the angle, CN and Q^n histograms, each normalised to sum 1 per curve the way
     ``stats.compare_rings`` normalises ('angles' [C, A, A(A+1)/2], 'cn' [C, A, A], 'qn' [C]); cos is NaN where a curve is all zero.
-    -> dict with those, 'r', 'sizes_a', 'sizes_b' and the two profiles 'a', 'b'."""
+    -> dict with those, 'r', 'sizes_a', 'sizes_b' and the two profiles 'a', 'b'.  ``method`` as in ``structure_profile``."""
     from .stats import _curve_metrics
     a_cells, b_cells = _as_cells(cells_a), _as_cells(cells_b)
     if len(a_cells) != len(b_cells):
         raise ValueError("the two batches must hold the same number of cells")
-    kw = dict(R=R, dR=dR, sigma=sigma, weights=weights, cutoff=cutoff, dtheta=dtheta, max_cn=max_cn, former=former, bridge=bridge, device=device)
+    kw = dict(R=R, dR=dR, sigma=sigma, weights=weights, cutoff=cutoff, dtheta=dtheta, max_cn=max_cn, former=former, bridge=bridge, device=device,
+              method=_check_method(method))
     a, b = structure_profile(a_cells, **kw), structure_profile(b_cells, **kw)
     if a.g.shape != b.g.shape:
         raise ValueError("the two batches differ in the number of atom types")

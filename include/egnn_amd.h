@@ -737,6 +737,72 @@ int egnn_cell_stats_host(int C, int A, const int32_t* cell_ptr, const double* la
                          double dR, int nbins, int64_t* counts, double cutoff, double dtheta, int max_cn, int former, int bridge,
                          int32_t* coordination, int64_t* cn, int64_t* angles, int32_t* qn, int64_t* qn_hist, int32_t* overflow);
 
+/* ---- linked-cell search of periodic cells (csrc/cells/cell_grid.hip; definitions in csrc/cells/cell_grid_math.h) ---------------
+ * A second way to the outputs of egnn_cell_bonds_count / _fill and egnn_cell_pair_counts, bit for bit, whose cost grows with the
+ * number of atoms and not with its square: the atoms of a cell are binned on a grid, sorted by (bin, atom index), and a centre is
+ * tested against the (2 reach + 1)^3 bins about its own instead of against the whole cell.  An extension: no file of the reference
+ * bins a cell; the statistics are those of make_dataset.py:50-57,99 (bonds) and evaluate_RDF.py:39-60 (pairs) as the entries above
+ * extend them.  Whether a site (j, s) counts is decided by the text the direct kernels compile, so the two ways agree exactly.
+ *   grid     nb int32 [C, 3] per cell, from egnn_cell_grid_dims: nb_k = floor(reach w_k / max(radius (1 + 1e-6), reach min_width)),
+ *            at most 256 (w: the perpendicular widths); a cell with an axis below 2 reach + 1 bins is not griddable and has
+ *            nb = 0, 0, 0: it takes no part here and is left to the direct entries.  1 <= reach <= 3.  nb is given twice (HOST copy
+ *            for the checks, as cell_ptr and lattice are): an entry refuses a grid finer than its radius and reach allow.
+ *   bins     d_bin_ptr int32 [C+1]: the first bin of every cell among the n_bins = sum nb_0 nb_1 nb_2 bins of the batch; the bin of
+ *            an atom is (b_0 nb_1 + b_1) nb_2 + b_2 with b_k = min(nb_k - 1, floor(wrap(frac_k) nb_k)).
+ *   sorted   the atoms of a gridded cell ascending by (bin, atom index), in the cell's own range of the batch: d_bin_start int32
+ *            [n_bins + 1] counts the gridded atoms before each bin, d_sorted_atom int32 [N] (index into the batch, -1 in a cell
+ *            that is not gridded), d_sorted_frac double [N, 3] (wrapped), d_sorted_type int32 [N].
+ *   tiles    tiles / d_tiles int32 [n_tiles, 2] = {cell, first centre}: 64 consecutive SORTED centres of a gridded cell, given
+ *            twice (HOST copy for the checks); a tile that names a cell with nb = 0 is EGNN_EINVAL.
+ * Bad arguments return EGNN_EINVAL, naming the cell, before anything is launched.  Results are bitwise reproducible.
+ *
+ * egnn_cell_grid_dims (host only, no GPU): writes nb; a singular lattice is EGNN_EINVAL. */
+int egnn_cell_grid_dims(int C, const double* lattice, double radius, int reach, double min_width, int32_t* nb);
+/* egnn_cell_grid_count / _fill bin and sort a batch (count / prefix-by-caller / fill).  The count pass WRITES d_atom_bin int32 [N]
+ * (-1 in a cell that is not gridded) and d_bin_count int32 [n_bins]; the caller takes the exclusive prefix sum d_bin_start over all
+ * bins of the batch; the fill pass WRITES the three sorted arrays in full.  The place of an atom inside its bin is its rank by atom
+ * index, not the order in which an atomic handed out slots.  d_work int32 [n_bins + N] is workspace. */
+int egnn_cell_grid_count(void* stream, int C, int N, const int32_t* cell_ptr, const double* lattice, const int32_t* nb, double radius,
+                         int reach, const int32_t* d_cell_ptr, const int32_t* d_nb, const int32_t* d_bin_ptr, const double* d_frac,
+                         int n_bins, int32_t* d_atom_bin, int32_t* d_bin_count);
+int egnn_cell_grid_fill(void* stream, int C, int N, const int32_t* cell_ptr, const double* lattice, const int32_t* nb, double radius,
+                        int reach, const int32_t* d_cell_ptr, const int32_t* d_nb, const int32_t* d_bin_ptr, const double* d_frac,
+                        const int32_t* d_type, int n_bins, const int32_t* d_bin_start, const int32_t* d_atom_bin, int32_t* d_work,
+                        int32_t* d_sorted_atom, double* d_sorted_frac, int32_t* d_sorted_type);
+/* egnn_cell_bonds_grid_count / _fill: the outputs of egnn_cell_bonds_count / _fill for the cells the tiles name, bit for bit, over
+ * a grid of radius = cutoff.  The count pass WRITES d_degree at the ORIGINAL index of every centre of its tiles and touches no other
+ * entry (egnn_cell_bonds_count zeroes all of d_degree first: in a mixed batch call it first); d_row_ptr is the same prefix sum as
+ * before, and the fill pass WRITES the rows of its centres, ascending by (atom, shift code). */
+int egnn_cell_bonds_grid_count(void* stream, int C, int N, const int32_t* cell_ptr, const double* lattice, const int32_t* nb,
+                               const int32_t* tiles, const int32_t* d_cell_ptr, const double* d_lattice, const int32_t* d_nb,
+                               const int32_t* d_bin_ptr, int n_bins, const int32_t* d_bin_start, const int32_t* d_sorted_atom,
+                               const double* d_sorted_frac, double cutoff, int reach, const int32_t* d_tiles, int n_tiles,
+                               int32_t* d_degree);
+int egnn_cell_bonds_grid_fill(void* stream, int C, int N, const int32_t* cell_ptr, const double* lattice, const int32_t* nb,
+                              const int32_t* tiles, const int32_t* d_cell_ptr, const double* d_lattice, const int32_t* d_nb,
+                              const int32_t* d_bin_ptr, int n_bins, const int32_t* d_bin_start, const int32_t* d_sorted_atom,
+                              const double* d_sorted_frac, double cutoff, int reach, const int32_t* d_tiles, int n_tiles,
+                              const int32_t* d_row_ptr, int n_bonds, int32_t* d_bond_atom, int32_t* d_bond_shift);
+/* egnn_cell_pair_counts_grid: d_counts int64 [C, A, A, nbins] as egnn_cell_pair_counts defines it, over a grid of radius =
+ * nbins dR.  It ADDS the counts of the cells its tiles name and zeroes nothing (egnn_cell_pair_counts zeroes all of d_counts and
+ * then adds its own tiles: in a mixed batch call it first, or zero d_counts).  A A nbins <= 16384. */
+int egnn_cell_pair_counts_grid(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* nb,
+                               const int32_t* tiles, const int32_t* d_cell_ptr, const double* d_lattice, const int32_t* d_nb,
+                               const int32_t* d_bin_ptr, int n_bins, const int32_t* d_bin_start, const double* d_sorted_frac,
+                               const int32_t* d_sorted_type, double dR, int nbins, int reach, const int32_t* d_tiles, int n_tiles,
+                               int64_t* d_counts);
+/* Host statement of the entries above: HOST pointers, no GPU, no tiles, the same definitions in plain C++.  nb int32 [C, 3] and
+ * *n_bins are always written; atom_bin int32 [N], sorted_atom int32 [N] and sorted_frac double [N, 3] where given; bin_start int32
+ * [n_bins + 1] where given and bin_cap holds it.  Where bond_ptr int32 [N+1] is given, the bond list of cutoff = radius is found
+ * THROUGH THE GRID WALK (rows sorted by key; the lists written where given and bond_cap holds them); where counts int64
+ * [C, A, A, nbins] is given, the pair counts likewise (nbins dR <= radius).  Either walk refuses a batch with a cell that is not
+ * griddable (EGNN_EINVAL naming the cell and its widths).  Also EGNN_EINVAL: a type outside [0, A), a coordinate that is not
+ * finite. */
+int egnn_cell_grid_host(int C, int A, const int32_t* cell_ptr, const double* lattice, const double* frac, const int32_t* type,
+                        double radius, int reach, double min_width, int32_t* nb, int64_t* n_bins, int32_t* atom_bin, int64_t bin_cap,
+                        int32_t* bin_start, int32_t* sorted_atom, double* sorted_frac, int32_t* bond_ptr, int64_t bond_cap,
+                        int32_t* bond_atom, int32_t* bond_shift, double dR, int nbins, int64_t* counts);
+
 /* ---- structure factors (csrc/eval/sq.hip; definitions in csrc/eval/sq_math.h) -----------------------------------------------
  * Reciprocal-space statistics: Debye sums of clusters and reciprocal-lattice sums of periodic cells.  No file of the reference
  * computes them (an extension, like the rings).  All sums are fp64 in one fixed order, no floating-point atomic: results are

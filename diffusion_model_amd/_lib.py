@@ -29,6 +29,7 @@ CELL_CENTRE_BLOCK = 64    # kCellCentreBlock: the centres of one tile of egnn_ce
 CELL_STAT_CENTRE_BLOCK, CELL_STAT_CHUNK, CELL_STAT_BOND_CENTRES, CELL_STAT_MAX_IMAGES, CELL_STAT_MAX_HIST = 64, 1024, 8, 16, 16384
 # kCellGrid* of csrc/cells/cell_grid_math.h: bins per axis, the reach, and the keys of a bond row staged per wavefront
 CELL_GRID_MAX_BINS, CELL_GRID_MAX_REACH, CELL_GRID_ROW_KEYS = 256, 3, 128
+CELL_SOAP_MAX_BOX = 4     # kCellSoapMaxBox of csrc/cells/cell_soap_math.h: the image box the shift code holds
 PREALIGN_MIN_ATOMS = 5    # kPrealignMinAtoms of csrc/eval/assign_host.h: atom 0 and its four nearest neighbours
 
 
@@ -203,6 +204,13 @@ SIGNATURES = {
     "egnn_cell_pair_counts_grid": (_i, [_vp, _i, _i, _i] + [_vp] * 8 + [_i, _vp, _vp, _vp, C.c_double, _i, _i, _vp, _i, _vp]),
     "egnn_cell_grid_host": (_i, [_i, _i, _vp, _vp, _vp, _vp, C.c_double, _i, C.c_double, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int64,
                                  _vp, _vp, C.c_double, _i, _vp]),
+    "egnn_cell_sites_count": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, _vp]),
+    "egnn_cell_sites_fill": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, _vp, _i, _vp, _vp]),
+    "egnn_cell_soap_descriptor": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _i] + [_vp] * 4),
+    "egnn_cell_soap_mean": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "egnn_cell_sites_host": (_i, [_i, _vp, _vp, _vp, C.c_double, _i, _vp, _vp, C.c_int64, _vp, _vp]),
+    "egnn_cell_soap_host": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp, _i, _vp, _vp, _vp]),
+    "egnn_cell_soap_mean_host": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "egnn_sq_debye": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _vp, _i, _vp, _vp, _vp]),
     "egnn_sq_cell_plan": (_i, [_i, _vp, C.c_double, _vp, _vp]),
     "egnn_sq_cell_count": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),

@@ -845,3 +845,239 @@ def compare_structures(cells_a, cells_b, R: float = 10.0, dR: float = 0.01, sigm
     return dict(r=a.r, sizes_a=a.sizes, sizes_b=b.sizes, g=_curve_metrics(a.g, b.g), total=_curve_metrics(a.total, b.total),
                 angles=_curve_metrics(unit(a.angles), unit(b.angles)), cn=_curve_metrics(unit(a.cn), unit(b.cn)),
                 qn=_curve_metrics(unit(a.qn_hist), unit(b.qn_hist)), a=a, b=b)
+
+
+# ---- SOAP descriptors of periodic cells (csrc/cells/cell_soap.hip) ---------------------------------------------------------------
+# One launch lists the sites of, and describes, a slab of centres: the site list (two int32 per site) and the descriptor rows (and
+# coefficients) of a slab stay within this many bytes, the sites estimated from the densest cell's number density with a quarter
+# to spare.  The outputs do not depend on the slabs.
+_SOAP_SLAB_BYTES = 256 << 20
+
+
+class SiteList:
+    """CSR of the sites about M listed centres of a batch of cells, over every image inside the radius: ``row_ptr`` int32 [M+1];
+    ``atom`` int32 [T], the site's atom as an index into the concatenated atoms of the batch; ``shift_code`` int32 [T]
+    (csrc/cells/cell_math.h) and ``shift`` int32 [T, 3], its lattice shift relative to the wrapped atoms, |s_k| <= 4, on the device;
+    ``centre_cell`` / ``centre_atom`` int64 [M] (atom counted inside its cell) on the host.  Rows ascend by (atom, shift) and leave
+    the centre itself out; a row has the format of a ``BondList`` row."""
+
+    def __init__(self, row_ptr, atom, shift_code, centre_cell, centre_atom):
+        self.row_ptr, self.atom, self.shift_code, self.centre_cell, self.centre_atom = row_ptr, atom, shift_code, centre_cell, centre_atom
+
+    @property
+    def shift(self) -> torch.Tensor:
+        return decode_shift(self.shift_code)
+
+    @property
+    def num_sites(self) -> int:
+        return int(self.atom.shape[0])
+
+
+def _check_site_boxes(cb: _CellBatch, radius: float):
+    """the refusals of csrc/cells/cell_soap_math.h, as ValueError naming the cell and its widths: the image box
+    floor(radius / w_k) + 1 must stay within 4, the range of the shift code"""
+    if not (math.isfinite(radius) and radius > 0.0):
+        raise ValueError("the radius must be positive and finite")
+    for c in range(cb.C):
+        L = cb.lattice_h[c].numpy().reshape(3, 3)
+        scale = float(np.prod(np.linalg.norm(L, axis=1)))
+        if not (scale < 1e300) or not abs(float(np.linalg.det(L))) > 1e-9 * scale:
+            raise ValueError(f"cell {c}: singular lattice")
+        w = _widths(L)
+        if not bool(np.all(np.floor(radius / w) + 1.0 <= _lib.CELL_SOAP_MAX_BOX)):
+            raise ValueError(f"cell {c}: perpendicular widths {w[0]:.6g}, {w[1]:.6g}, {w[2]:.6g} A and one is at most radius / 4 = "
+                             f"{radius / 4:.6g} A: its sites need more than {_lib.CELL_SOAP_MAX_BOX} images to a side (use a supercell)")
+
+
+class _SiteSearch:
+    """how the sites about centres of a batch are found at one radius, decided once per cell: "direct" by the site kernels
+    (egnn_cell_sites_count / _fill: any image box up to 4, work for the listed centres only), "grid" through the linked-cell bond
+    list of the whole cell at cutoff = radius (``_bond_list(.., "grid")``; ValueError for a cell that is not griddable), "auto" the
+    grid for a griddable cell of at least ``_GRID_MIN_ATOMS`` atoms.  That constant was measured for bond lists at 2 A, NOT at this
+    radius.  The one comparison at this radius (tools/cell_soap_time.py, profiles/cell_soap_time.json: 256 listed centres of a
+    24,000-atom cell at 8.37 A, whole calls, best of 5) has the grid at 3.0 ms against 9.3 ms direct, with a spread of the grid's
+    rounds (33.8 ms, the first call) above the difference and no smaller cell compared: no crossover, so no constant of its own.
+    The rows are bitwise the same either way."""
+
+    def __init__(self, cb: _CellBatch, radius: float, method: str):
+        self.cb, self.radius = cb, float(radius)
+        _check_method(method)
+        _check_site_boxes(cb, self.radius)
+        nb = _grid_cells(cb, method, self.radius, 1, _GRID_BOND_MIN_WIDTH)
+        self.grid_mask = None
+        if nb is not None:
+            mask = nb[:, 0] > 0
+            gc = np.nonzero(mask)[0]
+            self.grid_mask = torch.from_numpy(mask)
+            self.sub = _CellBatch([cb.cells[int(c)] for c in gc], cb.dev)
+            self.bonds = _bond_list(self.sub, self.radius, "grid")
+            first = torch.zeros(cb.C, dtype=torch.int64)   # the first atom of a gridded cell inside the sub-batch
+            first[torch.from_numpy(gc)] = self.sub.cell_ptr_h[:-1].long()
+            self.sub_first = first
+
+    def rows(self, idx_h: torch.Tensor, cell_h: torch.Tensor):
+        """-> (row_ptr int32 [m+1], atom int32 [T], shift code int32 [T]) on the device, for centres ``idx_h`` (into the batch) of cells
+        ``cell_h``, in their order"""
+        cb, dev, m = self.cb, self.cb.dev, int(idx_h.numel())
+        lib = _lib.lib()
+        gridded = torch.zeros(m, dtype=torch.bool) if self.grid_mask is None else self.grid_mask[cell_h]
+        direct = torch.where(gridded, torch.full_like(idx_h, -1), idx_h).to(torch.int32).to(dev)   # -1: an empty row from the site kernels
+        head = (_lib.stream_ptr(), cb.C, cb.N, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice),
+                _lib.ptr(cb.frac) if cb.N else None, self.radius, m, _lib.ptr(direct) if m else None)
+        deg = torch.zeros(max(m, 1), dtype=torch.int32, device=dev)[:m]
+        any_direct = bool((~gridded).any())
+        if any_direct:
+            _lib.check(lib.egnn_cell_sites_count(*head, _lib.ptr(deg)))
+        lens = deg.long()
+        if bool(gridded.any()):
+            gm = torch.nonzero(gridded).reshape(-1)
+            first_full = cb.cell_ptr_h.long()[cell_h[gm]]
+            sub_atom = (idx_h[gm] - first_full + self.sub_first[cell_h[gm]]).to(dev)
+            offset = (first_full - self.sub_first[cell_h[gm]]).to(dev)
+            rp = self.bonds.row_ptr.long()
+            src0, glen = rp[sub_atom], rp[sub_atom + 1] - rp[sub_atom]
+            gm = gm.to(dev)
+            lens[gm] = glen
+        row_ptr = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+        row_ptr[1:] = torch.cumsum(lens, 0)
+        T = int(row_ptr[-1])
+        if T >= 2 ** 31:
+            raise ValueError(f"more than 2^31 - 1 sites in one slab of {m} centres (lower the slab budget or the radius)")
+        row_ptr32 = row_ptr.to(torch.int32)
+        atom = torch.empty(max(T, 1), dtype=torch.int32, device=dev)[:T]
+        code = torch.empty(max(T, 1), dtype=torch.int32, device=dev)[:T]
+        if any_direct and T:
+            _lib.check(lib.egnn_cell_sites_fill(*head, _lib.ptr(row_ptr32), T, _lib.ptr(atom), _lib.ptr(code)))
+        if bool(gridded.any()) and int(glen.sum()):
+            rep = torch.repeat_interleave(torch.arange(gm.numel(), device=dev), glen)
+            within = torch.arange(rep.numel(), device=dev) - (torch.cumsum(glen, 0) - glen)[rep]
+            src, dst = src0[rep] + within, row_ptr[gm][rep] + within
+            atom[dst] = (self.bonds.atom[src].long() + offset[rep]).to(torch.int32)
+            code[dst] = self.bonds.shift_code[src]
+        return row_ptr32, atom, code
+
+
+def neighbour_sites(cells: Union[PeriodicCell, Sequence[PeriodicCell]], radius: float, centres=None, method: str = "auto",
+                    device=None) -> SiteList:
+    """The sites about every requested centre over EVERY image inside ``radius``: site (j, s), s in Z^3, belongs to centre i iff
+    |(w_j - w_i + s) L| < radius in fp64 and it is not (i, 0) (csrc/cells/cell_soap_math.h) -- ``bond_list`` without its limit of 27
+    images, so that a cell narrower than the radius is served: the image box floor(radius / w_k) + 1 may reach 4 on an axis.  A cell
+    with a perpendicular width <= radius / 4, or a singular lattice, raises ValueError naming the cell and its widths.  ``centres`` as
+    in ``local_environments``: None, a type index, or an index tensor into the concatenated atoms (any order, repeats allowed; the
+    rows follow it).  ``method``: "direct" (the site kernels: work for the listed centres only), "grid" (the linked-cell bond list of
+    the whole cell; ValueError for a cell too thin to be gridded at ``radius``), "auto" (the grid for a griddable cell of at least
+    ``_GRID_MIN_ATOMS`` atoms); the rows are bitwise the same either way."""
+    cb = _CellBatch(_as_cells(cells), device)
+    search = _SiteSearch(cb, float(radius), method)
+    idx_h, cell_h = _centres(cb, centres)
+    row_ptr, atom, code = search.rows(idx_h, cell_h)
+    return SiteList(row_ptr, atom, code, cell_h, idx_h - cb.cell_ptr_h.long()[cell_h])
+
+
+class _CellSoap:
+    """one batch of cells, one basis, one cut: the site search and the descriptor launches of slabs of centres"""
+
+    def __init__(self, cells, basis, neighbour_cut, method, device):
+        from .soap import SoapBasis
+        self.cb = cb = _CellBatch(_as_cells(cells), device)
+        if cb.A > _lib.SOAP_MAX_TYPES:
+            raise ValueError(f"{cb.A} atom types (at most {_lib.SOAP_MAX_TYPES})")
+        self.basis = SoapBasis() if basis is None else basis
+        self.cut = self.basis.neighbour_cut if neighbour_cut is None else float(neighbour_cut)
+        if not (math.isfinite(self.cut) and self.cut > 0.0):
+            raise ValueError("neighbour_cut must be positive and finite")
+        self.search = _SiteSearch(cb, self.cut, method)
+        self.F = self.basis.features(cb.A)
+        self.coeff_shape = (cb.A, self.basis.n_max, (self.basis.l_max + 1) ** 2)
+        self.tables = self.basis.device_tables(cb.dev)
+
+    def slab_centres(self, coefficients: bool, budget: int) -> int:
+        """centres per launch under ``budget`` bytes: descriptor row, coefficients, and the estimated sites of one centre"""
+        cb = self.cb
+        vol = np.abs(np.linalg.det(cb.lattice_h.numpy().reshape(-1, 3, 3)))
+        density = float(np.max(np.asarray(cb.sizes, dtype=np.float64) / vol)) if cb.C else 0.0
+        sites = int(math.ceil(1.25 * density * 4.0 / 3.0 * math.pi * self.cut ** 3)) + 1
+        per = 8 * self.F + (8 * int(np.prod(self.coeff_shape)) if coefficients else 0) + 8 * sites
+        return max(1, int(budget) // per)
+
+    def describe(self, idx_h, cell_h, desc, coeff):
+        """the descriptors of one slab of centres into ``desc`` [m, F] (and ``coeff``)"""
+        cb, m = self.cb, int(idx_h.numel())
+        if m == 0:
+            return
+        row_ptr, atom, code = self.search.rows(idx_h, cell_h)
+        T = int(atom.shape[0])
+        who = torch.cat([idx_h.to(torch.int32), torch.arange(m, dtype=torch.int32)]).to(cb.dev)   # one upload: the centres, then their rows
+        _lib.check(_lib.lib().egnn_cell_soap_descriptor(
+            _lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice),
+            _lib.ptr(cb.frac), _lib.ptr(cb.types), self.basis.n_max, self.basis.l_max, _lib.ptr(self.tables), m, _lib.ptr(row_ptr), T,
+            _lib.ptr(atom) if T else None, _lib.ptr(code) if T else None, m, _lib.ptr(who[:m]), _lib.ptr(who[m:]), _lib.ptr(desc),
+            _lib.ptr(coeff)))
+
+
+def soap_descriptors(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centres=None, basis=None, neighbour_cut=None,
+                     return_coefficients: bool = False, method: str = "auto", device=None, _slab_bytes: Optional[int] = None):
+    """The SOAP power spectrum of atoms of periodic cells, over the sites of every image inside the neighbour cut
+    (``neighbour_sites`` at ``neighbour_cut``, default ``basis.neighbour_cut`` = r_cut + sigma sqrt(2 ln 1000); the centre itself
+    included): -> float64 [M, F] in the feature order of ``soap.soap_descriptors``, with ``return_coefficients`` also float64
+    [M, A, n_max, (l_max+1)^2].  The site vectors and distances stay in fp64 from the fractional coordinates; the tables, formulas
+    and summation orders are those of the cluster descriptor (csrc/eval/soap_device.h), the sum running over the centre first and
+    then its sites by ascending (atom, shift).  A <= 4.  ``centres`` and ``method`` as in ``neighbour_sites``.  dscribe's
+    ``periodic=True`` is the behaviour restated, from its description ("SOAP").  Centres are processed in slabs of
+    at most ``_SOAP_SLAB_BYTES`` of site lists and rows; the outputs do not depend on the slabs."""
+    run = _CellSoap(cells, basis, neighbour_cut, method, device)
+    cb = run.cb
+    idx_h, cell_h = _centres(cb, centres)
+    M = int(idx_h.numel())
+    desc = torch.empty(max(M, 1), run.F, dtype=torch.float64, device=cb.dev)[:M]
+    coeff = torch.empty(max(M, 1), *run.coeff_shape, dtype=torch.float64, device=cb.dev)[:M] if return_coefficients else None
+    step = run.slab_centres(return_coefficients, _SOAP_SLAB_BYTES if _slab_bytes is None else _slab_bytes)
+    for m0 in range(0, M, step):
+        m1 = min(M, m0 + step)
+        run.describe(idx_h[m0:m1], cell_h[m0:m1], desc[m0:m1], coeff[m0:m1] if coeff is not None else None)
+    return (desc, coeff) if return_coefficients else desc
+
+
+def average_soap(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centres=None, basis=None, neighbour_cut=None, method: str = "auto",
+                 device=None, _slab_bytes: Optional[int] = None):
+    """The mean SOAP power spectrum of every cell over its centres -- None = every atom, or a type index: -> (float64 [C, F],
+    count int64 [C]).  The rows of a cell's centres (``soap_descriptors``) are added in ascending atom order into one running fp64
+    sum and divided once by their number (egnn_cell_soap_mean; no atomic: a cell gives the same bits in any batch and for any slab
+    size).  A cell without a centre of the type gives a row of zeros and count 0."""
+    if centres is not None and not (isinstance(centres, (int, np.integer)) and not isinstance(centres, bool)):
+        raise ValueError("average_soap takes centres=None (every atom) or a type index")
+    run = _CellSoap(cells, basis, neighbour_cut, method, device)
+    cb = run.cb
+    idx_h, cell_h = _centres(cb, centres)   # ascending atoms: the centres of a cell are contiguous
+    M = int(idx_h.numel())
+    count_h = torch.bincount(cell_h, minlength=cb.C)[:cb.C].to(torch.int64)
+    mean = torch.zeros(cb.C, run.F, dtype=torch.float64, device=cb.dev)
+    if M == 0:
+        return mean, count_h.to(cb.dev)
+    step = run.slab_centres(False, _SOAP_SLAB_BYTES if _slab_bytes is None else _slab_bytes)
+    count = count_h.to(cb.dev)
+    rows = torch.empty(min(step, M), run.F, dtype=torch.float64, device=cb.dev)
+    cells_edge = torch.arange(cb.C + 1, dtype=torch.int64)
+    for m0 in range(0, M, step):
+        m1 = min(M, m0 + step)
+        run.describe(idx_h[m0:m1], cell_h[m0:m1], rows[:m1 - m0], None)
+        cell_rows = torch.searchsorted(cell_h[m0:m1].contiguous(), cells_edge).to(torch.int32).to(cb.dev)
+        _lib.check(_lib.lib().egnn_cell_soap_mean(_lib.stream_ptr(), cb.C, run.F, m1 - m0, _lib.ptr(rows), _lib.ptr(cell_rows), _lib.ptr(count),
+                                                  int(m0 == 0), int(m1 == M), _lib.ptr(mean)))
+    return mean, count
+
+
+def soap_similarity(cells_a, cells_b, centres=None, basis=None, neighbour_cut=None, method: str = "auto", device=None):
+    """Cell-by-cell SOAP similarity of two batches (paired by index; atom counts may differ): -> float64 [C], ``soap.cosine`` of
+    the two ``average_soap`` rows; NaN where either cell has no centre of the type.  ValueError for batches of unequal length or
+    unequal numbers of atom types, as ``compare_structures``."""
+    from . import soap
+    a_cells, b_cells = _as_cells(cells_a), _as_cells(cells_b)
+    if len(a_cells) != len(b_cells):
+        raise ValueError("the two batches must hold the same number of cells")
+    if max(c.num_types for c in a_cells) != max(c.num_types for c in b_cells):
+        raise ValueError("the two batches differ in the number of atom types")
+    kw = dict(centres=centres, basis=basis, neighbour_cut=neighbour_cut, method=method, device=device)
+    (a, na), (b, nb) = average_soap(a_cells, **kw), average_soap(b_cells, **kw)
+    cos = soap.cosine(a, b)
+    return torch.where((na > 0) & (nb > 0), cos, torch.full_like(cos, float("nan")))

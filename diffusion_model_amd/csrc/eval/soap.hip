@@ -5,24 +5,14 @@
 // No kernel has an atomic: every output is the sum of one thread (or of one wavefront's fixed butterfly), so a repeated call is
 // bitwise reproducible.  A kernel trusts no entry it reads: a centre is checked against N, its graph against N, a type against
 // A, a pair against the row counts.
-#include "eval_device.h"
+#include "soap_device.h"
 #include "soap_host.h"
 #include "soap_math.h"
 
 namespace egnn {
 
-constexpr int kSoapThreads = 1024;    // threads of a descriptor workgroup (16 wavefronts share the staging of a chunk)
 constexpr int kSoapGramA = 4;         // rows of a in one tile of the cosine matrix: one per wavefront
 constexpr int kSoapGramB = 8;         // rows of b in one tile: eight running sums per lane
-
-// LDS of the descriptor kernel, in doubles: coefficients [A][n_max][LM] | solid harmonics [chunk][LM] | radial values
-// [chunk][n_max (l_max+1)] | dx, dy, dz, d2 [chunk][4]; then the species of the chunk's atoms, int [chunk]
-__host__ __device__ inline size_t soap_lds_doubles(int A, int n_max, int l_max) {
-  return (size_t)A * n_max * soap_lm_count(l_max) + (size_t)kSoapChunk * (soap_lm_count(l_max) + n_max * (l_max + 1) + 4);
-}
-__host__ __device__ inline size_t soap_lds_bytes(int A, int n_max, int l_max) {
-  return sizeof(double) * soap_lds_doubles(A, n_max, l_max) + sizeof(int) * kSoapChunk;
-}
 
 // ---- descriptor: one workgroup of 16 wavefronts per centre ---------------------------------------------------------------------
 // The graph's atoms are staged 32 at a time: one thread per atom takes the difference, d2 and the cut decision; then the
@@ -42,12 +32,8 @@ __global__ __launch_bounds__(kSoapThreads) void soap_descriptor_kernel(const flo
   __shared__ int s_range[2];
   const int tid = threadIdx.x, ci = blockIdx.x;
   if (ci >= n_centres) return;
-  const int L1 = l_max + 1, LM = soap_lm_count(l_max), nL = n_max * L1, nC = A * n_max * LM, F = soap_feature_count(A, n_max, l_max);
-  double* s_c = s_soap;
-  double* s_solid = s_c + nC;
-  double* s_rad = s_solid + kSoapChunk * LM;
-  double* s_xyz = s_rad + kSoapChunk * nL;
-  int* s_species = reinterpret_cast<int*>(s_xyz + 4 * kSoapChunk);
+  const int LM = soap_lm_count(l_max), nC = A * n_max * LM, F = soap_feature_count(A, n_max, l_max);
+  const SoapLds s = soap_lds_carve(s_soap, A, n_max, l_max);
   const int i = centres[ci];
   if (tid == 0) {   // the graph of atom i: the last g with graph_ptr[g] <= i
     int lo = -1, hi = -1;
@@ -64,75 +50,27 @@ __global__ __launch_bounds__(kSoapThreads) void soap_descriptor_kernel(const flo
     s_range[0] = lo;
     s_range[1] = hi;
   }
-  for (int o = tid; o < nC; o += kSoapThreads) s_c[o] = 0.0;
+  for (int o = tid; o < nC; o += kSoapThreads) s.c[o] = 0.0;
   __syncthreads();
   const int lo = s_range[0], hi = s_range[1];
   double* row = desc + (size_t)ci * F;
+  double* coeff_row = coeff ? coeff + (size_t)ci * nC : nullptr;
   if (lo < 0) {   // no such atom or no such graph: a row of zeros, which no descriptor is
-    for (int f = tid; f < F; f += kSoapThreads) row[f] = 0.0;
-    if (coeff) for (int o = tid; o < nC; o += kSoapThreads) coeff[(size_t)ci * nC + o] = 0.0;
+    soap_zero_row(A, n_max, l_max, row, coeff_row, tid);
     return;
   }
-  const double* norm = tables + soap_table_norm(n_max, l_max);
   for (int j0 = lo; j0 < hi; j0 += kSoapChunk) {   // uniform in the workgroup
     const int cnt = min(kSoapChunk, hi - j0);
     if (tid < cnt) {
       const int j = j0 + tid, tj = type[j];
       double dx, dy, dz;
       const double d2 = soap_dist2(pos + 3 * (size_t)i, pos + 3 * (size_t)j, &dx, &dy, &dz);
-      s_xyz[4 * tid] = dx; s_xyz[4 * tid + 1] = dy; s_xyz[4 * tid + 2] = dz; s_xyz[4 * tid + 3] = d2;
-      s_species[tid] = (d2 < cut2 && tj >= 0 && tj < A) ? tj : -1;
+      s.xyz[4 * tid] = dx; s.xyz[4 * tid + 1] = dy; s.xyz[4 * tid + 2] = dz; s.xyz[4 * tid + 3] = d2;
+      s.species[tid] = (d2 < cut2 && tj >= 0 && tj < A) ? tj : -1;
     }
-    __syncthreads();
-    for (int task = tid; task < cnt * L1; task += kSoapThreads) {
-      const int jj = task / L1, m = task - jj * L1;
-      if (s_species[jj] < 0) continue;
-      soap_solid_column(s_xyz[4 * jj], s_xyz[4 * jj + 1], s_xyz[4 * jj + 2], s_xyz[4 * jj + 3], m, l_max, norm, s_solid + jj * LM);
-    }
-    for (int task = tid; task < cnt * nL; task += kSoapThreads) {
-      const int jj = task / nL, q = task - jj * nL;
-      if (s_species[jj] < 0) continue;
-      s_rad[jj * nL + q] = soap_radial(tables, n_max, l_max, q, s_xyz[4 * jj + 3]);
-    }
-    __syncthreads();
-    for (int o = tid; o < n_max * LM; o += kSoapThreads) {
-      const int n = o / LM, lm = o - n * LM, q = n * L1 + soap_l_of(lm);
-      double acc[kSoapMaxTypes];
-#pragma unroll
-      for (int z = 0; z < kSoapMaxTypes; ++z) acc[z] = z < A ? s_c[(z * n_max + n) * LM + lm] : 0.0;
-      for (int jj = 0; jj < cnt; ++jj) {
-        const int z = s_species[jj];
-        if (z < 0) continue;
-        const double term = s_rad[jj * nL + q] * s_solid[jj * LM + lm];
-#pragma unroll
-        for (int t = 0; t < kSoapMaxTypes; ++t)
-          if (t == z) acc[t] += term;
-      }
-#pragma unroll
-      for (int z = 0; z < kSoapMaxTypes; ++z)
-        if (z < A) s_c[(z * n_max + n) * LM + lm] = acc[z];
-    }
-    __syncthreads();   // the staging is rewritten by the next chunk
+    soap_chunk_accumulate(s, cnt, A, n_max, l_max, tables, tid);   // soap_device.h: shared with cells/cell_soap.hip
   }
-  // beta over n, in place: the thread of column (z, lm) reads its n_max primitives, then writes its n_max coefficients
-  const double* beta = tables + soap_table_beta(n_max, l_max);
-  for (int col = tid; col < A * LM; col += kSoapThreads) {
-    const int z = col / LM, lm = col - z * LM;
-    const double* bl = beta + (size_t)soap_l_of(lm) * n_max * n_max;
-    double v[kSoapMaxN];
-#pragma unroll
-    for (int n = 0; n < kSoapMaxN; ++n) v[n] = n < n_max ? s_c[(z * n_max + n) * LM + lm] : 0.0;
-    for (int n = 0; n < n_max; ++n) {
-      double sum = 0.0;
-#pragma unroll
-      for (int np = 0; np < kSoapMaxN; ++np)
-        if (np < n_max) sum += bl[n * n_max + np] * v[np];
-      s_c[(z * n_max + n) * LM + lm] = sum;
-    }
-  }
-  __syncthreads();
-  if (coeff) for (int o = tid; o < nC; o += kSoapThreads) coeff[(size_t)ci * nC + o] = s_c[o];
-  for (int f = tid; f < F; f += kSoapThreads) row[f] = soap_power_entry(s_c, tables, f, A, n_max, l_max);
+  soap_finish(s, A, n_max, l_max, tables, row, coeff_row, tid);
 }
 
 // ---- cosine of listed pairs of rows: one wavefront per pair -------------------------------------------------------------------

@@ -803,6 +803,55 @@ int egnn_cell_grid_host(int C, int A, const int32_t* cell_ptr, const double* lat
                         int32_t* bin_start, int32_t* sorted_atom, double* sorted_frac, int32_t* bond_ptr, int64_t bond_cap,
                         int32_t* bond_atom, int32_t* bond_shift, double dR, int nbins, int64_t* counts);
 
+/* ---- SOAP descriptors of periodic cells (csrc/cells/cell_soap.hip; definitions in csrc/cells/cell_soap_math.h) -----------------
+ * The descriptor of egnn_soap_descriptor about atoms of periodic cells, over the sites of EVERY image inside the neighbour cut:
+ * site (j, s), s in Z^3, belongs to centre i iff |(wrap(frac_j) - wrap(frac_i) + s) L|^2 < cut^2 in fp64 (the vector of
+ * egnn_cell_bonds_*); the centre itself contributes at d = 0 and its own images are ordinary sites.  Vectors and d2 stay in fp64;
+ * tables, summation orders and the feature order are those of egnn_soap_descriptor.  An extension: template_matching.py:41-47 builds
+ * its descriptors on clusters; dscribe's periodic=True is the behaviour restated, from its description ("SOAP").
+ * Cells as in egnn_cell_bonds_* (cell_ptr and lattice given twice, HOST copies for the checks).  The image box of a cell is
+ * b_k = floor(cut / w_k) + 1 (w: the perpendicular widths) and must stay <= 4, the range of the shift code: a cell with a width
+ * <= cut / 4, or a singular lattice, is EGNN_EINVAL naming the cell and its widths, before anything is launched.  No atomic:
+ * results are bitwise reproducible and a cell gives the same bits in any batch.
+ *
+ * egnn_cell_sites_count / _fill (count / prefix-by-caller / fill): the sites of M listed centres, d_centre_atom int32 [M] (index
+ * into the batch; any order, repeats allowed; a centre outside [0, N) gets an empty row).  The count pass WRITES d_degree int32 [M];
+ * the caller takes the exclusive prefix sum d_row_ptr int32 [M+1]; the fill pass WRITES d_site_atom int32 [T] (index into the
+ * batch) and d_site_shift int32 [T] (shift code): a row in the format of a bond-list row, ascending by (atom, shift code), the
+ * centre (i, 0) left out.  One wavefront per centre walks every candidate (atom, shift of the box); work is done for the listed
+ * centres only.  Where every width is >= cut the rows are those of egnn_cell_bonds_fill at cutoff = cut, bitwise. */
+int egnn_cell_sites_count(void* stream, int C, int N, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                          const double* d_lattice, const double* d_frac, double cut, int M, const int32_t* d_centre_atom,
+                          int32_t* d_degree);
+int egnn_cell_sites_fill(void* stream, int C, int N, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                         const double* d_lattice, const double* d_frac, double cut, int M, const int32_t* d_centre_atom,
+                         const int32_t* d_row_ptr, int T, int32_t* d_site_atom, int32_t* d_site_shift);
+/* egnn_cell_soap_descriptor: d_desc double [M, F] (F = egnn_soap_features(A, n_max, l_max)) and, where given, d_coeff double
+ * [M, A, n_max, (l_max+1)^2], of the M >= 1 centres d_centre_atom; centre m owns row d_centre_row[m] of the CSR (d_row_ptr int32
+ * [n_rows + 1], d_site_atom, d_site_shift int32 [T]): the site kernels' (row m) or a bond list of cutoff = cut (row = atom).  The
+ * sum runs over the centre first, then the row in its order.  A <= 4, n_max <= 16, l_max <= 10; d_tables as egnn_soap_descriptor.
+ * A centre outside [0, N) or a row outside the CSR gives a row of zeros; a site outside the centre's cell contributes nothing. */
+int egnn_cell_soap_descriptor(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                              const double* d_lattice, const double* d_frac, const int32_t* d_type, int n_max, int l_max,
+                              const double* d_tables, int n_rows, const int32_t* d_row_ptr, int T, const int32_t* d_site_atom,
+                              const int32_t* d_site_shift, int M, const int32_t* d_centre_atom, const int32_t* d_centre_row, double* d_desc,
+                              double* d_coeff);
+/* egnn_cell_soap_mean: the mean descriptor of every cell, d_sum double [C, F].  Rows d_cell_rows[c] .. d_cell_rows[c + 1] (int32
+ * [C+1]) of d_desc [M, F] are the centres of cell c in this call, ascending; they are added in that order to the running sum
+ * (started from zero where first != 0, else continued from d_sum: centres may come in slabs), and where final != 0 the sum is
+ * divided once by d_count[c] (int64 [C], the cell's centres over all calls; a cell without one keeps a row of zeros). */
+int egnn_cell_soap_mean(void* stream, int C, int F, int M, const double* d_desc, const int32_t* d_cell_rows, const int64_t* d_count,
+                        int first, int final, double* d_sum);
+/* Host statements of the entries above: HOST pointers, no GPU, the same definitions in plain C++ (the box walk without a cull).
+ * egnn_cell_sites_host always writes row_ptr int32 [M+1]; the lists where given and site_cap holds them (call once with site_cap 0
+ * to learn T).  Also EGNN_EINVAL: a centre outside [0, N), a type outside [0, A), a coordinate that is not finite. */
+int egnn_cell_sites_host(int C, const int32_t* cell_ptr, const double* lattice, const double* frac, double cut, int M,
+                         const int32_t* centre_atom, int32_t* row_ptr, int64_t site_cap, int32_t* site_atom, int32_t* site_shift);
+int egnn_cell_soap_host(int C, int A, const int32_t* cell_ptr, const double* lattice, const double* frac, const int32_t* type, int n_max,
+                        int l_max, double cut, const double* tables, int M, const int32_t* centre_atom, double* desc, double* coeff);
+int egnn_cell_soap_mean_host(int C, int F, const int32_t* cell_rows, const double* desc, const int64_t* count, int first, int final,
+                             double* sum);
+
 /* ---- structure factors (csrc/eval/sq.hip; definitions in csrc/eval/sq_math.h) -----------------------------------------------
  * Reciprocal-space statistics: Debye sums of clusters and reciprocal-lattice sums of periodic cells.  No file of the reference
  * computes them (an extension, like the rings).  All sums are fp64 in one fixed order, no floating-point atomic: results are

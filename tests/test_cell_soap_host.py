@@ -1,0 +1,178 @@
+"""The SOAP descriptors of periodic cells on the host (egnn_cell_sites_host, egnn_cell_soap_host, egnn_cell_soap_mean_host:
+csrc/cells/cell_soap_host.cpp over the definitions the kernels compile, csrc/cells/cell_soap_math.h and csrc/eval/soap_math.h) against
+  * the numpy restatement tests/_cell_soap_util.py: site lists exactly, descriptors to rounding;
+  * the truth tests/golden/cell_soap_golden.npz (mpmath at 60 digits, sites by exact rational arithmetic): site keys exactly,
+    E_host = max |p - p_truth| / max |p_truth| below the project's CAP = 1e-7 (measured: printed by the test);
+  * the bond list of egnn_cell_env_host at cutoff = cut on cells whose widths all reach the cut: the same rows, bitwise.
+Refusals (a width <= cut / 4, a singular lattice, A = 5) and a stand-alone program under the address and undefined-behaviour
+sanitizers.  No GPU.  Every input first passes the gap check: no site within 1e-9 (relative) of the cut.
+"""
+import numpy as np
+import pytest
+
+from diffusion_model_amd import _lib
+from tests import _cell_soap_util as CSU
+from tests import _cells_util as CU
+from tests import _soap_util as SU
+from tests._host_program import build_and_run
+
+EINVAL = -22
+G = CSU.golden()
+SMALL_CUT, DEFAULT_CUT = SU.neighbour_cut(SU.CONFIGS["small"]), SU.neighbour_cut(SU.CONFIGS["default"])
+FIXTURE_CASES = [(name, A) for name, (_, As, _) in CSU.FIXTURES.items() for A in As]
+
+
+def _check_sites(cells, cut, centres):
+    """host == restatement exactly -> the CSR"""
+    want_ptr, want_atom, want_code, gap = CSU.site_lists(cells, cut, centres)
+    assert gap > 1e-9, "ambiguous input: a site on the cut"
+    rc, row_ptr, atom, code = CSU.host_sites(_lib.lib(), cells, cut, centres)
+    assert rc == 0, _lib.lib().egnn_last_error()
+    assert np.array_equal(row_ptr, want_ptr) and np.array_equal(atom, want_atom) and np.array_equal(code, want_code)
+    return row_ptr, atom, code
+
+
+@pytest.mark.parametrize("name", list(CSU.FIXTURES))
+def test_site_lists_of_the_fixtures_equal_restatement_and_truth(name):
+    cell, centres, cut = CSU.checked_fixture(name, CSU.FIXTURES[name][1][0])
+    row_ptr, atom, code = _check_sites([cell], cut, centres)
+    assert np.array_equal(row_ptr, G[f"{name}_row_ptr"]) and np.array_equal(atom.astype(np.int64) * 729 + code, G[f"{name}_keys"])
+    b = CSU.box(cell["lattice"], cut)
+    assert int(np.abs(CU.shift_decode(code)).max(initial=0)) <= int(b.max())
+    if name == "thin":
+        assert b.tolist() == [4, 1, 2] and int(np.abs(CU.shift_decode(code)[:, 0]).max()) == 4, "the thin axis must reach shift 4"
+    if name == "crist":
+        assert b.tolist() == [2, 2, 2] and int(np.diff(row_ptr).min()) > 128
+    if name == "one":
+        assert np.all(atom == 0) and len(atom) == 18 and CU.CENTRE_CODE not in code.tolist()
+
+
+@pytest.mark.parametrize("cell,cut", [("chain", SMALL_CUT), ("triclinic", SMALL_CUT), ("cristobalite", SMALL_CUT), ("cristobalite", DEFAULT_CUT),
+                                      ("chain", DEFAULT_CUT)])
+def test_site_lists_of_the_cell_fixtures(cell, cut):
+    c = getattr(CU, cell + "_cell")()
+    n = len(c["frac"])
+    _check_sites([c], cut, np.arange(n))
+    _check_sites([c], cut, np.array([n - 1, 0, n - 1]))
+
+
+def test_site_lists_of_a_mixed_batch():
+    cells = [CU.one_atom_cell(), CSU.fixture("thin", 2), CU.chain_cell(), CU.triclinic_cell(), CU.one_atom_cell()]
+    N = sum(len(c["frac"]) for c in cells)
+    every = _check_sites(cells, SMALL_CUT, np.arange(N))
+    listed = np.array([N - 1, 5, 0, 20, 5, 13])
+    row_ptr, atom, code = _check_sites(cells, SMALL_CUT, listed)
+    for m, i in enumerate(listed):                       # a listed centre owns the row it has among all atoms
+        lo, hi = every[0][i], every[0][i + 1]
+        assert np.array_equal(atom[row_ptr[m]:row_ptr[m + 1]], every[1][lo:hi]) and np.array_equal(code[row_ptr[m]:row_ptr[m + 1]], every[2][lo:hi])
+    rc, ptr0, _, _ = CSU.host_sites(_lib.lib(), cells, SMALL_CUT, np.zeros(0, np.int32))
+    assert rc == 0 and ptr0.tolist() == [0]
+
+
+@pytest.mark.parametrize("cell,cut", [("chain", 2.0), ("chain", 3.1), ("triclinic", SMALL_CUT), ("cristobalite", SMALL_CUT), ("triclinic", 2.0)])
+def test_site_lists_equal_the_bond_list_where_27_images_are_complete(cell, cut):
+    c = getattr(CU, cell + "_cell")()
+    assert np.all(CU.widths(c["lattice"]) >= cut)
+    rc, env = CU.host_environments(_lib.lib(), [c], centres=[0], shells=1, cutoff=cut, max_atoms=1024)
+    assert rc == 0, _lib.lib().egnn_last_error()
+    row_ptr, atom, code = _check_sites([c], cut, np.arange(len(c["frac"])))
+    assert np.array_equal(row_ptr, env["bond_ptr"]) and np.array_equal(atom, env["bond_atom"]) and np.array_equal(code, env["bond_shift"])
+
+
+@pytest.mark.parametrize("name,A", FIXTURE_CASES)
+def test_host_descriptors_against_the_truth(name, A):
+    cfg = CSU.FIXTURES[name][0]
+    desc, coeff = CSU.host_on_golden(name, A)
+    E = SU.descriptor_error(desc, G[f"{name}_A{A}_desc"])
+    print(f"cell SOAP {name} A={A} ({cfg}): E_host = {E:.3e}")
+    assert E < SU.CAP
+    if f"{name}_A{A}_coeff" in G.files:
+        Ec = SU.descriptor_error(coeff, G[f"{name}_A{A}_coeff"])
+        print(f"cell SOAP {name} A={A} ({cfg}): coefficients E_host = {Ec:.3e}")
+        assert Ec < SU.CAP
+    assert not np.any(desc == -7.0) and not np.any(coeff == -7.0)
+
+
+@pytest.mark.parametrize("cfg", ["small", "default"])
+def test_e_host_stays_below_the_cap(cfg):
+    print(f"cell SOAP {cfg}: E_host = {CSU.e_host(cfg):.3e} (cluster SOAP: {SU.e_host(cfg):.3e})")
+    assert CSU.e_host(cfg) < SU.CAP
+
+
+@pytest.mark.parametrize("name,A", [("thin", 3), ("one", 1)])
+def test_host_descriptors_against_the_restatement(name, A):
+    cell, centres, cut = CSU.checked_fixture(name, A)
+    cfg = CSU.FIXTURES[name][0]
+    want, want_c = CSU.descriptors([cell], A, centres, SU.tables(cfg)[0], cut)
+    desc, coeff = CSU.host_on_golden(name, A)
+    assert SU.descriptor_error(desc, want) < 8 * CSU.e_host(cfg) and SU.descriptor_error(coeff, want_c) < 8 * CSU.e_host(cfg)
+
+
+def test_a_cell_gives_the_same_bits_in_any_batch_and_order():
+    L, cfg, flat = _lib.lib(), SU.CONFIGS["small"], SU.tables("small")[1]
+    thin = CSU.fixture("thin", 2)
+    cells = [CU.one_atom_cell(), thin, CU.chain_cell()]
+    alone = CSU.host_on_golden("thin", 2)[0]
+    rc, desc, _ = CSU.host_soap(L, cells, 2, cfg, flat, 1 + np.arange(12))
+    assert rc == 0 and np.array_equal(desc, alone)
+    rc, desc, _ = CSU.host_soap(L, cells, 2, cfg, flat, [12, 1, 12, 14], coeff=False)
+    assert rc == 0 and np.array_equal(desc[0], alone[11]) and np.array_equal(desc[1], alone[0]) and np.array_equal(desc[2], alone[11])
+    # whole lattice vectors added to fractions that stay exact under the addition (multiples of 2^-40): the same wrapped atoms, the
+    # same bits
+    exact = dict(thin, frac=np.round(thin["frac"] * 2.0 ** 40) / 2.0 ** 40)
+    shifted = dict(exact, frac=exact["frac"] + np.array([3.0, -2.0, 1.0]))
+    assert np.array_equal(CU.wrap(shifted["frac"]), CU.wrap(exact["frac"]))
+    rc, want, _ = CSU.host_soap(L, [exact], 2, cfg, flat, np.arange(12), coeff=False)
+    rc2, desc, _ = CSU.host_soap(L, [shifted], 2, cfg, flat, np.arange(12), coeff=False)
+    assert rc == 0 and rc2 == 0 and np.array_equal(desc, want)
+
+
+def test_mean_host_is_the_running_sum_divided_once():
+    L = _lib.lib()
+    rng = np.random.default_rng(4)
+    desc = rng.choice([-1.0, 1.0], (9, 70)) * 10.0 ** rng.uniform(-6, 2, (9, 70))
+    cell_of_row = np.array([0, 0, 0, 2, 2, 3, 3, 3, 3])
+    want, count = CSU.running_mean(desc, cell_of_row, 4)
+    rows = np.searchsorted(cell_of_row, np.arange(5))
+    once = np.full((4, 70), -7.0)
+    assert CSU.host_mean(L, desc, rows, count, 1, 1, once) == 0 and np.array_equal(once, want)
+    assert np.all(once[1] == 0.0) and count.tolist() == [3, 0, 2, 4]
+    for cutat in (1, 3, 4, 7):                           # continued over two calls, cut inside and between cells
+        total = np.full((4, 70), -7.0)
+        assert CSU.host_mean(L, desc[:cutat], np.searchsorted(cell_of_row[:cutat], np.arange(5)), count, 1, 0, total) == 0
+        assert CSU.host_mean(L, desc[cutat:], np.searchsorted(cell_of_row[cutat:], np.arange(5)), count, 0, 1, total) == 0
+        assert np.array_equal(total, want), cutat
+
+
+def test_refusals():
+    L, cfg, flat = _lib.lib(), SU.CONFIGS["small"], SU.tables("small")[1]
+    thin = CSU.fixture("thin", 2)
+    w = CU.widths(thin["lattice"])
+    assert CSU.host_soap(L, [thin], 2, cfg, flat, [0])[0] == 0
+    for cut, ok in ((4.0 * w.min() * (1 - 1e-12), True), (4.0 * w.min() * (1 + 1e-12), False)):   # either side of width = cut / 4
+        rc = CSU.host_sites(L, [thin], cut, [0])[0]
+        assert (rc == 0) == ok
+        assert CSU.host_soap(L, [thin], 2, cfg, flat, [0], cut=cut)[0] == rc
+    msg = L.egnn_last_error().decode()
+    assert "cell 0" in msg and f"{w[0]:.6g}" in msg and f"{w[1]:.6g}" in msg and f"{w[2]:.6g}" in msg and "cut / 4" in msg
+    rc = CSU.host_sites(L, [CU.chain_cell(), thin], 5.3, [0])[0]
+    assert rc == EINVAL and b"cell 1" in L.egnn_last_error()
+    flatcell = dict(thin, lattice=np.array([[1.15, 0, 0], [0.4, 4.8, 0], [2.3, 0, 0]]))
+    assert CSU.host_sites(L, [flatcell], SMALL_CUT, [0])[0] == EINVAL and b"singular" in L.egnn_last_error()
+    assert CSU.host_soap(L, [flatcell], 2, cfg, flat, [0])[0] == EINVAL and b"singular" in L.egnn_last_error()
+    assert CSU.host_soap(L, [thin], 5, cfg, flat, [0])[0] == EINVAL and b"atom types" in L.egnn_last_error()
+    assert CSU.host_soap(L, [thin], 1, cfg, flat, [0])[0] == EINVAL and b"type" in L.egnn_last_error()
+    for bad in ([12], [-1]):
+        assert CSU.host_sites(L, [thin], SMALL_CUT, bad)[0] == EINVAL and b"centre 0" in L.egnn_last_error()
+        assert CSU.host_soap(L, [thin], 2, cfg, flat, bad)[0] == EINVAL
+    for cut in (0.0, -1.0, np.nan, np.inf):
+        assert CSU.host_sites(L, [thin], cut, [0])[0] == EINVAL
+        assert CSU.host_soap(L, [thin], 2, cfg, flat, [0], cut=cut)[0] == EINVAL
+    nan = thin["frac"].copy()
+    nan[3, 1] = np.nan
+    assert CSU.host_sites(L, [dict(thin, frac=nan)], SMALL_CUT, [0])[0] == EINVAL and b"not finite" in L.egnn_last_error()
+
+
+def test_cell_soap_host_under_sanitizers(tmp_path):
+    r = build_and_run(tmp_path, "cell_soap_main", ["cells/cell_soap_host.cpp", "host_logic.cpp"])
+    assert r.returncode == 0 and "CELL-SOAP-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

@@ -211,6 +211,10 @@ SIGNATURES = {
     "egnn_cell_sites_host": (_i, [_i, _vp, _vp, _vp, C.c_double, _i, _vp, _vp, C.c_int64, _vp, _vp]),
     "egnn_cell_soap_host": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp, _i, _vp, _vp, _vp]),
     "egnn_cell_soap_mean_host": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "egnn_cell_boo_qlm": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [C.c_double, C.c_uint, _i, _vp, _i, _vp, _i, _vp, _vp, _i] + [_vp] * 4),
+    "egnn_cell_boo_invariants": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [C.c_uint, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, C.c_double, _i, _i, _vp, _i, _vp,
+                                      _vp, _i] + [_vp] * 5),
+    "egnn_cell_boo_host": (_i, [_i, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_uint, _i, _vp, _i, _vp, _vp, _vp, _i, C.c_double, _i, _i] + [_vp] * 5),
     "egnn_sq_debye": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _vp, _i, _vp, _vp, _vp]),
     "egnn_sq_cell_plan": (_i, [_i, _vp, C.c_double, _vp, _vp]),
     "egnn_sq_cell_count": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),

@@ -19,6 +19,10 @@ The bond list and the pair counts come from kernels that test every atom of a ce
 and ``"auto"`` for large cells -- from ``csrc/cells/cell_grid.hip``, which bins the atoms on a grid and searches the neighbouring
 bins only: O(n) instead of O(n^2), and bitwise the same outputs (``csrc/cells/cell_grid_math.h``).
 
+``neighbour_sites`` / ``soap_descriptors`` (``csrc/cells/cell_soap.hip``) reach every image inside a radius; ``bond_order`` and
+``bond_order_profile`` (``csrc/cells/cell_boo.hip``) compute Steinhardt's bond-orientational order over those sites: q_l, w_l, the
+Lechner-Dellago averages and the ten Wolde-Frenkel solid-bond count (an extension: no file of the reference computes them).
+
 The definitions (``csrc/cells/cell_math.h``) are those of the INFINITE lattice: a site is (atom, integer shift), a bond joins
 sites closer than the cutoff, an environment is what ``shells`` bonds reach.  Wherever the reference's search uses no bond that
 wraps round its 3x3x3 supercell the two site sets are identical; where it does, the reference aliases an image onto a site on the
@@ -1081,3 +1085,230 @@ def soap_similarity(cells_a, cells_b, centres=None, basis=None, neighbour_cut=No
     (a, na), (b, nb) = average_soap(a_cells, **kw), average_soap(b_cells, **kw)
     cos = soap.cosine(a, b)
     return torch.where((na > 0) & (nb > 0), cos, torch.full_like(cos, float("nan")))
+
+
+# ---- bond-orientational order (csrc/cells/cell_boo.hip; definitions in csrc/cells/cell_boo_math.h) ----------------------------------
+_BOO_DIGITS = 60
+_BOO_SLAB_BYTES = 256 << 20   # site lists of one slab of pass 1 or pass 2; the outputs do not depend on the slabs
+
+
+def _boo_norm(l_max: int) -> np.ndarray:
+    """N_lm of csrc/eval/soap_math.h, float64 [(l_max+1)^2], as ``soap.build_tables`` builds it: mpmath, rounded once"""
+    import mpmath as mp
+    from .soap import DIGITS
+    norm = np.empty((l_max + 1) ** 2)
+    with mp.workdps(int(DIGITS)):
+        for l in range(l_max + 1):
+            for m in range(-l, l + 1):
+                v = mp.sqrt((2 * l + 1) / (4 * mp.pi) * mp.factorial(l - abs(m)) / mp.factorial(l + abs(m)))
+                norm[l * l + l + m] = float(v * mp.sqrt(2) if m else v)
+    return norm
+
+
+def _wigner3j_lll(l: int, m1: int, m2: int, m3: int):
+    """the 3j symbol (l l l; m1 m2 m3), m1 + m2 + m3 = 0, by Racah's formula in exact arithmetic -> (s, r), Fractions with
+    3j = s sqrt(r): s the alternating sum with the phase (-1)^(l - l - m3), r the triangle coefficient times the six factorials"""
+    from fractions import Fraction
+    f = math.factorial
+    r = Fraction(f(l) ** 3, f(3 * l + 1)) * f(l + m1) * f(l - m1) * f(l + m2) * f(l - m2) * f(l + m3) * f(l - m3)
+    s = Fraction(0)
+    for t in range(max(0, -m1, m2), min(l, l - m1, l + m2) + 1):
+        s += Fraction((-1) ** t, f(t) * f(t + m1) * f(t - m2) * f(l - t) * f(l - t - m1) * f(l - t + m2))
+    return (-1) ** (m3 % 2) * s, r
+
+
+_BOO_TABLES = {}
+
+
+def _boo_tables(l_max: int):
+    """-> (norm float64 [(l_max+1)^2], g_off int32 [l_max+2], g_idx int32 [E, 3], g_val float64 [E]): N_lm and the tensors G^l of
+    csrc/cells/cell_boo_math.h.  With q^c_m the coefficients in the complex harmonics (Condon-Shortley phase) and q_mu those in the
+    real basis, q^c_0 = q_0, q^c_m = (-1)^m (q_m + i q_-m) / sqrt 2 and q^c_-m = (q_m - i q_-m) / sqrt 2 (m > 0), so
+    w_l = sum_{m1+m2+m3=0} 3j q^c_m1 q^c_m2 q^c_m3 = sum_abc T_abc q_a q_b q_c; G_abc (a <= b <= c, as l + mu) is the sum of T over the
+    orderings of (a, b, c).  The 3j symbols are exact (Racah); the square roots and the basis change are taken in mpmath at 60 digits
+    and every entry is rounded once.  Even l only: for odd l the contraction of the antisymmetric symbol with a symmetric product
+    vanishes identically and the table is empty.  Built once per l_max."""
+    if l_max in _BOO_TABLES:
+        return _BOO_TABLES[l_max]
+    import mpmath as mp
+    off, idx, val = [0], [], []
+    with mp.workdps(_BOO_DIGITS):
+        half = 1 / mp.sqrt(2)
+
+        def real_parts(m):   # q^c_m = sum of coefficient * q_mu over these (mu, coefficient)
+            if m == 0:
+                return [(0, mp.mpc(1))]
+            if m > 0:
+                return [(m, (-1) ** m * half * mp.mpc(1)), (-m, (-1) ** m * half * mp.mpc(0, 1))]
+            return [(-m, half * mp.mpc(1)), (m, -half * mp.mpc(0, 1))]
+
+        for l in range(l_max + 1):
+            entries = {}
+            if l % 2 == 0:
+                for m1 in range(-l, l + 1):
+                    for m2 in range(max(-l, -l - m1), min(l, l - m1) + 1):
+                        m3 = -m1 - m2
+                        s, r = _wigner3j_lll(l, m1, m2, m3)
+                        if s == 0:
+                            continue
+                        tj = mp.mpf(s.numerator) / s.denominator * mp.sqrt(mp.mpf(r.numerator) / r.denominator)
+                        for a, ca in real_parts(m1):
+                            for b, cb_ in real_parts(m2):
+                                for c, cc in real_parts(m3):
+                                    key = tuple(sorted((l + a, l + b, l + c)))
+                                    entries[key] = entries.get(key, mp.mpc(0)) + tj * ca * cb_ * cc
+            for key in sorted(entries):
+                v = entries[key]
+                if abs(v.imag) > mp.mpf(10) ** -40:
+                    raise AssertionError(f"G^{l}{key} is not real")
+                if abs(v.real) > mp.mpf(10) ** -40:
+                    idx.append(key)
+                    val.append(float(v.real))
+            off.append(len(idx))
+    out = (_boo_norm(l_max), np.asarray(off, dtype=np.int32), np.asarray(idx, dtype=np.int32).reshape(-1, 3), np.asarray(val, dtype=np.float64))
+    _BOO_TABLES[l_max] = out
+    return out
+
+
+def _boo_select(select, A: int) -> int:
+    """-> the bit mask of csrc/cells/cell_boo_math.h: bit type_i * A + type_j set where sites of type j about centres of type i are kept"""
+    if select is None:
+        return (1 << (A * A)) - 1
+    if isinstance(select, str):
+        if select != "same":
+            raise ValueError('select must be None, "same", a list of (centre type, site type) pairs or a bool [A, A] array')
+        return sum(1 << (a * A + a) for a in range(A))
+    arr = np.asarray(select.detach().cpu() if isinstance(select, torch.Tensor) else select)
+    if arr.dtype == np.bool_:
+        if arr.shape != (A, A):
+            raise ValueError(f"a bool select must be [{A}, {A}]")
+        return sum(1 << (a * A + b) for a in range(A) for b in range(A) if arr[a, b])
+    pairs = arr.reshape(-1, 2) if arr.size else np.zeros((0, 2), np.int64)
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= A):
+        raise ValueError(f"a select pair names a type outside [0, {A})")
+    return int(np.bitwise_or.reduce([1 << (int(a) * A + int(b)) for a, b in pairs], initial=0))
+
+
+class BondOrder:
+    """Bond-orientational order of M centres, rows in the caller's centre order, on the device: ``q``, ``w``, ``w_hat`` float64
+    [M, l_max+1] (Steinhardt's q_l, w_l and w_l / (sum_m q_lm^2)^(3/2)); ``q_avg``, ``w_avg``, ``w_hat_avg`` the same from the
+    Lechner-Dellago averaged q_lm (None without ``averaged``); ``n`` int32 [M], the kept sites, and ``n_solid`` int32 [M], those
+    with a solid bond; ``qlm`` float64 [M, (l_max+1)^2] in the real basis (index l^2 + l + m) or None; ``centre_cell`` /
+    ``centre_atom`` int64 [M] (atom counted inside its cell) on the host."""
+
+    def __init__(self, q, w, w_hat, q_avg, w_avg, w_hat_avg, n, n_solid, qlm, centre_cell, centre_atom):
+        self.q, self.w, self.w_hat, self.q_avg, self.w_avg, self.w_hat_avg = q, w, w_hat, q_avg, w_avg, w_hat_avg
+        self.n, self.n_solid, self.qlm, self.centre_cell, self.centre_atom = n, n_solid, qlm, centre_cell, centre_atom
+
+
+def _boo_slab(cb: _CellBatch, cutoff: float, budget: int) -> int:
+    """centres per launch under ``budget`` bytes of site lists, the sites estimated as ``_CellSoap.slab_centres`` does"""
+    vol = np.abs(np.linalg.det(cb.lattice_h.numpy().reshape(-1, 3, 3)))
+    density = float(np.max(np.asarray(cb.sizes, dtype=np.float64) / vol)) if cb.C else 0.0
+    sites = int(math.ceil(1.25 * density * 4.0 / 3.0 * math.pi * cutoff ** 3)) + 1
+    return max(1, int(budget) // (8 * sites))
+
+
+def bond_order(cells: Union[PeriodicCell, Sequence[PeriodicCell]], cutoff: float = 2.0, l_max: int = 6, centres=None, select=None,
+               averaged: bool = True, l_solid: int = 6, threshold: float = 0.7, return_qlm: bool = False, method: str = "auto", device=None,
+               _slab_bytes: Optional[int] = None) -> BondOrder:
+    """Steinhardt's bond-orientational order of atoms of periodic cells (csrc/cells/cell_boo_math.h): the neighbours of an atom are
+    its ``neighbour_sites`` at ``cutoff`` over every image, kept where ``select`` allows the pair (centre type, site type): None = all
+    pairs, "same" = equal types, a list of pairs, or a bool [A, A] array; ``select=[(1, 1)]`` is the Si sublattice of silica.
+    q_lm = mean of the real orthonormal Y_lm over the kept sites, q_l = sqrt(4 pi / (2l+1) sum_m q_lm^2), w_l the contraction with
+    the Wigner 3j symbol (exactly 0 for odd l) and w_hat_l = w_l / (sum_m q_lm^2)^(3/2); with ``averaged`` the same from
+    qbar_lm(i) = (q_lm(i) + sum over kept sites q_lm(atom)) / (1 + n_i) (Lechner and Dellago); ``n_solid`` counts the kept sites with
+    q(i).q(k) / (|q(i)| |q(k)|) > ``threshold`` at ``l_solid`` <= ``l_max`` (ten Wolde and Frenkel).  l_max <= 10.  ``centres`` and
+    ``method`` as in ``neighbour_sites``.  Pass 1 (q_lm) always covers every atom of the batch, since the averages and the solid
+    bonds read the neighbours' rows.  All fp64, every sum in one stated order: results are bitwise reproducible, the same for a cell
+    alone and in a batch, and do not depend on the slabs the site rows go through in."""
+    cb = _CellBatch(_as_cells(cells), device)
+    l_max, l_solid = int(l_max), int(l_solid)
+    if cb.A > _lib.CELL_MAX_TYPES:
+        raise ValueError(f"{cb.A} atom types (at most {_lib.CELL_MAX_TYPES})")
+    if not 0 <= l_max <= _lib.SOAP_MAX_L:
+        raise ValueError(f"l_max {l_max} outside [0, {_lib.SOAP_MAX_L}]")
+    if not 0 <= l_solid <= l_max:
+        raise ValueError(f"l_solid {l_solid} outside [0, l_max = {l_max}]")
+    cutoff = float(cutoff)
+    mask = _boo_select(select, cb.A)
+    search = _SiteSearch(cb, cutoff, method)
+    idx_h, cell_h = _centres(cb, centres)
+    M, LM, L1, dev = int(idx_h.numel()), (l_max + 1) ** 2, l_max + 1, cb.dev
+    norm_h, off_h, gidx_h, gval_h = _boo_tables(l_max)
+    norm, off = torch.from_numpy(norm_h).to(dev), torch.from_numpy(off_h).to(dev)
+    E = int(gval_h.shape[0])
+    gidx = torch.from_numpy(gidx_h).to(dev) if E else None
+    gval = torch.from_numpy(gval_h).to(dev) if E else None
+    lib = _lib.lib()
+    step = _boo_slab(cb, cutoff, _BOO_SLAB_BYTES if _slab_bytes is None else _slab_bytes)
+    head = (_lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice),
+            _lib.ptr(cb.frac), _lib.ptr(cb.types))
+
+    def rows_of(atoms_h, cells_of):
+        m = int(atoms_h.numel())
+        row_ptr, atom, code = search.rows(atoms_h, cells_of)
+        T = int(atom.shape[0])
+        who = torch.cat([atoms_h.to(torch.int32), torch.arange(m, dtype=torch.int32)]).to(dev)   # the centres, then their rows
+        return (m, _lib.ptr(row_ptr), T, _lib.ptr(atom) if T else None, _lib.ptr(code) if T else None, m, _lib.ptr(who[:m]), _lib.ptr(who[m:])), \
+            (row_ptr, atom, code, who)
+
+    all_qlm = torch.empty(max(cb.N, 1), LM, dtype=torch.float64, device=dev)[:cb.N]
+    all_n = torch.empty(max(cb.N, 1), dtype=torch.int32, device=dev)[:cb.N]
+    every, every_cell = _centres(cb, None)
+    kept_rows = None
+    for a0 in range(0, cb.N, step):   # pass 1: every atom
+        a1 = min(cb.N, a0 + step)
+        args, keep = rows_of(every[a0:a1], every_cell[a0:a1])
+        _lib.check(lib.egnn_cell_boo_qlm(*head, cutoff, mask, l_max, _lib.ptr(norm), *args, _lib.ptr(all_qlm[a0:a1]), _lib.ptr(all_n[a0:a1])))
+        if centres is None and a0 == 0 and a1 == cb.N:
+            kept_rows = (args, keep)   # one slab of every atom: pass 2 reads the same rows
+    blocks = 6 if averaged else 3
+    out = torch.empty(max(M, 1), blocks, L1, dtype=torch.float64, device=dev)[:M]
+    n = torch.empty(max(M, 1), dtype=torch.int32, device=dev)[:M]
+    n_solid = torch.empty(max(M, 1), dtype=torch.int32, device=dev)[:M]
+    for m0 in range(0, M, step):      # pass 2: the listed centres
+        m1 = min(M, m0 + step)
+        args, keep = kept_rows if kept_rows is not None else rows_of(idx_h[m0:m1], cell_h[m0:m1])
+        _lib.check(lib.egnn_cell_boo_invariants(*head, mask, l_max, _lib.ptr(all_qlm), E, _lib.host_ptr(off_h), _lib.ptr(off), _lib.ptr(gidx), _lib.ptr(gval),
+                                                l_solid, float(threshold), int(bool(averaged)), *args, _lib.ptr(out[m0:m1]), _lib.ptr(n[m0:m1]),
+                                                _lib.ptr(n_solid[m0:m1])))
+    qlm = all_qlm[idx_h.to(dev)] if return_qlm else None
+    avg = (out[:, 3], out[:, 4], out[:, 5]) if averaged else (None, None, None)
+    return BondOrder(out[:, 0], out[:, 1], out[:, 2], *avg, n, n_solid, qlm, cell_h, idx_h - cb.cell_ptr_h.long()[cell_h])
+
+
+def bond_order_profile(cells: Union[PeriodicCell, Sequence[PeriodicCell]], cutoff: float = 2.0, l_max: int = 6, select=None, l_solid: int = 6,
+                       threshold: float = 0.7, min_solid: Optional[int] = None, bins: int = 50, method: str = "auto", device=None) -> dict:
+    """Per cell and centre type, from ``bond_order`` of every atom: ``count`` int64 [C, A]; ``q_mean``, ``q_avg_mean`` and
+    ``w_hat_mean`` float64 [C, A, l_max+1], each a running fp64 sum over the centres in ascending atom order divided once by the
+    count (zeros where there is no centre); ``solid_fraction`` float64 [C, A], the share of centres with ``n_solid >= min_solid``
+    (default: all of ``n``, i.e. every kept site a solid bond; an atom without a site counts); ``q_avg_hist`` int64
+    [C, A, l_max+1, bins], histograms of qbar_l on [0, 1] (the last bin closed).  Torch ops on the arrays of ``bond_order``, not a hot
+    path; a cell gives the same values alone and in a batch."""
+    cell_list = _as_cells(cells)
+    bo = bond_order(cell_list, cutoff=cutoff, l_max=l_max, select=select, averaged=True, l_solid=l_solid, threshold=threshold, method=method,
+                    device=device)
+    C, A, L1, bins = len(cell_list), max(c.num_types for c in cell_list), int(l_max) + 1, int(bins)
+    if bins < 1:
+        raise ValueError("bins must be positive")
+    types = torch.cat([c.types for c in cell_list]).long()
+    q, q_avg, w_hat = bo.q.cpu(), bo.q_avg.cpu(), bo.w_hat.cpu()
+    n, n_solid = bo.n.cpu().long(), bo.n_solid.cpu().long()
+    solid = n_solid >= (n if min_solid is None else int(min_solid))
+    count = torch.zeros(C, A, dtype=torch.int64)
+    means = {k: torch.zeros(C, A, L1, dtype=torch.float64) for k in ("q_mean", "q_avg_mean", "w_hat_mean")}
+    frac = torch.zeros(C, A, dtype=torch.float64)
+    hist = torch.zeros(C, A, L1, bins, dtype=torch.int64)
+    for c in range(C):
+        for a in range(A):
+            rows = torch.nonzero((bo.centre_cell == c) & (types == a)).reshape(-1)   # ascending atoms
+            count[c, a] = rows.numel()
+            if rows.numel() == 0:
+                continue
+            for key, src in (("q_mean", q), ("q_avg_mean", q_avg), ("w_hat_mean", w_hat)):
+                means[key][c, a] = torch.cumsum(src[rows], 0)[-1] / float(rows.numel())   # cumsum: the running sum, in order
+            frac[c, a] = float(solid[rows].sum()) / float(rows.numel())
+            b = torch.clamp((q_avg[rows] * bins).floor().long(), 0, bins - 1)          # [m, L1]
+            hist[c, a] = torch.zeros(L1, bins, dtype=torch.int64).scatter_add_(1, b.T.contiguous(), torch.ones_like(b.T))
+    return dict(count=count, solid_fraction=frac, q_avg_hist=hist, **means)

@@ -852,6 +852,46 @@ int egnn_cell_soap_host(int C, int A, const int32_t* cell_ptr, const double* lat
 int egnn_cell_soap_mean_host(int C, int F, const int32_t* cell_rows, const double* desc, const int64_t* count, int first, int final,
                              double* sum);
 
+/* ---- bond-orientational order of periodic cells (csrc/cells/cell_boo.hip; definitions in csrc/cells/cell_boo_math.h) ------------
+ * Steinhardt's q_l, w_l and w^_l per atom, the Lechner-Dellago neighbour averages and the ten Wolde-Frenkel solid-bond count, over
+ * the sites of egnn_cell_sites_* at cut = cutoff.  No file of the reference computes them (an extension, like the rings).  A site
+ * (j, s) of centre i is KEPT where bit type_i * A + type_j of `select` is set (and it does not lie on the centre); n is the number
+ * of kept sites.  Y_lm are the real orthonormal harmonics of egnn_soap_descriptor on the unit vector (d_norm double [(l_max+1)^2]:
+ * its N_lm table), l_max <= 10, A <= 4.  All fp64; every sum is one thread's running sum in ascending order (no atomic, no
+ * reduction across lanes): the device executes the host statement's operations, results are bitwise reproducible and a cell gives
+ * the same bits in any batch.  Cells, the CSR (d_row_ptr int32 [n_rows + 1], d_site_atom, d_site_shift int32 [T]) and the centres
+ * (d_centre_atom, d_centre_row int32 [M], M >= 1) as in egnn_cell_soap_descriptor.  Bad arguments are EGNN_EINVAL with a message
+ * before anything is launched.
+ *
+ * egnn_cell_boo_qlm (pass 1): d_qlm double [M, (l_max+1)^2], row m = (sum of Y_lm over the kept sites of row d_centre_row[m],
+ * ascending) / n, zeros where n = 0; d_n int32 [M].  A width <= cutoff / 4 is refused as by egnn_cell_sites_count.
+ * egnn_cell_boo_invariants (pass 2): d_qlm double [N, (l_max+1)^2] holds the rows of EVERY atom of the batch (pass 1 with centre m =
+ * atom m).  d_out double [M, blocks, l_max+1], blocks = q, w, w^ and, with averaged != 0, qbar, wbar, wbar^ (3 or 6);
+ * q_l = sqrt(4 pi / (2l+1) sum_m q_lm^2); w_l = sum over the entries of G^l of G q_a q_b q_c, G the 3j tensor (l l l; m1 m2 m3) in
+ * the real basis for a <= b <= c with multiplicities folded in: g_off int32 [l_max + 2] (HOST copy and d_g_off), d_g_idx int32
+ * [E, 3] (a, b, c in [0, 2l]), d_g_val double [E], empty for odd l (w_l = 0); w^_l = w_l / (sum_m q_lm^2)^(3/2), 0 where the sum is
+ * 0.  qbar_lm = (q_lm(i) + sum over kept sites of q_lm(atom)) / (1 + n).  d_n int32 [M]; d_n_solid int32 [M] counts the kept sites
+ * with s_ik = q(i).q(k) / (|q(i)| |q(k)|) at l_solid strictly above threshold (0 where a norm is 0). */
+int egnn_cell_boo_qlm(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                      const double* d_lattice, const double* d_frac, const int32_t* d_type, double cutoff, unsigned select, int l_max,
+                      const double* d_norm, int n_rows, const int32_t* d_row_ptr, int T, const int32_t* d_site_atom,
+                      const int32_t* d_site_shift, int M, const int32_t* d_centre_atom, const int32_t* d_centre_row, double* d_qlm,
+                      int32_t* d_n);
+int egnn_cell_boo_invariants(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                             const double* d_lattice, const double* d_frac, const int32_t* d_type, unsigned select, int l_max,
+                             const double* d_qlm, int E, const int32_t* g_off, const int32_t* d_g_off, const int32_t* d_g_idx,
+                             const double* d_g_val, int l_solid, double threshold, int averaged, int n_rows, const int32_t* d_row_ptr, int T,
+                             const int32_t* d_site_atom, const int32_t* d_site_shift, int M, const int32_t* d_centre_atom,
+                             const int32_t* d_centre_row, double* d_out, int32_t* d_n, int32_t* d_n_solid);
+/* Host statement of the two entries above: HOST pointers, no GPU, the same definitions in plain C++.  It finds its own sites as
+ * egnn_cell_sites_host does (the box walk without a cull), computes q_lm of every atom and the invariants of the M >= 0 listed
+ * centres: out [M, blocks, l_max+1], n and n_solid int32 [M], and where given qlm double [M, (l_max+1)^2] (the centres' rows).  Also
+ * EGNN_EINVAL: a centre outside [0, N), a type outside [0, A), a coordinate that is not finite, a width <= cutoff / 4. */
+int egnn_cell_boo_host(int C, int A, const int32_t* cell_ptr, const double* lattice, const double* frac, const int32_t* type, double cutoff,
+                       unsigned select, int l_max, const double* norm, int E, const int32_t* g_off, const int32_t* g_idx, const double* g_val,
+                       int l_solid, double threshold, int averaged, int M, const int32_t* centre_atom, double* out, int32_t* n,
+                       int32_t* n_solid, double* qlm);
+
 /* ---- structure factors (csrc/eval/sq.hip; definitions in csrc/eval/sq_math.h) -----------------------------------------------
  * Reciprocal-space statistics: Debye sums of clusters and reciprocal-lattice sums of periodic cells.  No file of the reference
  * computes them (an extension, like the rings).  All sums are fp64 in one fixed order, no floating-point atomic: results are

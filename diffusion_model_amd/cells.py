@@ -120,6 +120,17 @@ def _bond_tiles(sizes) -> np.ndarray:
     return np.stack([ci, t * _lib.CELL_CENTRE_BLOCK], 1).astype(np.int32).reshape(-1, 2)
 
 
+def _empty(n: int, *shape, dtype, device) -> torch.Tensor:
+    """uninitialised [n, *shape]; a tensor of no rows still has storage behind it"""
+    t = torch.empty(max(n, 1), *shape, dtype=dtype, device=device)
+    return t if n else t[:0]   # no view in the common case: these calls run at a rate where one shows
+
+
+def _ptr_or_none(t: Optional[torch.Tensor], n: Optional[int] = None):
+    """the pointer of ``t`` for the library, None (NULL) where it holds nothing: ``n`` entries, by default its rows"""
+    return _lib.ptr(t) if (t is not None and (t.shape[0] if n is None else n)) else None
+
+
 class _CellBatch:
     """a batch of cells on the device: host and device copies of cell_ptr and the lattices, device copies of the coordinates,
     the types and the bond tiles"""
@@ -143,6 +154,16 @@ class _CellBatch:
         self.frac = torch.cat([c.frac for c in cells]).contiguous().to(dev)
         self.types = self.types_h.to(dev)
         self.tiles = torch.from_numpy(tiles).to(dev)
+        self._host_ptrs = (_lib.ptr(self.cell_ptr_h), _lib.ptr(self.lattice_h))
+        self._dev_ptrs = (_lib.ptr(self.cell_ptr), _lib.ptr(self.lattice), _ptr_or_none(self.frac, self.N), _ptr_or_none(self.types, self.N))
+
+    def args(self, A: bool = False, lattice=True, frac: bool = True, types: bool = False, host=(), dev=()):
+        """the argument prefix the entries of include/egnn_amd.h share: (stream, C, N[, A], the HOST copies cell_ptr[, lattice],
+        *host, the device arrays cell_ptr[, lattice], *dev[, frac][, types]).  ``lattice``: True, False, or "host" for an entry
+        that reads no lattice on the device; ``host`` / ``dev``: what an entry takes right after the two groups (grids, plans)."""
+        hp, dp = self._host_ptrs, self._dev_ptrs   # taken once: the entries are called at a rate where building them shows
+        return ((_lib.stream_ptr(), self.C, self.N) + ((self.A,) if A else ()) + (hp if lattice else hp[:1]) + tuple(host) +
+                (dp[:2] if lattice is True else dp[:1]) + tuple(dev) + (dp[2:3] if frac else ()) + (dp[3:] if types else ()))
 
 
 # ---- linked-cell search (csrc/cells/cell_grid.hip) ---------------------------------------------------------------------------------
@@ -164,11 +185,23 @@ def _check_method(method: str) -> str:
     return method
 
 
-def _widths(lattice) -> np.ndarray:
-    """perpendicular widths of one cell, for messages"""
-    a, b, c = np.asarray(lattice, dtype=np.float64).reshape(3, 3)
-    det = abs(float(np.dot(a, np.cross(b, c))))
-    return np.array([det / np.linalg.norm(np.cross(b, c)), det / np.linalg.norm(np.cross(c, a)), det / np.linalg.norm(np.cross(a, b))])
+def _widths(lattice):
+    """cell_widths (csrc/cells/cell_math.h) restated in numpy, for messages and work lists only: lattices [..., 3, 3] -> (the
+    perpendicular widths float64 [C, 3], singular bool [C]: |det| <= 1e-9 |a||b||c| or not finite; its widths mean nothing)"""
+    L = np.asarray(lattice, dtype=np.float64).reshape(-1, 3, 3)
+    det, faces = _width_parts(L, (0, 1, 2))
+    scale = np.prod(np.linalg.norm(L, axis=2), axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = det[:, None] / np.stack(faces, 1)
+    return w, ~(scale < 1e300) | ~(det > 1e-9 * scale)
+
+
+def _width_parts(L: np.ndarray, axes):
+    """lattices [C, 3, 3] -> (|det| [C], the face areas |a_{k+1} x a_{k+2}| [C] of the axes k asked for): w_k = |det| / face_k.
+    The work lists are built on every call and ask for the one axis they need."""
+    cross = {k: np.cross(L[:, (k + 1) % 3], L[:, (k + 2) % 3]) for k in set(axes) | {0}}
+    det = np.abs(np.einsum("ck,ck->c", L[:, 0], cross[0]))
+    return det, [np.linalg.norm(cross[k], axis=1) for k in axes]
 
 
 def _grid_cells(cb: "_CellBatch", method: str, radius: float, reach: int, min_width: float) -> Optional[np.ndarray]:
@@ -184,7 +217,7 @@ def _grid_cells(cb: "_CellBatch", method: str, radius: float, reach: int, min_wi
     if method == "grid":
         if not ok.all():
             c = int(np.nonzero(~ok)[0][0])
-            w = _widths(cb.lattice_h[c].numpy())
+            w = _widths(cb.lattice_h[c].numpy())[0][0]
             raise ValueError(f"cell {c}: perpendicular widths {w[0]:.6g}, {w[1]:.6g}, {w[2]:.6g} A hold fewer than {2 * int(reach) + 1} bins of "
                              f"{max(float(radius) / int(reach), float(min_width)):.6g} A on an axis: not griddable at radius {float(radius):.6g} "
                              f"and reach {int(reach)} (use method='direct' or 'auto')")
@@ -210,29 +243,28 @@ class _CellGrid:
             raise ValueError("more than 2^31 - 2 bins in the batch (fewer cells per call)")
         self.n_bins = B = int(bin_ptr[-1])
         self.nb, self.bin_ptr = self.nb_h.to(dev), torch.from_numpy(bin_ptr.astype(np.int32)).to(dev)
-        atom_bin = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
-        bin_count = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
-        head = (_lib.stream_ptr(), cb.C, N, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(self.nb_h), self.radius, self.reach,
-                _lib.ptr(cb.cell_ptr), _lib.ptr(self.nb), _lib.ptr(self.bin_ptr), _lib.ptr(cb.frac) if N else None)
-        _lib.check(lib.egnn_cell_grid_count(*head, B, _lib.ptr(atom_bin) if N else None, _lib.ptr(bin_count) if B else None))
+        self.atom_bin = atom_bin = _empty(N, dtype=torch.int32, device=dev)
+        bin_count = _empty(B, dtype=torch.int32, device=dev)
+        head = cb.args(lattice="host", host=(_lib.ptr(self.nb_h), self.radius, self.reach), dev=(_lib.ptr(self.nb), _lib.ptr(self.bin_ptr)))
+        _lib.check(lib.egnn_cell_grid_count(*head, B, _ptr_or_none(atom_bin), _ptr_or_none(bin_count)))
         self.bin_start = torch.zeros(B + 1, dtype=torch.int32, device=dev)
         if B:
-            self.bin_start[1:] = torch.cumsum(bin_count[:B].long(), 0).to(torch.int32)
-        work = torch.empty(max(B + N, 1), dtype=torch.int32, device=dev)
+            self.bin_start[1:] = torch.cumsum(bin_count.long(), 0).to(torch.int32)
+        work = _empty(B + N, dtype=torch.int32, device=dev)
+        # the walking kernels index the sorted arrays: they keep their storage where N = 0
         self.sorted_atom = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
         self.sorted_frac = torch.empty(max(N, 1), 3, dtype=torch.float64, device=dev)
         self.sorted_type = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
-        _lib.check(lib.egnn_cell_grid_fill(*head, _lib.ptr(cb.types) if N else None, B, _lib.ptr(self.bin_start), _lib.ptr(atom_bin) if N else None,
-                                           _lib.ptr(work), *((_lib.ptr(t) if N else None) for t in (self.sorted_atom, self.sorted_frac, self.sorted_type))))
-        self.atom_bin = atom_bin[:N]
+        _lib.check(lib.egnn_cell_grid_fill(*head, _ptr_or_none(cb.types, N), B, _lib.ptr(self.bin_start), _ptr_or_none(atom_bin), _lib.ptr(work),
+                                           *(_ptr_or_none(t, N) for t in (self.sorted_atom, self.sorted_frac, self.sorted_type))))
         self.tiles_h = torch.from_numpy(_bond_tiles(np.where(self.mask, np.asarray(cb.sizes, dtype=np.int64), 0)))
         self.n_tiles, self.tiles = len(self.tiles_h), self.tiles_h.to(dev)
 
-    def args(self, cb: "_CellBatch"):
-        """the arguments the walking entries share after (stream, C, N[, A]): the HOST copies, then the device arrays up to n_bins
-        and bin_start"""
-        return (_lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(self.nb_h), _lib.ptr(self.tiles_h) if self.n_tiles else None,
-                _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice), _lib.ptr(self.nb), _lib.ptr(self.bin_ptr), self.n_bins, _lib.ptr(self.bin_start))
+    def args(self, cb: "_CellBatch", A: bool = False):
+        """the arguments the walking entries share: the batch's prefix with the HOST copies of the grids and tiles, and the device
+        arrays up to n_bins and bin_start"""
+        return cb.args(A=A, frac=False, host=(_lib.ptr(self.nb_h), _ptr_or_none(self.tiles_h)),
+                       dev=(_lib.ptr(self.nb), _lib.ptr(self.bin_ptr), self.n_bins, _lib.ptr(self.bin_start)))
 
 
 class BondList:
@@ -260,13 +292,11 @@ def decode_shift(code: torch.Tensor) -> torch.Tensor:
 
 def _bond_args(cb: _CellBatch, cutoff: float, tiles: Optional[torch.Tensor] = None):
     tiles = cb.tiles if tiles is None else tiles
-    return (_lib.stream_ptr(), cb.C, cb.N, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice),
-            _lib.ptr(cb.frac), float(cutoff), _lib.ptr(tiles) if len(tiles) else None, len(tiles))
+    return (*cb.args(), float(cutoff), _ptr_or_none(tiles), len(tiles))
 
 
 def _grid_bond_args(cb: _CellBatch, grid: _CellGrid, cutoff: float):
-    return (_lib.stream_ptr(), cb.C, cb.N, *grid.args(cb), _lib.ptr(grid.sorted_atom), _lib.ptr(grid.sorted_frac), float(cutoff), grid.reach,
-            _lib.ptr(grid.tiles) if grid.n_tiles else None, grid.n_tiles)
+    return (*grid.args(cb), _lib.ptr(grid.sorted_atom), _lib.ptr(grid.sorted_frac), float(cutoff), grid.reach, _ptr_or_none(grid.tiles), grid.n_tiles)
 
 
 def _bonds_count(cb: _CellBatch, cutoff: float) -> torch.Tensor:
@@ -276,10 +306,8 @@ def _bonds_count(cb: _CellBatch, cutoff: float) -> torch.Tensor:
 
 
 def _bonds_fill(cb: _CellBatch, cutoff: float, row_ptr: torch.Tensor, E: int):
-    atom = torch.empty(max(E, 1), dtype=torch.int32, device=cb.dev)[:E]
-    code = torch.empty(max(E, 1), dtype=torch.int32, device=cb.dev)[:E]
-    _lib.check(_lib.lib().egnn_cell_bonds_fill(*_bond_args(cb, cutoff), _lib.ptr(row_ptr), E, _lib.ptr(atom) if E else None,
-                                               _lib.ptr(code) if E else None))
+    atom, code = (_empty(E, dtype=torch.int32, device=cb.dev) for _ in range(2))
+    _lib.check(_lib.lib().egnn_cell_bonds_fill(*_bond_args(cb, cutoff), _lib.ptr(row_ptr), E, _ptr_or_none(atom), _ptr_or_none(code)))
     return atom, code
 
 
@@ -311,9 +339,8 @@ def _bond_list(cb: _CellBatch, cutoff: float, method: str = "direct", reach: int
         _lib.check(lib.egnn_cell_bonds_count(*_bond_args(cb, cutoff, direct), _lib.ptr(deg)))   # zeroes every degree, then its own centres
     _lib.check(lib.egnn_cell_bonds_grid_count(*_grid_bond_args(cb, grid, cutoff), _lib.ptr(deg)))
     row_ptr, E = _row_ptr(cb, deg)
-    atom = torch.empty(max(E, 1), dtype=torch.int32, device=cb.dev)[:E]
-    code = torch.empty(max(E, 1), dtype=torch.int32, device=cb.dev)[:E]
-    lists = (_lib.ptr(row_ptr), E, _lib.ptr(atom) if E else None, _lib.ptr(code) if E else None)
+    atom, code = (_empty(E, dtype=torch.int32, device=cb.dev) for _ in range(2))
+    lists = (_lib.ptr(row_ptr), E, _ptr_or_none(atom), _ptr_or_none(code))
     if len(direct):
         _lib.check(lib.egnn_cell_bonds_fill(*_bond_args(cb, cutoff, direct), *lists))
     _lib.check(lib.egnn_cell_bonds_grid_fill(*_grid_bond_args(cb, grid, cutoff), *lists))
@@ -324,26 +351,23 @@ def _env_args(cb: _CellBatch, bonds: BondList, cc: torch.Tensor, shells: int, ma
     """the arguments the two environment entries share after the cell arrays: the bond list, the centres ``cc`` int32 [2, M] =
     (cell, atom) on the device, shells, max_atoms"""
     E, M = bonds.num_bonds, int(cc.shape[1])
-    return (_lib.ptr(bonds.row_ptr), E, _lib.ptr(bonds.atom) if E else None, _lib.ptr(bonds.shift_code) if E else None, M,
-            _lib.ptr(cc[0]) if M else None, _lib.ptr(cc[1]) if M else None, int(shells), int(max_atoms))
+    return (_lib.ptr(bonds.row_ptr), E, _ptr_or_none(bonds.atom, E), _ptr_or_none(bonds.shift_code, E), M, _ptr_or_none(cc[0], M),
+            _ptr_or_none(cc[1], M), int(shells), int(max_atoms))
 
 
 def _env_count(cb: _CellBatch, bonds: BondList, cc: torch.Tensor, shells: int, max_atoms: int) -> torch.Tensor:
     M = int(cc.shape[1])
-    size = torch.empty(max(M, 1), dtype=torch.int32, device=cb.dev)[:M]
-    _lib.check(_lib.lib().egnn_cell_env_count(_lib.stream_ptr(), cb.C, cb.N, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.cell_ptr),
-                                              *_env_args(cb, bonds, cc, shells, max_atoms), _lib.ptr(size) if M else None))
+    size = _empty(M, dtype=torch.int32, device=cb.dev)
+    _lib.check(_lib.lib().egnn_cell_env_count(*cb.args(lattice=False, frac=False), *_env_args(cb, bonds, cc, shells, max_atoms), _ptr_or_none(size, M)))
     return size
 
 
 def _env_fill(cb: _CellBatch, bonds: BondList, cc: torch.Tensor, shells: int, max_atoms: int, env_ptr: torch.Tensor, T: int):
     """-> (atom, shift code, type: int32 [T]; pos float32 [T, 3])"""
-    e_atom, e_code, e_type = (torch.empty(max(T, 1), dtype=torch.int32, device=cb.dev)[:T] for _ in range(3))
-    pos = torch.empty(max(T, 1), 3, dtype=torch.float32, device=cb.dev)[:T]
-    _lib.check(_lib.lib().egnn_cell_env_fill(_lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h),
-                                             _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice), _lib.ptr(cb.frac), _lib.ptr(cb.types),
-                                             *_env_args(cb, bonds, cc, shells, max_atoms), _lib.ptr(env_ptr), T,
-                                             *((_lib.ptr(t) if T else None) for t in (e_atom, e_code, e_type, pos))))
+    e_atom, e_code, e_type = (_empty(T, dtype=torch.int32, device=cb.dev) for _ in range(3))
+    pos = _empty(T, 3, dtype=torch.float32, device=cb.dev)
+    _lib.check(_lib.lib().egnn_cell_env_fill(*cb.args(A=True, types=True), *_env_args(cb, bonds, cc, shells, max_atoms), _lib.ptr(env_ptr), T,
+                                             *(_ptr_or_none(t, T) for t in (e_atom, e_code, e_type, pos))))
     return e_atom, e_code, e_type, pos
 
 
@@ -524,19 +548,17 @@ class _SqCellRun:
         self.vec_ptr, self.row_ptr = self.vec_ptr_h.to(cb.dev), row_ptr64.to(torch.int32)
         tiles_h = _sq_vector_tiles(self.counts)
         self.n_tiles, self.tiles = len(tiles_h), torch.from_numpy(tiles_h).to(cb.dev)
-        self.hkl = torch.empty(max(K, 1), 3, dtype=torch.int32, device=cb.dev)[:K]
-        self.kabs = torch.empty(max(K, 1), dtype=torch.float64, device=cb.dev)[:K]
-        self.bins = torch.empty(max(K, 1), dtype=torch.int32, device=cb.dev)[:K]
-        self.rho_out = torch.empty(max(K, 1), cb.A, 2, dtype=torch.float64, device=cb.dev)[:K]
+        self.hkl = _empty(K, 3, dtype=torch.int32, device=cb.dev)
+        self.kabs = _empty(K, dtype=torch.float64, device=cb.dev)
+        self.bins = _empty(K, dtype=torch.int32, device=cb.dev)
+        self.rho_out = _empty(K, cb.A, 2, dtype=torch.float64, device=cb.dev)
 
     def rho(self):
-        cb, K = self.cb, self.K
-        _lib.check(_lib.lib().egnn_sq_cell_rho(
-            _lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(self.plan_h), _lib.ptr(self.vec_ptr_h),
-            _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice), _lib.ptr(self.plan), _lib.ptr(self.vec_ptr), _lib.ptr(cb.frac) if cb.N else None,
-            _lib.ptr(cb.types) if cb.N else None, self.q_max, self.dq, self.nbins, self.n_rows, _lib.ptr(self.row_ptr), K,
-            _lib.ptr(self.tiles) if self.n_tiles else None, self.n_tiles, _lib.ptr(self.hkl) if K else None, _lib.ptr(self.kabs) if K else None,
-            _lib.ptr(self.bins) if K else None, _lib.ptr(self.rho_out) if K else None))
+        cb = self.cb
+        head = cb.args(A=True, types=True, host=(_lib.ptr(self.plan_h), _lib.ptr(self.vec_ptr_h)), dev=(_lib.ptr(self.plan), _lib.ptr(self.vec_ptr)))
+        _lib.check(_lib.lib().egnn_sq_cell_rho(*head, self.q_max, self.dq, self.nbins, self.n_rows, _lib.ptr(self.row_ptr), self.K,
+                                               _ptr_or_none(self.tiles), self.n_tiles,
+                                               *(_ptr_or_none(t) for t in (self.hkl, self.kabs, self.bins, self.rho_out))))
 
     def shells(self):
         cb, K, A, nbins = self.cb, self.K, self.cb.A, self.nbins
@@ -544,8 +566,8 @@ class _SqCellRun:
         mean_k = torch.empty(cb.C, nbins, dtype=torch.float64, device=cb.dev)
         s = torch.empty(cb.C, A, A, nbins, dtype=torch.float64, device=cb.dev)
         _lib.check(_lib.lib().egnn_sq_cell_shells(_lib.stream_ptr(), cb.C, A, nbins, _lib.ptr(self.vec_ptr_h), _lib.ptr(self.vec_ptr), K,
-                                                  _lib.ptr(self.kabs) if K else None, _lib.ptr(self.bins) if K else None,
-                                                  _lib.ptr(self.rho_out) if K else None, _lib.ptr(count), _lib.ptr(mean_k), _lib.ptr(s)))
+                                                  *(_ptr_or_none(t) for t in (self.kabs, self.bins, self.rho_out)), _lib.ptr(count),
+                                                  _lib.ptr(mean_k), _lib.ptr(s)))
         return count, mean_k, s
 
 
@@ -632,11 +654,9 @@ def _pair_nbins(R: float, dR: float) -> int:
 def _image_boxes(cb: _CellBatch, dR: float, nbins: int) -> np.ndarray:
     """S_0 = ceil(nbins dR / w_0) per cell, for the work list only (the library takes the box from its own arithmetic and refuses
     a cell it finds too wide or singular): clipped to [0, 16]"""
-    L = cb.lattice_h.numpy().reshape(-1, 3, 3)
-    bc = np.cross(L[:, 1], L[:, 2])
-    det = np.abs(np.einsum("ck,ck->c", L[:, 0], bc))
     with np.errstate(divide="ignore", invalid="ignore"):
-        s = np.ceil(nbins * dR * np.linalg.norm(bc, axis=1) / det)
+        det, (face,) = _width_parts(cb.lattice_h.numpy().reshape(-1, 3, 3), (0,))
+        s = np.ceil(nbins * dR * face / det)
     return np.clip(np.nan_to_num(s, nan=0.0, posinf=_lib.CELL_STAT_MAX_IMAGES), 0, _lib.CELL_STAT_MAX_IMAGES).astype(np.int64)
 
 
@@ -653,17 +673,14 @@ def _pair_counts(cb: _CellBatch, dR: float, nbins: int, tiles: Optional[torch.Te
         tiles = torch.from_numpy(_pair_tiles(direct_sizes, _image_boxes(cb, dR, nbins))).to(cb.dev)
     counts = torch.empty(cb.C, cb.A, cb.A, max(nbins, 1), dtype=torch.int64, device=cb.dev)
     if nb is None or len(tiles):
-        _lib.check(_lib.lib().egnn_cell_pair_counts(_lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h),
-                                                    _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice), _lib.ptr(cb.frac) if cb.N else None,
-                                                    _lib.ptr(cb.types) if cb.N else None, float(dR), int(nbins),
-                                                    _lib.ptr(tiles) if len(tiles) else None, len(tiles), _lib.ptr(counts)))
+        _lib.check(_lib.lib().egnn_cell_pair_counts(*cb.args(A=True, types=True), float(dR), int(nbins), _ptr_or_none(tiles), len(tiles),
+                                                    _lib.ptr(counts)))
     else:
         counts.zero_()
     if nb is not None:
         grid = _CellGrid(cb, nb, nbins * float(dR), reach)
-        _lib.check(_lib.lib().egnn_cell_pair_counts_grid(_lib.stream_ptr(), cb.C, cb.N, cb.A, *grid.args(cb), _lib.ptr(grid.sorted_frac),
-                                                         _lib.ptr(grid.sorted_type), float(dR), int(nbins), grid.reach,
-                                                         _lib.ptr(grid.tiles) if grid.n_tiles else None, grid.n_tiles, _lib.ptr(counts)))
+        _lib.check(_lib.lib().egnn_cell_pair_counts_grid(*grid.args(cb, A=True), _lib.ptr(grid.sorted_frac), _lib.ptr(grid.sorted_type), float(dR),
+                                                         int(nbins), grid.reach, _ptr_or_none(grid.tiles), grid.n_tiles, _lib.ptr(counts)))
     return counts
 
 
@@ -675,18 +692,16 @@ def _bond_stats(cb: _CellBatch, bonds: BondList, dtheta: float, max_cn: int, for
     A, C, N, E, ncn = cb.A, cb.C, cb.N, bonds.num_bonds, max(max_cn, 0) + 1
     if tiles is None:
         tiles = torch.from_numpy(_stat_bond_tiles(cb.sizes)).to(cb.dev)
-    coordination = torch.empty(max(N, 1), A, dtype=torch.int32, device=cb.dev)[:N]
-    qn = torch.empty(max(N, 1), dtype=torch.int32, device=cb.dev)[:N]
+    coordination = _empty(N, A, dtype=torch.int32, device=cb.dev)
+    qn = _empty(N, dtype=torch.int32, device=cb.dev)
     cn = torch.empty(C, A, A, ncn, dtype=torch.int64, device=cb.dev)
     ang = torch.empty(C, A, A * (A + 1) // 2, max(nth, 1), dtype=torch.int64, device=cb.dev)
     qn_hist = torch.empty(C, ncn, dtype=torch.int64, device=cb.dev)
     over = torch.empty(C, dtype=torch.int32, device=cb.dev)
     _lib.check(_lib.lib().egnn_cell_bond_stats(
-        _lib.stream_ptr(), C, N, A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice),
-        _lib.ptr(cb.frac) if N else None, _lib.ptr(cb.types) if N else None, _lib.ptr(bonds.row_ptr), E, _lib.ptr(bonds.atom) if E else None,
-        _lib.ptr(bonds.shift_code) if E else None, dtheta, max_cn, int(former), int(bridge), _lib.ptr(tiles) if len(tiles) else None,
-        len(tiles), _lib.ptr(coordination) if N else None, _lib.ptr(cn), _lib.ptr(ang), _lib.ptr(qn) if N else None, _lib.ptr(qn_hist),
-        _lib.ptr(over)))
+        *cb.args(A=True, types=True), _lib.ptr(bonds.row_ptr), E, _ptr_or_none(bonds.atom), _ptr_or_none(bonds.shift_code), dtheta, max_cn,
+        int(former), int(bridge), _ptr_or_none(tiles), len(tiles), _ptr_or_none(coordination), _lib.ptr(cn), _lib.ptr(ang), _ptr_or_none(qn),
+        _lib.ptr(qn_hist), _lib.ptr(over)))
     return coordination, cn, ang, qn, qn_hist, over
 
 
@@ -882,12 +897,10 @@ def _check_site_boxes(cb: _CellBatch, radius: float):
     floor(radius / w_k) + 1 must stay within 4, the range of the shift code"""
     if not (math.isfinite(radius) and radius > 0.0):
         raise ValueError("the radius must be positive and finite")
-    for c in range(cb.C):
-        L = cb.lattice_h[c].numpy().reshape(3, 3)
-        scale = float(np.prod(np.linalg.norm(L, axis=1)))
-        if not (scale < 1e300) or not abs(float(np.linalg.det(L))) > 1e-9 * scale:
+    widths, singular = _widths(cb.lattice_h.numpy())
+    for c, w in enumerate(widths):
+        if singular[c]:
             raise ValueError(f"cell {c}: singular lattice")
-        w = _widths(L)
         if not bool(np.all(np.floor(radius / w) + 1.0 <= _lib.CELL_SOAP_MAX_BOX)):
             raise ValueError(f"cell {c}: perpendicular widths {w[0]:.6g}, {w[1]:.6g}, {w[2]:.6g} A and one is at most radius / 4 = "
                              f"{radius / 4:.6g} A: its sites need more than {_lib.CELL_SOAP_MAX_BOX} images to a side (use a supercell)")
@@ -926,8 +939,7 @@ class _SiteSearch:
         lib = _lib.lib()
         gridded = torch.zeros(m, dtype=torch.bool) if self.grid_mask is None else self.grid_mask[cell_h]
         direct = torch.where(gridded, torch.full_like(idx_h, -1), idx_h).to(torch.int32).to(dev)   # -1: an empty row from the site kernels
-        head = (_lib.stream_ptr(), cb.C, cb.N, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice),
-                _lib.ptr(cb.frac) if cb.N else None, self.radius, m, _lib.ptr(direct) if m else None)
+        head = (*cb.args(), self.radius, m, _ptr_or_none(direct))
         deg = torch.zeros(max(m, 1), dtype=torch.int32, device=dev)[:m]
         any_direct = bool((~gridded).any())
         if any_direct:
@@ -948,8 +960,7 @@ class _SiteSearch:
         if T >= 2 ** 31:
             raise ValueError(f"more than 2^31 - 1 sites in one slab of {m} centres (lower the slab budget or the radius)")
         row_ptr32 = row_ptr.to(torch.int32)
-        atom = torch.empty(max(T, 1), dtype=torch.int32, device=dev)[:T]
-        code = torch.empty(max(T, 1), dtype=torch.int32, device=dev)[:T]
+        atom, code = (_empty(T, dtype=torch.int32, device=dev) for _ in range(2))
         if any_direct and T:
             _lib.check(lib.egnn_cell_sites_fill(*head, _lib.ptr(row_ptr32), T, _lib.ptr(atom), _lib.ptr(code)))
         if bool(gridded.any()) and int(glen.sum()):
@@ -978,6 +989,24 @@ def neighbour_sites(cells: Union[PeriodicCell, Sequence[PeriodicCell]], radius: 
     return SiteList(row_ptr, atom, code, cell_h, idx_h - cb.cell_ptr_h.long()[cell_h])
 
 
+def _slab_sites(cb: _CellBatch, radius: float) -> int:
+    """the sites about one centre inside ``radius``, estimated from the densest cell's number density with a quarter to spare:
+    what the slabs of the SOAP and bond-order launches are sized by"""
+    vol = np.abs(np.linalg.det(cb.lattice_h.numpy().reshape(-1, 3, 3)))
+    density = float(np.max(np.asarray(cb.sizes, dtype=np.float64) / vol)) if cb.C else 0.0
+    return int(math.ceil(1.25 * density * 4.0 / 3.0 * math.pi * radius ** 3)) + 1
+
+
+def _row_args(search: _SiteSearch, atoms_h: torch.Tensor, cells_of: torch.Tensor):
+    """the site rows of centres ``atoms_h`` as the entries over a site CSR take them -> ((n_rows, row_ptr, T, site atom, site shift, M,
+    centre atom, centre row), the tensors behind the pointers): row m is centre m's"""
+    m = int(atoms_h.numel())
+    row_ptr, atom, code = search.rows(atoms_h, cells_of)
+    who = torch.cat([atoms_h.to(torch.int32), torch.arange(m, dtype=torch.int32)]).to(search.cb.dev)   # one upload: the centres, then their rows
+    return (m, _lib.ptr(row_ptr), int(atom.shape[0]), _ptr_or_none(atom), _ptr_or_none(code), m, _lib.ptr(who[:m]), _lib.ptr(who[m:])), \
+        (row_ptr, atom, code, who)
+
+
 class _CellSoap:
     """one batch of cells, one basis, one cut: the site search and the descriptor launches of slabs of centres"""
 
@@ -997,26 +1026,16 @@ class _CellSoap:
 
     def slab_centres(self, coefficients: bool, budget: int) -> int:
         """centres per launch under ``budget`` bytes: descriptor row, coefficients, and the estimated sites of one centre"""
-        cb = self.cb
-        vol = np.abs(np.linalg.det(cb.lattice_h.numpy().reshape(-1, 3, 3)))
-        density = float(np.max(np.asarray(cb.sizes, dtype=np.float64) / vol)) if cb.C else 0.0
-        sites = int(math.ceil(1.25 * density * 4.0 / 3.0 * math.pi * self.cut ** 3)) + 1
-        per = 8 * self.F + (8 * int(np.prod(self.coeff_shape)) if coefficients else 0) + 8 * sites
+        per = 8 * self.F + (8 * int(np.prod(self.coeff_shape)) if coefficients else 0) + 8 * _slab_sites(self.cb, self.cut)
         return max(1, int(budget) // per)
 
     def describe(self, idx_h, cell_h, desc, coeff):
         """the descriptors of one slab of centres into ``desc`` [m, F] (and ``coeff``)"""
-        cb, m = self.cb, int(idx_h.numel())
-        if m == 0:
+        if int(idx_h.numel()) == 0:
             return
-        row_ptr, atom, code = self.search.rows(idx_h, cell_h)
-        T = int(atom.shape[0])
-        who = torch.cat([idx_h.to(torch.int32), torch.arange(m, dtype=torch.int32)]).to(cb.dev)   # one upload: the centres, then their rows
-        _lib.check(_lib.lib().egnn_cell_soap_descriptor(
-            _lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice),
-            _lib.ptr(cb.frac), _lib.ptr(cb.types), self.basis.n_max, self.basis.l_max, _lib.ptr(self.tables), m, _lib.ptr(row_ptr), T,
-            _lib.ptr(atom) if T else None, _lib.ptr(code) if T else None, m, _lib.ptr(who[:m]), _lib.ptr(who[m:]), _lib.ptr(desc),
-            _lib.ptr(coeff)))
+        rows, keep = _row_args(self.search, idx_h, cell_h)
+        _lib.check(_lib.lib().egnn_cell_soap_descriptor(*self.cb.args(A=True, types=True), self.basis.n_max, self.basis.l_max, _lib.ptr(self.tables),
+                                                        *rows, _lib.ptr(desc), _lib.ptr(coeff)))
 
 
 def soap_descriptors(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centres=None, basis=None, neighbour_cut=None,
@@ -1033,8 +1052,8 @@ def soap_descriptors(cells: Union[PeriodicCell, Sequence[PeriodicCell]], centres
     cb = run.cb
     idx_h, cell_h = _centres(cb, centres)
     M = int(idx_h.numel())
-    desc = torch.empty(max(M, 1), run.F, dtype=torch.float64, device=cb.dev)[:M]
-    coeff = torch.empty(max(M, 1), *run.coeff_shape, dtype=torch.float64, device=cb.dev)[:M] if return_coefficients else None
+    desc = _empty(M, run.F, dtype=torch.float64, device=cb.dev)
+    coeff = _empty(M, *run.coeff_shape, dtype=torch.float64, device=cb.dev) if return_coefficients else None
     step = run.slab_centres(return_coefficients, _SOAP_SLAB_BYTES if _slab_bytes is None else _slab_bytes)
     for m0 in range(0, M, step):
         m1 = min(M, m0 + step)
@@ -1201,14 +1220,6 @@ class BondOrder:
         self.n, self.n_solid, self.qlm, self.centre_cell, self.centre_atom = n, n_solid, qlm, centre_cell, centre_atom
 
 
-def _boo_slab(cb: _CellBatch, cutoff: float, budget: int) -> int:
-    """centres per launch under ``budget`` bytes of site lists, the sites estimated as ``_CellSoap.slab_centres`` does"""
-    vol = np.abs(np.linalg.det(cb.lattice_h.numpy().reshape(-1, 3, 3)))
-    density = float(np.max(np.asarray(cb.sizes, dtype=np.float64) / vol)) if cb.C else 0.0
-    sites = int(math.ceil(1.25 * density * 4.0 / 3.0 * math.pi * cutoff ** 3)) + 1
-    return max(1, int(budget) // (8 * sites))
-
-
 def bond_order(cells: Union[PeriodicCell, Sequence[PeriodicCell]], cutoff: float = 2.0, l_max: int = 6, centres=None, select=None,
                averaged: bool = True, l_solid: int = 6, threshold: float = 0.7, return_qlm: bool = False, method: str = "auto", device=None,
                _slab_bytes: Optional[int] = None) -> BondOrder:
@@ -1241,35 +1252,25 @@ def bond_order(cells: Union[PeriodicCell, Sequence[PeriodicCell]], cutoff: float
     gidx = torch.from_numpy(gidx_h).to(dev) if E else None
     gval = torch.from_numpy(gval_h).to(dev) if E else None
     lib = _lib.lib()
-    step = _boo_slab(cb, cutoff, _BOO_SLAB_BYTES if _slab_bytes is None else _slab_bytes)
-    head = (_lib.stream_ptr(), cb.C, cb.N, cb.A, _lib.ptr(cb.cell_ptr_h), _lib.ptr(cb.lattice_h), _lib.ptr(cb.cell_ptr), _lib.ptr(cb.lattice),
-            _lib.ptr(cb.frac), _lib.ptr(cb.types))
-
-    def rows_of(atoms_h, cells_of):
-        m = int(atoms_h.numel())
-        row_ptr, atom, code = search.rows(atoms_h, cells_of)
-        T = int(atom.shape[0])
-        who = torch.cat([atoms_h.to(torch.int32), torch.arange(m, dtype=torch.int32)]).to(dev)   # the centres, then their rows
-        return (m, _lib.ptr(row_ptr), T, _lib.ptr(atom) if T else None, _lib.ptr(code) if T else None, m, _lib.ptr(who[:m]), _lib.ptr(who[m:])), \
-            (row_ptr, atom, code, who)
-
-    all_qlm = torch.empty(max(cb.N, 1), LM, dtype=torch.float64, device=dev)[:cb.N]
-    all_n = torch.empty(max(cb.N, 1), dtype=torch.int32, device=dev)[:cb.N]
+    # centres per launch under the budget in bytes of site lists
+    step = max(1, int(_BOO_SLAB_BYTES if _slab_bytes is None else _slab_bytes) // (8 * _slab_sites(cb, cutoff)))
+    head = cb.args(A=True, types=True)
+    all_qlm = _empty(cb.N, LM, dtype=torch.float64, device=dev)
+    all_n = _empty(cb.N, dtype=torch.int32, device=dev)
     every, every_cell = _centres(cb, None)
     kept_rows = None
     for a0 in range(0, cb.N, step):   # pass 1: every atom
         a1 = min(cb.N, a0 + step)
-        args, keep = rows_of(every[a0:a1], every_cell[a0:a1])
+        args, keep = _row_args(search, every[a0:a1], every_cell[a0:a1])
         _lib.check(lib.egnn_cell_boo_qlm(*head, cutoff, mask, l_max, _lib.ptr(norm), *args, _lib.ptr(all_qlm[a0:a1]), _lib.ptr(all_n[a0:a1])))
         if centres is None and a0 == 0 and a1 == cb.N:
             kept_rows = (args, keep)   # one slab of every atom: pass 2 reads the same rows
     blocks = 6 if averaged else 3
-    out = torch.empty(max(M, 1), blocks, L1, dtype=torch.float64, device=dev)[:M]
-    n = torch.empty(max(M, 1), dtype=torch.int32, device=dev)[:M]
-    n_solid = torch.empty(max(M, 1), dtype=torch.int32, device=dev)[:M]
+    out = _empty(M, blocks, L1, dtype=torch.float64, device=dev)
+    n, n_solid = (_empty(M, dtype=torch.int32, device=dev) for _ in range(2))
     for m0 in range(0, M, step):      # pass 2: the listed centres
         m1 = min(M, m0 + step)
-        args, keep = kept_rows if kept_rows is not None else rows_of(idx_h[m0:m1], cell_h[m0:m1])
+        args, keep = kept_rows if kept_rows is not None else _row_args(search, idx_h[m0:m1], cell_h[m0:m1])
         _lib.check(lib.egnn_cell_boo_invariants(*head, mask, l_max, _lib.ptr(all_qlm), E, _lib.host_ptr(off_h), _lib.ptr(off), _lib.ptr(gidx), _lib.ptr(gval),
                                                 l_solid, float(threshold), int(bool(averaged)), *args, _lib.ptr(out[m0:m1]), _lib.ptr(n[m0:m1]),
                                                 _lib.ptr(n_solid[m0:m1])))

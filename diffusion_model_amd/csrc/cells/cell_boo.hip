@@ -11,7 +11,7 @@
 //
 // A kernel trusts no index: centre, cell, row, site atom, shift code, type and G entry are checked against the extents of the
 // arrays before they are used.
-#include "../eval/eval_device.h"
+#include "cell_device.h"
 #include "cell_boo_host.h"
 #include "cell_boo_math.h"
 
@@ -20,41 +20,6 @@ namespace egnn {
 static_assert(kBooChunk * kBooParts == 64, "a wavefront stages kBooChunk sites with kBooParts lanes each");
 constexpr int kBooMaxLM = (kBooMaxL + 1) * (kBooMaxL + 1);
 static_assert(kBooMaxLM <= 128, "a lane holds two running sums: lm = lane and lane + 64");
-
-// the cell of batch atom i (the text of cell_soap.hip): the last c with cell_ptr[c] <= i; false unless the range is sane and holds i
-__device__ __forceinline__ bool boo_cell_of_atom(const int* __restrict__ cell_ptr, int C, int N, int i, int* cell, int* lo, int* hi) {
-  if (i < 0 || i >= N) return false;
-  int a = 0, b = C;
-  while (b - a > 1) {
-    const int mid = (a + b) / 2;
-    if (cell_ptr[mid] <= i) a = mid; else b = mid;
-  }
-  *cell = a;
-  *lo = cell_ptr[a];
-  *hi = cell_ptr[a + 1];
-  return *lo >= 0 && *hi <= N && i >= *lo && i < *hi && *hi - *lo <= kCellMaxAtoms;
-}
-
-// what both kernels read of row m: its centre, the centre's cell and lattice, the entries of its CSR row; false: no such row
-struct BooRow {
-  int i, lo, hi, e0, e1;
-  double L[9];
-};
-
-__device__ __forceinline__ bool boo_row_read(const double* __restrict__ lattice, const int* __restrict__ cell_ptr, int C, int N,
-                                             const int* __restrict__ row_ptr, int n_rows, int T, const int* __restrict__ centre_atom,
-                                             const int* __restrict__ centre_row, int m, BooRow* R) {
-  int c = 0;
-  R->i = centre_atom[m];
-  if (!boo_cell_of_atom(cell_ptr, C, N, R->i, &c, &R->lo, &R->hi)) return false;
-  const int r = centre_row[m];
-  if (r < 0 || r >= n_rows) return false;
-  R->e0 = row_ptr[r];
-  R->e1 = row_ptr[r + 1];
-  if (R->e0 < 0 || R->e1 < R->e0 || R->e1 > T) return false;
-  for (int k = 0; k < 9; ++k) R->L[k] = lattice[9 * (size_t)c + k];
-  return true;
-}
 
 // ---- pass 1: q_lm ----------------------------------------------------------------------------------------------------------------
 // The wavefront walks its row kBooChunk entries at a time.  Lane (part, slot) = (lane / 16, lane % 16) tests entry k0 + slot
@@ -75,17 +40,19 @@ __global__ __launch_bounds__(64 * kBooWaves) void cell_boo_qlm_kernel(const doub
   if (m >= M) return;   // uniform in a wavefront; no workgroup barrier follows
   const int LM = soap_lm_count(l_max), stride = boo_stride(l_max);
   double* stage = s_boo + (size_t)wave * kBooChunk * stride;
-  BooRow R;
-  const bool valid = boo_row_read(lattice, cell_ptr, C, N, row_ptr, n_rows, T, centre_atom, centre_row, m, &R);
+  CellCentreRow R;
+  const bool valid = cell_centre_row_read(cell_ptr, C, N, row_ptr, n_rows, T, centre_atom, centre_row, m, &R);
   const int slot_of = lane & (kBooChunk - 1), part = lane / kBooChunk;
   double acc0 = 0.0, acc1 = 0.0;
   int kept = 0;
   if (valid) {
+    double L[9];
+    cell_lattice_read(lattice, R.c, L);
     for (int k0 = R.e0; k0 < R.e1; k0 += kBooChunk) {   // uniform in the wavefront
       const int e = k0 + slot_of;
       bool keep = false;
       double u[3] = {0.0, 0.0, 0.0};
-      if (e < R.e1) keep = boo_site(frac, type, R.L, R.lo, R.hi, A, select, R.i, site_atom[e], site_shift[e], u);
+      if (e < R.e1) keep = boo_site(frac, type, L, R.lo, R.hi, A, select, R.i, site_atom[e], site_shift[e], u);
       const unsigned long long hits = __ballot(keep) & ((1ull << kBooChunk) - 1ull);   // the lanes of part 0: one bit a slot
       const int cnt = __popcll(hits);
       if (keep) {
@@ -127,12 +94,14 @@ __global__ __launch_bounds__(64 * kBooWaves) void cell_boo_invariants_kernel(
   if (m >= M) return;   // uniform in a wavefront; no workgroup barrier follows
   const int L1 = l_max + 1, LM = soap_lm_count(l_max), sets = averaged ? 2 : 1;
   double* o = out + (size_t)m * (3 * sets) * L1;
-  BooRow R;
-  if (!boo_row_read(lattice, cell_ptr, C, N, row_ptr, n_rows, T, centre_atom, centre_row, m, &R)) {
+  CellCentreRow R;
+  if (!cell_centre_row_read(cell_ptr, C, N, row_ptr, n_rows, T, centre_atom, centre_row, m, &R)) {
     for (int k = lane; k < 3 * sets * L1; k += 64) o[k] = 0.0;
     if (lane == 0) { n_out[m] = 0; n_solid_out[m] = 0; }
     return;
   }
+  double L[9];
+  cell_lattice_read(lattice, R.c, L);
   double* own = s_rows[wave][0];
   double* avg = s_rows[wave][1];
   double acc0 = lane < LM ? qlm[(size_t)R.i * LM + lane] : 0.0, acc1 = lane + 64 < LM ? qlm[(size_t)R.i * LM + lane + 64] : 0.0;
@@ -147,7 +116,7 @@ __global__ __launch_bounds__(64 * kBooWaves) void cell_boo_invariants_kernel(
     if (e < R.e1) {
       double u[3];
       j = site_atom[e];
-      keep = boo_site(frac, type, R.L, R.lo, R.hi, A, select, R.i, j, site_shift[e], u);
+      keep = boo_site(frac, type, L, R.lo, R.hi, A, select, R.i, j, site_shift[e], u);
     }
     const bool is_solid = keep && boo_solid(own, qlm + (size_t)j * LM, l_solid) > threshold;
     unsigned long long hits = __ballot(keep);
@@ -178,8 +147,7 @@ __global__ __launch_bounds__(64 * kBooWaves) void cell_boo_invariants_kernel(
 static int cell_boo_rows_check(const char* who, const void* d_cell_ptr, const void* d_lattice, const void* d_frac, const void* d_type,
                                int n_rows, const void* d_row_ptr, int T, const void* d_site_atom, const void* d_site_shift, int M,
                                const void* d_centre_atom, const void* d_centre_row) {
-  if (!d_cell_ptr || !d_lattice || !d_frac || !d_type || n_rows < 0 || !d_row_ptr || T < 0 || (T > 0 && (!d_site_atom || !d_site_shift)) || M < 1 ||
-      !d_centre_atom || !d_centre_row) {
+  if (!cell_rows_given(d_cell_ptr, d_lattice, d_frac, d_type, n_rows, d_row_ptr, T, d_site_atom, d_site_shift, M, d_centre_atom, d_centre_row)) {
     set_error("bad %s arguments (d_cell_ptr, d_lattice, d_frac, d_type, d_row_ptr and the centres given; n_rows >= 0 rows of T >= 0 sites; "
               "M >= 1)", who);
     return EGNN_EINVAL;

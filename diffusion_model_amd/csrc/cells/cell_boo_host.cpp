@@ -42,8 +42,7 @@ struct BooCells {
 // the kept sites of atom i in ascending (atom, shift code): f(atom, unit vector)
 template <typename F>
 void boo_walk(const BooCells& b, int i, F f) {
-  int c = 0;
-  while (b.cell_ptr[c + 1] <= i) ++c;   // empty cells skipped
+  const int c = cell_of_atom_host(b.cell_ptr, b.C, i);
   const int lo = b.cell_ptr[c], hi = b.cell_ptr[c + 1];
   const double* L = b.lattice + 9 * (size_t)c;
   int box[3];
@@ -51,9 +50,10 @@ void boo_walk(const BooCells& b, int i, F f) {
   cell_soap_box(L, b.cut, box, width);
   const int nbox = cell_soap_box_count(box);
   const double cut2 = b.cut * b.cut;
-  const double wi[3] = {cell_wrap(b.frac[3 * (size_t)i]), cell_wrap(b.frac[3 * (size_t)i + 1]), cell_wrap(b.frac[3 * (size_t)i + 2])};
+  double wi[3], wj[3];
+  cell_wrapped_read(b.frac, i, wi);
   for (int j = lo; j < hi; ++j) {
-    const double wj[3] = {cell_wrap(b.frac[3 * (size_t)j]), cell_wrap(b.frac[3 * (size_t)j + 1]), cell_wrap(b.frac[3 * (size_t)j + 2])};
+    cell_wrapped_read(b.frac, j, wj);
     for (int t = 0; t < nbox; ++t) {
       int s[3];
       double r[3], u[3];
@@ -88,15 +88,7 @@ int egnn_cell_boo_host(int C, int A, const int32_t* cell_ptr, const double* latt
   if (cutoff == 0.0) { set_error("%s: cutoff must be positive and finite", who); return EGNN_EINVAL; }
   if (int rc = cell_soap_batch_check(who, C, N, cell_ptr, lattice, cutoff)) return rc;
   if (N > 0 && (!frac || !type)) { set_error("bad %s arguments (frac and type given)", who); return EGNN_EINVAL; }
-  for (int i = 0; i < N; ++i)
-    for (int k = 0; k < 3; ++k)
-      if (!(fabs(frac[3 * (size_t)i + k]) < 1e15)) { set_error("%s: atom %d has a fractional coordinate that is not finite", who, i); return EGNN_EINVAL; }
-  if (int rc = type_range_check(who, type, 0, N, A)) return rc;
-  for (int m = 0; m < M; ++m)
-    if (centre_atom[m] < 0 || centre_atom[m] >= N) {
-      set_error("%s: centre %d is atom %d outside [0, %d)", who, m, centre_atom[m], N);
-      return EGNN_EINVAL;
-    }
+  if (int rc = cell_inputs_check(who, N, frac, type, A, M, centre_atom)) return rc;
   const int L1 = l_max + 1, LM = soap_lm_count(l_max), blocks = averaged ? 6 : 3;
   Scratch<double> all((size_t)N * LM), col((size_t)LM), acc((size_t)LM);
   if (!all.p || !col.p || !acc.p) { set_error("%s: out of memory", who); return EGNN_ENOMEM; }

@@ -43,15 +43,12 @@ EGNN_HD int boo_stride(int l_max) { return soap_lm_count(l_max) | 1; }
 // whether site (atom j, shift code) of a row of centre i is kept; u is its unit vector where it is.  lo .. hi: the centre's cell.
 EGNN_HD bool boo_site(const double* frac, const int* type, const double* L, int lo, int hi, int A, unsigned select, int i, int j, int code,
                       double* u) {
-  if (j < lo || j >= hi || code < 0 || code >= kCellShiftCodes) return false;
+  if (!cell_site_listed(lo, hi, j, code)) return false;
   const int ti = type[i], tj = type[j];
   if (ti < 0 || ti >= A || tj < 0 || tj >= A || !boo_selected(select, A, ti, tj)) return false;
-  const double wi[3] = {cell_wrap(frac[3 * (size_t)i]), cell_wrap(frac[3 * (size_t)i + 1]), cell_wrap(frac[3 * (size_t)i + 2])};
-  const double wj[3] = {cell_wrap(frac[3 * (size_t)j]), cell_wrap(frac[3 * (size_t)j + 1]), cell_wrap(frac[3 * (size_t)j + 2])};
-  int s[3];
-  double r[3];
-  cell_shift_decode(code, s);
-  cell_site_vector(wj, wi, s, L, r);
+  double wi[3], r[3];
+  cell_wrapped_read(frac, i, wi);
+  cell_listed_vector(frac, L, wi, j, code, r);
   const double d2 = cell_norm2(r);
   if (!(d2 > 0.0)) return false;
   const double d = sqrt(d2);

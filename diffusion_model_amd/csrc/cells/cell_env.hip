@@ -9,9 +9,8 @@
 //
 // A kernel trusts no index: tile, cell, centre, bond row, neighbour and shift code are checked against the extents of the arrays
 // before they are used, and every write is checked against the extent of its output.
-#include "../eval/eval_device.h"
+#include "cell_device.h"
 #include "cell_host.h"
-#include "cell_math.h"
 
 namespace egnn {
 
@@ -32,15 +31,11 @@ __global__ __launch_bounds__(256) void cell_bond_kernel(const double* __restrict
   __shared__ double s_w[3][kCellChunk];
   __shared__ int s_cnt[kCellCentreBlock];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c = tiles[2 * blockIdx.x], c0 = tiles[2 * blockIdx.x + 1];
-  if (c < 0 || c >= C) return;
-  const int lo = cell_ptr[c], hi = cell_ptr[c + 1];
-  if (lo < 0 || hi < lo || hi > N) return;
-  const int n = hi - lo;
-  if (c0 < 0 || c0 >= n) return;
-  const int nc = min(kCellCentreBlock, n - c0);
+  CellTile T;
+  if (!cell_tile_read<kCellCentreBlock>(tiles + 2 * (size_t)blockIdx.x, cell_ptr, C, N, &T)) return;
+  const int c0 = T.c0, lo = T.lo, n = T.n, nc = T.nc;
   double L[9], width[3], reach[3];
-  for (int k = 0; k < 9; ++k) L[k] = lattice[9 * (size_t)c + k];
+  cell_lattice_read(lattice, T.c, L);
   const bool regular = cell_widths(L, width);
   for (int k = 0; k < 3; ++k) reach[k] = regular ? cutoff * (1.0 + 1e-6) / width[k] : 4.0;   // 4.0: no image is skipped
   const double c2 = cutoff * cutoff;
@@ -50,17 +45,15 @@ __global__ __launch_bounds__(256) void cell_bond_kernel(const double* __restrict
   for (int j0 = 0; j0 < n; j0 += kCellChunk) {
     const int nj = min(kCellChunk, n - j0);
     __syncthreads();   // the readers of the previous chunk are done
-    for (int t = tid; t < 3 * nj; t += 256) {
-      const int a = t / 3, k = t - 3 * a;
-      s_w[k][a] = cell_wrap(frac[3 * (size_t)(lo + j0) + t]);
-    }
+    cell_chunk_stage<kCellChunk>(frac, nullptr, lo + j0, nj, tid, s_w, nullptr);
     __syncthreads();
     for (int ci = wave * per_wave; ci < ci_end; ++ci) {   // uniform in a wavefront
       const int i = lo + c0 + ci;
-      const double wi0 = cell_wrap(frac[3 * (size_t)i]), wi1 = cell_wrap(frac[3 * (size_t)i + 1]), wi2 = cell_wrap(frac[3 * (size_t)i + 2]);
+      double wi[3];
+      cell_wrapped_read(frac, i, wi);
       int cnt = s_cnt[ci];
       int row_lo = 0, row_hi = 0;
-      if (FILL) { row_lo = row_ptr[i]; row_hi = row_ptr[i + 1]; }
+      if (FILL) { row_lo = row_ptr[i]; row_hi = row_ptr[i + 1]; }   // not cell_row_read: every write below is tested against the row
       for (int jb = 0; jb < nj; jb += 64) {
         const int jj = jb + lane;
         unsigned mask = 0;
@@ -68,13 +61,13 @@ __global__ __launch_bounds__(256) void cell_bond_kernel(const double* __restrict
           const bool self = j0 + jj == c0 + ci;
           const double wj0 = s_w[0][jj], wj1 = s_w[1][jj], wj2 = s_w[2][jj];
           for (int sx = -1; sx <= 1; ++sx) {
-            const double d0 = cell_delta(wj0, wi0, sx);
+            const double d0 = cell_delta(wj0, wi[0], sx);
             if (!(fabs(d0) < reach[0])) continue;
             for (int sy = -1; sy <= 1; ++sy) {
-              const double d1 = cell_delta(wj1, wi1, sy);
+              const double d1 = cell_delta(wj1, wi[1], sy);
               if (!(fabs(d1) < reach[1])) continue;
               for (int sz = -1; sz <= 1; ++sz) {
-                const double d2 = cell_delta(wj2, wi2, sz);
+                const double d2 = cell_delta(wj2, wi[2], sz);
                 if (!(fabs(d2) < reach[2])) continue;
                 if (self && sx == 0 && sy == 0 && sz == 0) continue;
                 double r[3];
@@ -140,13 +133,10 @@ __global__ __launch_bounds__(256) void cell_env_kernel(const double* __restrict_
   const int cap = max_atoms + kCellEnvSlack, H = 1 << log_table;
   int* list = env_lds + (size_t)wave * (cap + H);
   int* table = list + cap;
-  const int c = centre_cell[m];
-  bool valid = c >= 0 && c < C;
-  int lo = 0, hi = 0, ctr = 0;
-  if (valid) {
-    lo = cell_ptr[c]; hi = cell_ptr[c + 1]; ctr = centre[m];
-    valid = lo >= 0 && hi >= lo && hi <= N && hi - lo <= kCellMaxAtoms && ctr >= lo && ctr < hi;
-  }
+  const int c = centre_cell[m], ctr = centre[m];
+  int lo = 0, n = 0;
+  const bool valid = cell_read(c, cell_ptr, C, N, &lo, &n) && n <= kCellMaxAtoms && ctr >= lo && ctr < lo + n;
+  const int hi = lo + n;
   if (!valid) {   // refused by the host check of every caller that has one; size 0 says so, nothing is listed
     if (!FILL && lane == 0) size_out[m] = 0;
     return;
@@ -164,20 +154,17 @@ __global__ __launch_bounds__(256) void cell_env_kernel(const double* __restrict_
     const int end = count;
     for (int fb = begin; fb < end && count <= max_atoms; fb += 64) {
       const int f = fb + lane;
-      int code = 0, e0 = 0, deg = 0;
+      int code = 0, e0 = 0, e1 = 0, deg = 0;
       if (f < end) {
         const int key = list[f];
-        const int atom = lo + key / kCellShiftCodes;
         code = key % kCellShiftCodes;
-        e0 = row_ptr[atom];
-        const int e1 = row_ptr[atom + 1];
-        if (e0 >= 0 && e1 >= e0 && e1 <= n_bonds) deg = e1 - e0;
+        if (cell_row_read(row_ptr, N, n_bonds, lo + key / kCellShiftCodes, &e0, &e1)) deg = e1 - e0;
       }
       for (int k = 0; count <= max_atoms && __ballot(k < deg) != 0ull; ++k) {
         int fresh = -1;
         if (k < deg) {
           const int ja = bond_atom[e0 + k], sc = bond_shift[e0 + k];
-          if (ja >= lo && ja < hi && sc >= 0 && sc < kCellShiftCodes) {
+          if (cell_site_listed(lo, hi, ja, sc)) {
             const int nc = cell_shift_add(code, sc);
             if (nc >= 0) fresh = (ja - lo) * kCellShiftCodes + nc;
           }
@@ -207,9 +194,9 @@ __global__ __launch_bounds__(256) void cell_env_kernel(const double* __restrict_
   if (count > max_atoms) return;
   const int base = env_ptr[m];
   if (base < 0 || env_ptr[m + 1] - base != count || base > n_sites - count) return;   // not the sizes the count pass gave
-  double L[9];
-  for (int k = 0; k < 9; ++k) L[k] = lattice[9 * (size_t)c + k];
-  const double wi[3] = {cell_wrap(frac[3 * (size_t)ctr]), cell_wrap(frac[3 * (size_t)ctr + 1]), cell_wrap(frac[3 * (size_t)ctr + 2])};
+  double L[9], wi[3];
+  cell_lattice_read(lattice, c, L);
+  cell_wrapped_read(frac, ctr, wi);
   for (int e = lane; e < count; e += 64) {
     const int key = list[e];
     int rank = 0;
@@ -218,11 +205,8 @@ __global__ __launch_bounds__(256) void cell_env_kernel(const double* __restrict_
       for (int t = 1; t < count; ++t) rank += list[t] < key;
     }
     const int atom = lo + key / kCellShiftCodes, code = key % kCellShiftCodes;
-    const double wj[3] = {cell_wrap(frac[3 * (size_t)atom]), cell_wrap(frac[3 * (size_t)atom + 1]), cell_wrap(frac[3 * (size_t)atom + 2])};
-    int s[3];
     double r[3];
-    cell_shift_decode(code, s);
-    cell_site_vector(wj, wi, s, L, r);
+    cell_listed_vector(frac, L, wi, atom, code, r);   // the search lists entries cell_site_listed has passed
     const size_t at = (size_t)base + rank;
     const int ty = type[atom];
     env_atom[at] = atom;

@@ -11,7 +11,7 @@
 //
 // A kernel trusts no index: tile, cell, grid, bin, bin range, sorted atom, bond row and shift code are checked against the extents
 // of the arrays before they are used, and every write is checked against the extent of its output.
-#include "../eval/eval_device.h"
+#include "cell_device.h"
 #include "cell_grid_host.h"
 #include "cell_grid_math.h"
 
@@ -26,11 +26,7 @@ struct GridCell {
 __device__ __forceinline__ bool grid_cell_read(int c, const int* __restrict__ cell_ptr, int C, int N, const int* __restrict__ nbv,
                                                const int* __restrict__ bin_ptr, int n_bins, const int* __restrict__ bin_start,
                                                GridCell* G) {
-  if (c < 0 || c >= C) return false;
-  const int lo = cell_ptr[c], hi = cell_ptr[c + 1];
-  if (lo < 0 || hi < lo || hi > N) return false;
-  G->lo = lo;
-  G->n = hi - lo;
+  if (!cell_read(c, cell_ptr, C, N, &G->lo, &G->n)) return false;
   for (int k = 0; k < 3; ++k) {
     G->nb[k] = nbv[3 * (size_t)c + k];
     if (G->nb[k] < 1 || G->nb[k] > kCellGridMaxBins) return false;
@@ -53,14 +49,10 @@ __device__ __forceinline__ void grid_bin_range(const GridCell& G, const int* __r
   *cnt = b - a;
 }
 
-// the cell of atom i: the last c with cell_ptr[c] <= i; -1 where cell_ptr does not hold i
-__device__ __forceinline__ int grid_cell_of(const int* __restrict__ cell_ptr, int C, int i) {
-  int a = 0, b = C;   // cell_ptr[a] <= i is supposed, b is beyond
-  while (b - a > 1) {
-    const int mid = (a + b) / 2;
-    if (cell_ptr[mid] <= i) a = mid; else b = mid;
-  }
-  return cell_ptr[a] <= i && i < cell_ptr[a + 1] ? a : -1;
+// the cell of atom i, -1 where cell_ptr does not hold i
+__device__ __forceinline__ int grid_cell_of(const int* __restrict__ cell_ptr, int C, int N, int i) {
+  int c, lo, hi;
+  return cell_of_atom(cell_ptr, C, N, i, &c, &lo, &hi) ? c : -1;
 }
 
 // ---- binning -------------------------------------------------------------------------------------------------------------------
@@ -71,7 +63,7 @@ __global__ __launch_bounds__(256) void cell_grid_bin_kernel(const double* __rest
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   int bin = -1;
-  const int c = grid_cell_of(cell_ptr, C, i);
+  const int c = grid_cell_of(cell_ptr, C, N, i);
   GridCell G;
   if (c >= 0 && nbv[3 * (size_t)c] != 0 && grid_cell_read(c, cell_ptr, C, N, nbv, bin_ptr, n_bins, nullptr, &G)) {
     bin = cell_grid_bin(frac + 3 * (size_t)i, G.nb);
@@ -89,7 +81,7 @@ __global__ __launch_bounds__(256) void cell_grid_scatter_kernel(const int* __res
   if (i >= N) return;
   const int bin = atom_bin[i];
   if (bin < 0) return;
-  const int c = grid_cell_of(cell_ptr, C, i);
+  const int c = grid_cell_of(cell_ptr, C, N, i);
   GridCell G;
   if (c < 0 || !grid_cell_read(c, cell_ptr, C, N, nbv, bin_ptr, n_bins, bin_start, &G)) return;
   int p0, cnt;
@@ -111,7 +103,7 @@ __global__ __launch_bounds__(256) void cell_grid_rank_kernel(const double* __res
   if (i >= N) return;
   const int bin = atom_bin[i];
   if (bin < 0) return;
-  const int c = grid_cell_of(cell_ptr, C, i);
+  const int c = grid_cell_of(cell_ptr, C, N, i);
   GridCell G;
   if (c < 0 || !grid_cell_read(c, cell_ptr, C, N, nbv, bin_ptr, n_bins, bin_start, &G)) return;
   int p0, cnt;
@@ -126,7 +118,7 @@ __global__ __launch_bounds__(256) void cell_grid_rank_kernel(const double* __res
   if (!seen || rank >= cnt) return;   // the bin does not hold this atom: bin_start is not the prefix sum of the count pass
   const size_t at = (size_t)G.lo + p0 + rank;
   sorted_atom[at] = i;
-  for (int k = 0; k < 3; ++k) sorted_frac[3 * at + k] = cell_wrap(frac[3 * (size_t)i + k]);
+  cell_wrapped_read(frac, i, sorted_frac + 3 * at);
   sorted_type[at] = type[i];
 }
 
@@ -212,10 +204,11 @@ __global__ __launch_bounds__(256) void cell_bond_grid_kernel(const double* __res
   if (reach < 1 || reach > kCellGridMaxReach || !grid_cell_read(c, cell_ptr, C, N, nbv, bin_ptr, n_bins, bin_start, &G)) return;
   for (int k = 0; k < 3; ++k)
     if (G.nb[k] < 2 * reach + 1) return;
-  if (c0 < 0 || c0 >= G.n) return;
-  const int nc = min(kCellCentreBlock, G.n - c0), hi = G.lo + G.n;
+  int nc;
+  if (!cell_block_read<kCellCentreBlock>(c0, G.n, &nc)) return;
+  const int hi = G.lo + G.n;
   double L[9];
-  for (int k = 0; k < 9; ++k) L[k] = lattice[9 * (size_t)c + k];
+  cell_lattice_read(lattice, c, L);
   const double c2 = cutoff * cutoff;
   constexpr int per_wave = kCellCentreBlock / kWaves;
   const int ci_end = min(nc, (wave + 1) * per_wave);
@@ -233,8 +226,8 @@ __global__ __launch_bounds__(256) void cell_bond_grid_kernel(const double* __res
       if (lane == 0) degree[i] = deg;
       continue;
     }
-    const int row_lo = row_ptr[i], row_hi = row_ptr[i + 1];
-    if (row_lo < 0 || row_hi < row_lo || row_hi > n_bonds) continue;
+    int row_lo, row_hi;
+    if (!cell_row_read(row_ptr, N, n_bonds, i, &row_lo, &row_hi)) continue;
     const int deg = row_hi - row_lo, pieces = (deg + kCellGridRowKeys - 1) / kCellGridRowKeys;
     for (int P = 0; P < pieces; ++P) {
       auto stage = [&](int* buf, int piece) {
@@ -311,10 +304,10 @@ __global__ __launch_bounds__(256) void cell_pair_grid_kernel(const double* __res
   if (reach < 1 || reach > kCellGridMaxReach || !grid_cell_read(c, cell_ptr, C, N, nbv, bin_ptr, n_bins, bin_start, &G)) return;
   for (int k = 0; k < 3; ++k)
     if (G.nb[k] < 2 * reach + 1) return;
-  if (c0 < 0 || c0 >= G.n) return;
-  const int nc = min(kCellStatCentreBlock, G.n - c0);
+  int nc;
+  if (!cell_block_read<kCellStatCentreBlock>(c0, G.n, &nc)) return;
   double L[9];
-  for (int k = 0; k < 9; ++k) L[k] = lattice[9 * (size_t)c + k];
+  cell_lattice_read(lattice, c, L);
   const double limit = cell_stat_r2_limit(dR, nbins);
   const int nh = A * A * nbins;
   const int span = 2 * reach + 1, T = span * span * span;

@@ -97,8 +97,7 @@ int egnn_cell_grid_host(int C, int A, const int32_t* cell_ptr, const double* lat
     }
   }
   if (int rc = type_range_check(who, type, 0, N, A)) return rc;
-  for (size_t t = 0; t < 3 * (size_t)N; ++t)
-    if (!(fabs(frac[t]) < 1e15)) { set_error("%s: atom %d has a fractional coordinate that is not finite", who, (int)(t / 3)); return EGNN_EINVAL; }
+  if (int rc = cell_frac_finite_check(who, frac, 0, N)) return rc;
 
   // ---- the grids ----
   Scratch<int32_t> dims(3 * (size_t)C);
@@ -128,8 +127,8 @@ int egnn_cell_grid_host(int C, int A, const int32_t* cell_ptr, const double* lat
   // ---- bins, bin starts (a counting sort: stable, so a bin holds its atoms ascending by index) ----
   Scratch<double> w(3 * (size_t)N);
   Scratch<int32_t> bin(N), start((size_t)B + 1), order(N), cursor((size_t)B + 1);
-  if (!w.p || !bin.p || !start.p || !order.p || !cursor.p) { set_error("%s: out of memory", who); return EGNN_ENOMEM; }
-  for (size_t t = 0; t < 3 * (size_t)N; ++t) w[t] = cell_wrap(frac[t]);
+  if (int rc = cell_wrap_batch(who, N, frac, w)) return rc;
+  if (!bin.p || !start.p || !order.p || !cursor.p) { set_error("%s: out of memory", who); return EGNN_ENOMEM; }
   for (int c = 0; c < C; ++c) {
     const int d[3] = {dims[3 * (size_t)c], dims[3 * (size_t)c + 1], dims[3 * (size_t)c + 2]};
     for (int i = cell_ptr[c]; i < cell_ptr[c + 1]; ++i) {

@@ -9,23 +9,35 @@
 
 namespace egnn {
 
-int cell_batch_check(const char* who, int C, int N, const int32_t* cell_ptr, const double* lattice, double cutoff) {
-  if (C < 1 || N < 0 || !cell_ptr) { set_error("bad %s arguments (C >= 1, N >= 0, the host copy of cell_ptr given)", who); return EGNN_EINVAL; }
-  if (!(cutoff > 0.0) || !(cutoff < 1e30)) { set_error("%s: cutoff must be positive and finite", who); return EGNN_EINVAL; }
+int cell_batch_core_check(const char* who, int C, int N, const int32_t* cell_ptr, const double* lattice, CellWidthRule rule, double reach) {
   if (cell_ptr[0] != 0 || cell_ptr[C] != N) { set_error("%s: cell_ptr must run from 0 to N = %d", who, N); return EGNN_EINVAL; }
   for (int c = 0; c < C; ++c)
     if (int rc = ptr_step_check(who, "cell_ptr", "cell", cell_ptr, c, kCellMaxAtoms)) return rc;
   if (!lattice) return EGNN_OK;
   for (int c = 0; c < C; ++c) {
+    const double* L = lattice + 9 * (size_t)c;
     double w[3];
-    if (!cell_widths(lattice + 9 * (size_t)c, w)) { set_error("%s: cell %d has a singular lattice", who, c); return EGNN_EINVAL; }
-    for (int k = 0; k < 3; ++k)
-      if (!(w[k] >= cutoff)) {
-        set_error("%s: cell %d has a perpendicular width %.6g below the cutoff %.6g (27 images are not complete)", who, c, w[k], cutoff);
-        return EGNN_EINVAL;
-      }
+    if (!cell_widths(L, w)) { set_error("%s: cell %d has a singular lattice", who, c); return EGNN_EINVAL; }
+    if (rule)
+      if (int rc = rule(who, c, L, w, reach)) return rc;
   }
   return EGNN_OK;
+}
+
+// 27 images hold every bond of a cell whose widths reach the cutoff (cell_math.h)
+static int cell_widths_cover_rule(const char* who, int c, const double*, const double* w, double cutoff) {
+  for (int k = 0; k < 3; ++k)
+    if (!(w[k] >= cutoff)) {
+      set_error("%s: cell %d has a perpendicular width %.6g below the cutoff %.6g (27 images are not complete)", who, c, w[k], cutoff);
+      return EGNN_EINVAL;
+    }
+  return EGNN_OK;
+}
+
+int cell_batch_check(const char* who, int C, int N, const int32_t* cell_ptr, const double* lattice, double cutoff) {
+  if (C < 1 || N < 0 || !cell_ptr) { set_error("bad %s arguments (C >= 1, N >= 0, the host copy of cell_ptr given)", who); return EGNN_EINVAL; }
+  if (!(cutoff > 0.0) || !(cutoff < 1e30)) { set_error("%s: cutoff must be positive and finite", who); return EGNN_EINVAL; }
+  return cell_batch_core_check(who, C, N, cell_ptr, lattice, cell_widths_cover_rule, cutoff);
 }
 
 int cell_env_params_check(const char* who, int M, int shells, int max_atoms, const void* centre_cell, const void* centre) {
@@ -57,10 +69,9 @@ int egnn_cell_env_host(int C, int A, const int32_t* cell_ptr, const double* latt
   if (int rc = cell_env_params_check(who, M, shells, max_atoms, centre_cell, centre)) return rc;
   const int N = cell_ptr[C];
   if (int rc = cell_batch_check(who, C, N, cell_ptr, lattice, cutoff)) return rc;
-  for (int i = 0; i < N; ++i) {
-    if (type[i] < 0 || type[i] >= A) { set_error("%s: atom %d has type %d outside [0, %d)", who, i, type[i], A); return EGNN_EINVAL; }
-    for (int k = 0; k < 3; ++k)
-      if (!(fabs(frac[3 * (size_t)i + k]) < 1e15)) { set_error("%s: atom %d has a fractional coordinate that is not finite", who, i); return EGNN_EINVAL; }
+  for (int i = 0; i < N; ++i) {   // atom by atom: the first bad atom is named, its type before its coordinates
+    if (int rc = type_range_check(who, type, i, i + 1, A)) return rc;
+    if (int rc = cell_frac_finite_check(who, frac, i, i + 1)) return rc;
   }
   for (int m = 0; m < M; ++m) {
     const int c = centre_cell[m];
@@ -71,10 +82,12 @@ int egnn_cell_env_host(int C, int A, const int32_t* cell_ptr, const double* latt
     }
   }
 
+  int n_max = 0;
+  for (int c = 0; c < C; ++c) n_max = cell_ptr[c + 1] - cell_ptr[c] > n_max ? cell_ptr[c + 1] - cell_ptr[c] : n_max;
   Scratch<double> w(3 * (size_t)N);
-  Scratch<int32_t> keys((size_t)max_atoms + 2), seen((size_t)max_atoms + 2);
-  if (!w.p || !keys.p || !seen.p) { set_error("%s: out of memory", who); return EGNN_ENOMEM; }
-  for (size_t t = 0; t < 3 * (size_t)N; ++t) w[t] = cell_wrap(frac[t]);
+  Scratch<int32_t> keys((size_t)max_atoms + 2), seen((size_t)max_atoms + 2), r_atom(27 * (size_t)n_max), r_code(27 * (size_t)n_max);
+  if (int rc = cell_wrap_batch(who, N, frac, w)) return rc;
+  if (!keys.p || !seen.p || !r_atom.p || !r_code.p) { set_error("%s: out of memory", who); return EGNN_ENOMEM; }
   const double c2 = cutoff * cutoff;
 
   // ---- bond list: rows ascending by (atom, shift code); counted, then written ----
@@ -84,22 +97,17 @@ int egnn_cell_env_host(int C, int A, const int32_t* cell_ptr, const double* latt
     int64_t n_bonds = 0;
     for (int c = 0; c < C; ++c) {
       const double* L = lattice + 9 * (size_t)c;
-      for (int i = cell_ptr[c]; i < cell_ptr[c + 1]; ++i) {
-        for (int j = cell_ptr[c]; j < cell_ptr[c + 1]; ++j)
-          for (int sx = -1; sx <= 1; ++sx)
-            for (int sy = -1; sy <= 1; ++sy)
-              for (int sz = -1; sz <= 1; ++sz) {
-                if (j == i && sx == 0 && sy == 0 && sz == 0) continue;
-                const int s[3] = {sx, sy, sz};
-                double r[3];
-                cell_site_vector(&w[3 * (size_t)j], &w[3 * (size_t)i], s, L, r);
-                if (!(cell_norm2(r) < c2)) continue;
-                if (pass == 1) {
-                  b_atom[(size_t)n_bonds] = j;
-                  b_shift[(size_t)n_bonds] = cell_shift_code(sx, sy, sz);
-                }
-                ++n_bonds;
-              }
+      const int lo = cell_ptr[c], hi = cell_ptr[c + 1];
+      double width[3], reach[3];
+      cell_widths(L, width);   // regular: the batch check has passed
+      for (int k = 0; k < 3; ++k) reach[k] = cutoff * (1.0 + 1e-6) / width[k];
+      for (int i = lo; i < hi; ++i) {
+        const int deg = cell_row_bonds(w.p, L, reach, lo, hi, i, c2, r_atom.p, r_code.p);
+        if (pass == 1 && deg > 0) {
+          memcpy(b_atom.p + n_bonds, r_atom.p, sizeof(int32_t) * (size_t)deg);
+          memcpy(b_shift.p + n_bonds, r_code.p, sizeof(int32_t) * (size_t)deg);
+        }
+        n_bonds += deg;
         if (n_bonds > 2147483647LL) { set_error("%s: more than 2^31 - 1 bonds", who); return EGNN_EINVAL; }
         bond_ptr[i + 1] = (int32_t)n_bonds;
       }
@@ -158,10 +166,8 @@ int egnn_cell_env_host(int C, int A, const int32_t* cell_ptr, const double* latt
           const int32_t key = t < 0 ? key0 : seen[t];
           if (t >= 0 && key == key0) continue;
           const int atom = lo + key / kCellShiftCodes, code = key % kCellShiftCodes;
-          int s[3];
           double r[3];
-          cell_shift_decode(code, s);
-          cell_site_vector(&w[3 * (size_t)atom], &w[3 * (size_t)centre[m]], s, L, r);
+          cell_listed_vector(w.p, L, &w[3 * (size_t)centre[m]], atom, code, r);
           env_atom[at] = atom;
           env_shift[at] = code;
           env_type[at] = type[atom];

@@ -65,7 +65,32 @@ EGNN_HD void cell_site_vector(const double* wj, const double* wi, const int* s, 
   cell_cartesian(cell_delta(wj[0], wi[0], s[0]), cell_delta(wj[1], wi[1], s[1]), cell_delta(wj[2], wi[2], s[2]), L, r);
 }
 
-// perpendicular widths w_k = |det L| / |a_{k+1} x a_{k+2}|; false for a lattice that is singular (|det| <= 1e-9 |a||b||c|) or not
+// the wrapped fractional coordinates of batch atom i
+EGNN_HD void cell_wrapped_read(const double* frac, int i, double* w) {
+  for (int k = 0; k < 3; ++k) w[k] = cell_wrap(frac[3 * (size_t)i + k]);
+}
+
+// whether entry (atom j, shift code) of a bond or site list names a site of the cell [lo, hi)
+EGNN_HD bool cell_site_listed(int lo, int hi, int j, int code) { return j >= lo && j < hi && code >= 0 && code < kCellShiftCodes; }
+
+// vector from the centre at wrapped wi to the site (j, code) of an entry that cell_site_listed has passed.  frac may be wrapped
+// already: cell_wrap of a value in [0, 1) is that value.
+EGNN_HD void cell_listed_vector(const double* frac, const double* L, const double* wi, int j, int code, double* r) {
+  double wj[3];
+  int s[3];
+  cell_wrapped_read(frac, j, wj);
+  cell_shift_decode(code, s);
+  cell_site_vector(wj, wi, s, L, r);
+}
+
+// the test and the vector of a list entry in one: false, r untouched, where (j, code) names no site of the cell [lo, hi)
+EGNN_HD bool cell_listed_site_vector(const double* frac, const double* L, int lo, int hi, const double* wi, int j, int code, double* r) {
+  if (!cell_site_listed(lo, hi, j, code)) return false;
+  cell_listed_vector(frac, L, wi, j, code, r);
+  return true;
+}
+
+// perpendicular widths w_k =|det L| / |a_{k+1} x a_{k+2}|; false for a lattice that is singular (|det| <= 1e-9 |a||b||c|) or not
 // finite
 EGNN_HD bool cell_widths(const double* L, double* w) {
   const double* a = L;

@@ -11,23 +11,10 @@
 // are used, and every write is checked against the extent of its output.
 #include "../eval/soap_device.h"
 #include "cell_soap_host.h"
+#include "cell_device.h"
 #include "cell_soap_math.h"
 
 namespace egnn {
-
-// the cell of batch atom i: the last c with cell_ptr[c] <= i; false unless the cell's range is sane and holds i
-__device__ __forceinline__ bool cell_of_atom(const int* __restrict__ cell_ptr, int C, int N, int i, int* cell, int* lo, int* hi) {
-  if (i < 0 || i >= N) return false;
-  int a = 0, b = C;   // cell_ptr[a] <= i < cell_ptr[b] is the aim
-  while (b - a > 1) {
-    const int mid = (a + b) / 2;
-    if (cell_ptr[mid] <= i) a = mid; else b = mid;
-  }
-  *cell = a;
-  *lo = cell_ptr[a];
-  *hi = cell_ptr[a + 1];
-  return *lo >= 0 && *hi <= N && i >= *lo && i < *hi && *hi - *lo <= kCellMaxAtoms;
-}
 
 // ---- site lists ----------------------------------------------------------------------------------------------------------------
 // One wavefront per listed centre, four per workgroup, no LDS and no barrier.  The wavefront walks the candidates q = j nbox + t of
@@ -48,22 +35,19 @@ __global__ __launch_bounds__(64 * kCellSiteWaves) void cell_sites_kernel(const d
   double L[9], width[3];
   bool valid = cell_of_atom(cell_ptr, C, N, i, &c, &lo, &hi);
   if (valid) {
-    for (int k = 0; k < 9; ++k) L[k] = lattice[9 * (size_t)c + k];
+    cell_lattice_read(lattice, c, L);
     valid = cell_soap_box(L, cut, b, width);
   }
   int row_lo = 0, row_hi = 0;
-  if (FILL) {
-    row_lo = row_ptr[m];
-    row_hi = row_ptr[m + 1];
-    if (row_lo < 0 || row_hi < row_lo || row_hi > T) valid = false;
-  }
+  if (FILL && !cell_row_read(row_ptr, M, T, m, &row_lo, &row_hi)) valid = false;
   if (!valid) {
     if (!FILL && lane == 0) degree[m] = 0;
     return;
   }
   const int n = hi - lo, nbox = cell_soap_box_count(b), total = n * nbox;   // at most 2^20 * 729 < 2^31
   const int self = (i - lo) * nbox + ((b[0] * (2 * b[1] + 1) + b[1]) * (2 * b[2] + 1) + b[2]);   // the candidate (i, 0)
-  const double wi[3] = {cell_wrap(frac[3 * (size_t)i]), cell_wrap(frac[3 * (size_t)i + 1]), cell_wrap(frac[3 * (size_t)i + 2])};
+  double wi[3];
+  cell_wrapped_read(frac, i, wi);
   const double cut2 = cut * cut;
   int cnt = 0;
   for (int q0 = 0; q0 < total; q0 += 64) {   // uniform in the wavefront
@@ -73,9 +57,8 @@ __global__ __launch_bounds__(64 * kCellSiteWaves) void cell_sites_kernel(const d
     if (q < total && q != self) {
       j = q / nbox;
       cell_soap_box_shift(q - j * nbox, b, s);
-      const size_t at = 3 * (size_t)(lo + j);
-      const double wj[3] = {cell_wrap(frac[at]), cell_wrap(frac[at + 1]), cell_wrap(frac[at + 2])};
-      double r[3];
+      double wj[3], r[3];
+      cell_wrapped_read(frac, lo + j, wj);
       hit = cell_soap_site(wj, wi, s, L, cut2, r);
     }
     const unsigned long long hits = __ballot(hit);
@@ -115,18 +98,9 @@ __global__ __launch_bounds__(kSoapThreads) void cell_soap_kernel(const double* _
   const SoapLds s = soap_lds_carve(s_soap, A, n_max, l_max);
   const int i = centre_atom[m];
   if (tid == 0) {
-    int c = -1, lo = 0, hi = 0, e0 = 0, e1 = 0;
-    if (cell_of_atom(cell_ptr, C, N, i, &c, &lo, &hi)) {
-      const int r = centre_row[m];
-      if (r >= 0 && r < n_rows) {
-        e0 = row_ptr[r];
-        e1 = row_ptr[r + 1];
-      }
-      if (r < 0 || r >= n_rows || e0 < 0 || e1 < e0 || e1 > T) c = -1;
-    } else {
-      c = -1;
-    }
-    s_range[0] = c; s_range[1] = lo; s_range[2] = hi; s_range[3] = e0; s_range[4] = e1;
+    CellCentreRow R = {};
+    const bool found = cell_centre_row_read(cell_ptr, C, N, row_ptr, n_rows, T, centre_atom, centre_row, m, &R);
+    s_range[0] = found ? R.c : -1; s_range[1] = R.lo; s_range[2] = R.hi; s_range[3] = R.e0; s_range[4] = R.e1;
   }
   for (int o = tid; o < nC; o += kSoapThreads) s.c[o] = 0.0;
   __syncthreads();
@@ -149,14 +123,10 @@ __global__ __launch_bounds__(kSoapThreads) void cell_soap_kernel(const double* _
         species = (ti >= 0 && ti < A) ? ti : -1;
       } else {
         const int j = site_atom[e0 + k - 1], code = site_shift[e0 + k - 1];
-        if (j >= lo && j < hi && code >= 0 && code < kCellShiftCodes) {
-          const double wi[3] = {cell_wrap(frac[3 * (size_t)i]), cell_wrap(frac[3 * (size_t)i + 1]), cell_wrap(frac[3 * (size_t)i + 2])};
-          const double wj[3] = {cell_wrap(frac[3 * (size_t)j]), cell_wrap(frac[3 * (size_t)j + 1]), cell_wrap(frac[3 * (size_t)j + 2])};
-          double L[9];
-          for (int x = 0; x < 9; ++x) L[x] = lattice[9 * (size_t)c + x];
-          int sh[3];
-          cell_shift_decode(code, sh);
-          cell_site_vector(wj, wi, sh, L, r);
+        double wi[3], L[9];
+        cell_wrapped_read(frac, i, wi);
+        cell_lattice_read(lattice, c, L);
+        if (cell_listed_site_vector(frac, L, lo, hi, wi, j, code, r)) {
           const int tj = type[j];
           species = (tj >= 0 && tj < A) ? tj : -1;
         }
@@ -243,8 +213,8 @@ int egnn_cell_soap_descriptor(void* stream, int C, int N, int A, const int32_t* 
                               const int32_t* d_site_shift, int M, const int32_t* d_centre_atom, const int32_t* d_centre_row, double* d_desc,
                               double* d_coeff) {
   const char* who = "egnn_cell_soap_descriptor";
-  if (!d_cell_ptr || !d_lattice || !d_frac || !d_type || n_rows < 0 || !d_row_ptr || T < 0 || (T > 0 && (!d_site_atom || !d_site_shift)) ||
-      M < 1 || !d_centre_atom || !d_centre_row || !d_desc) {
+  if (!cell_rows_given(d_cell_ptr, d_lattice, d_frac, d_type, n_rows, d_row_ptr, T, d_site_atom, d_site_shift, M, d_centre_atom, d_centre_row) ||
+      !d_desc) {
     set_error("bad %s arguments (d_cell_ptr, d_lattice, d_frac, d_type, d_row_ptr, the centres and d_desc given; n_rows >= 0 rows of T >= 0 "
               "sites; M >= 1)", who);
     return EGNN_EINVAL;

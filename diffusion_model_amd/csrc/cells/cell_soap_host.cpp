@@ -10,25 +10,23 @@
 
 namespace egnn {
 
+// the shift code holds the sites of a cell whose image box stays within 4 (cell_soap_math.h)
+static int cell_widths_box_rule(const char* who, int c, const double* L, const double* w, double cut) {
+  int b[3];
+  double w_box[3];
+  if (cell_soap_box(L, cut, b, w_box)) return EGNN_OK;
+  set_error("%s: cell %d has perpendicular widths %.6g, %.6g, %.6g and one is at most cut / 4 = %.6g (an image box beyond %d)", who, c, w[0],
+            w[1], w[2], cut / 4.0, kCellSoapMaxBox);
+  return EGNN_EINVAL;
+}
+
 int cell_soap_batch_check(const char* who, int C, int N, const int32_t* cell_ptr, const double* lattice, double cut) {
   if (C < 1 || N < 0 || !cell_ptr || !lattice) {
     set_error("bad %s arguments (C >= 1, N >= 0, the host copies of cell_ptr and lattice given)", who);
     return EGNN_EINVAL;
   }
   if (cut != 0.0 && (!soap_cut_ok(cut) || !(cut < 1e30))) { set_error("%s: cut must be positive and finite", who); return EGNN_EINVAL; }
-  if (cell_ptr[0] != 0 || cell_ptr[C] != N) { set_error("%s: cell_ptr must run from 0 to N = %d", who, N); return EGNN_EINVAL; }
-  for (int c = 0; c < C; ++c)
-    if (int rc = ptr_step_check(who, "cell_ptr", "cell", cell_ptr, c, kCellMaxAtoms)) return rc;
-  for (int c = 0; c < C; ++c) {
-    double w[3] = {0.0, 0.0, 0.0};
-    int b[3];
-    if (cut == 0.0 ? cell_widths(lattice + 9 * (size_t)c, w) : cell_soap_box(lattice + 9 * (size_t)c, cut, b, w)) continue;
-    if (w[0] == 0.0 && w[1] == 0.0 && w[2] == 0.0) { set_error("%s: cell %d has a singular lattice", who, c); return EGNN_EINVAL; }
-    set_error("%s: cell %d has perpendicular widths %.6g, %.6g, %.6g and one is at most cut / 4 = %.6g (an image box beyond %d)", who, c, w[0],
-              w[1], w[2], cut / 4.0, kCellSoapMaxBox);
-    return EGNN_EINVAL;
-  }
-  return EGNN_OK;
+  return cell_batch_core_check(who, C, N, cell_ptr, lattice, cut == 0.0 ? nullptr : cell_widths_box_rule, cut);
 }
 
 int cell_soap_basis_check(const char* who, int A, int n_max, int l_max, const void* tables) {
@@ -42,21 +40,7 @@ int cell_soap_basis_check(const char* who, int A, int n_max, int l_max, const vo
 // what the two host statements ask of their inputs beyond the batch check: finite coordinates, centres inside the batch
 static int cell_soap_inputs_check(const char* who, int N, const double* frac, int M, const int32_t* centre_atom) {
   if (M < 0 || (M > 0 && !centre_atom) || (N > 0 && !frac)) { set_error("bad %s arguments (M >= 0 centres and frac given)", who); return EGNN_EINVAL; }
-  for (int i = 0; i < N; ++i)
-    for (int k = 0; k < 3; ++k)
-      if (!(fabs(frac[3 * (size_t)i + k]) < 1e15)) { set_error("%s: atom %d has a fractional coordinate that is not finite", who, i); return EGNN_EINVAL; }
-  for (int m = 0; m < M; ++m)
-    if (centre_atom[m] < 0 || centre_atom[m] >= N) {
-      set_error("%s: centre %d is atom %d outside [0, %d)", who, m, centre_atom[m], N);
-      return EGNN_EINVAL;
-    }
-  return EGNN_OK;
-}
-
-static int cell_of_atom(const int32_t* cell_ptr, int i) {
-  int c = 0;
-  while (cell_ptr[c + 1] <= i) ++c;   // empty cells skipped
-  return c;
+  return cell_inputs_check(who, N, frac, nullptr, 0, M, centre_atom);
 }
 
 }  // namespace egnn
@@ -74,15 +58,14 @@ int egnn_cell_sites_host(int C, const int32_t* cell_ptr, const double* lattice, 
   if (int rc = cell_soap_batch_check(who, C, N, cell_ptr, lattice, cut)) return rc;
   if (int rc = cell_soap_inputs_check(who, N, frac, M, centre_atom)) return rc;
   Scratch<double> w(3 * (size_t)N);
-  if (!w.p) { set_error("%s: out of memory", who); return EGNN_ENOMEM; }
-  for (size_t t = 0; t < 3 * (size_t)N; ++t) w[t] = cell_wrap(frac[t]);
+  if (int rc = cell_wrap_batch(who, N, frac, w)) return rc;
   const double cut2 = cut * cut;
   const bool lists = site_atom && site_shift;
   row_ptr[0] = 0;
   for (int pass = 0; pass < 2; ++pass) {
     int64_t total = 0;
     for (int m = 0; m < M; ++m) {
-      const int i = centre_atom[m], c = cell_of_atom(cell_ptr, i), lo = cell_ptr[c], n = cell_ptr[c + 1] - lo;
+      const int i = centre_atom[m], c = cell_of_atom_host(cell_ptr, C, i), lo = cell_ptr[c], n = cell_ptr[c + 1] - lo;
       const double* L = lattice + 9 * (size_t)c;
       int b[3];
       double width[3];
@@ -123,13 +106,13 @@ int egnn_cell_soap_host(int C, int A, const int32_t* cell_ptr, const double* lat
   const int L1 = l_max + 1, LM = soap_lm_count(l_max), nF = soap_feature_count(A, n_max, l_max);
   const size_t nC = (size_t)A * n_max * LM;
   Scratch<double> w(3 * (size_t)N), prim(nC), c(nC), solid((size_t)LM), radial((size_t)n_max * L1);
-  if (!w.p || !prim.p || !c.p || !solid.p || !radial.p) { set_error("%s: out of memory", who); return EGNN_ENOMEM; }
-  for (size_t t = 0; t < 3 * (size_t)N; ++t) w[t] = cell_wrap(frac[t]);
+  if (int rc = cell_wrap_batch(who, N, frac, w)) return rc;
+  if (!prim.p || !c.p || !solid.p || !radial.p) { set_error("%s: out of memory", who); return EGNN_ENOMEM; }
   const double cut2 = cut * cut;
   const double* norm = tables + soap_table_norm(n_max, l_max);
   const double* beta = tables + soap_table_beta(n_max, l_max);
   for (int m = 0; m < M; ++m) {
-    const int i = centre_atom[m], cell = cell_of_atom(cell_ptr, i), lo = cell_ptr[cell], n = cell_ptr[cell + 1] - lo;
+    const int i = centre_atom[m], cell = cell_of_atom_host(cell_ptr, C, i), lo = cell_ptr[cell], n = cell_ptr[cell + 1] - lo;
     const double* L = lattice + 9 * (size_t)cell;
     int b[3];
     double width[3];

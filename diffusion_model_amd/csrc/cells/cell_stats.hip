@@ -9,7 +9,7 @@
 //
 // A kernel trusts no index: tile, cell, centre block, neighbour chunk, shift piece, bond row, neighbour and shift code are checked
 // against the extents of the arrays before they are used, and every write is checked against the extent of its output.
-#include "../eval/eval_device.h"
+#include "cell_device.h"
 #include "cell_stats_host.h"
 #include "cell_stats_math.h"
 
@@ -37,17 +37,14 @@ __global__ __launch_bounds__(256) void cell_pair_kernel(const double* __restrict
   __shared__ int s_type[kCellStatChunk];
   const int tid = threadIdx.x;
   const int* tile = tiles + 5 * (size_t)blockIdx.x;
-  const int c = tile[0], c0 = tile[1], j0 = tile[2], piece = tile[3], pieces = tile[4];
-  if (c < 0 || c >= C) return;
-  const int lo = cell_ptr[c], hi = cell_ptr[c + 1];
-  if (lo < 0 || hi < lo || hi > N) return;
-  const int n = hi - lo;
-  if (c0 < 0 || c0 >= n || j0 < 0 || j0 >= n) return;
+  const int j0 = tile[2], piece = tile[3], pieces = tile[4];
+  CellTile T;
+  if (!cell_tile_read<kCellStatCentreBlock>(tile, cell_ptr, C, N, &T) || j0 < 0 || j0 >= T.n) return;
   if (pieces < 1 || pieces > 2 * kCellStatMaxImages + 1 || piece < 0 || piece >= pieces) return;
-  const int nc = min(kCellStatCentreBlock, n - c0), nj = min(kCellStatChunk, n - j0);
+  const int c = T.c, c0 = T.c0, lo = T.lo, nc = T.nc, nj = min(kCellStatChunk, T.n - j0);
   double L[9], width[3], reach[3];
   int S[3];
-  for (int k = 0; k < 9; ++k) L[k] = lattice[9 * (size_t)c + k];
+  cell_lattice_read(lattice, c, L);
   if (!cell_stat_image_box(L, dR, nbins, S) || !cell_widths(L, width)) return;   // refused by the host check of every entry
   if (S[0] > kCellStatMaxImages || S[1] > kCellStatMaxImages || S[2] > kCellStatMaxImages) return;
   for (int k = 0; k < 3; ++k) reach[k] = cell_stat_axis_reach(dR, nbins, width[k]);
@@ -57,18 +54,15 @@ __global__ __launch_bounds__(256) void cell_pair_kernel(const double* __restrict
   const double limit = cell_stat_r2_limit(dR, nbins);
   const int nh = A * A * nbins;
   for (int k = tid; k < nh; k += 256) cell_pair_hist[k] = 0u;
-  for (int t = tid; t < 3 * nj; t += 256) {
-    const int a = t / 3, k = t - 3 * a;
-    s_w[k][a] = cell_wrap(frac[3 * (size_t)(lo + j0) + t]);
-  }
-  for (int t = tid; t < nj; t += 256) s_type[t] = type[lo + j0 + t];
+  cell_chunk_stage<kCellStatChunk>(frac, type, lo + j0, nj, tid, s_w, s_type);
   __syncthreads();
   constexpr int slices = 256 / kCellStatCentreBlock;
   const int ci = tid % kCellStatCentreBlock, slice = tid / kCellStatCentreBlock;
   if (ci < nc && sx_lo < sx_hi) {
     const int i = lo + c0 + ci, ti = type[i];
     if (ti >= 0 && ti < A) {
-      const double wi0 = cell_wrap(frac[3 * (size_t)i]), wi1 = cell_wrap(frac[3 * (size_t)i + 1]), wi2 = cell_wrap(frac[3 * (size_t)i + 2]);
+      double wi[3];
+      cell_wrapped_read(frac, i, wi);
       unsigned* row = cell_pair_hist + (size_t)ti * A * nbins;
       for (int j = slice; j < nj; j += slices) {
         const int tj = s_type[j];
@@ -77,13 +71,13 @@ __global__ __launch_bounds__(256) void cell_pair_kernel(const double* __restrict
         const double wj0 = s_w[0][j], wj1 = s_w[1][j], wj2 = s_w[2][j];
         unsigned* bins = row + tj * nbins;
         for (int sx = sx_lo; sx < sx_hi; ++sx) {
-          const double d0 = cell_delta(wj0, wi0, sx);
+          const double d0 = cell_delta(wj0, wi[0], sx);
           if (!(fabs(d0) < reach[0])) continue;
           for (int sy = -S[1]; sy <= S[1]; ++sy) {
-            const double d1 = cell_delta(wj1, wi1, sy);
+            const double d1 = cell_delta(wj1, wi[1], sy);
             if (!(fabs(d1) < reach[1])) continue;
             for (int sz = -S[2]; sz <= S[2]; ++sz) {
-              const double d2 = cell_delta(wj2, wi2, sz);
+              const double d2 = cell_delta(wj2, wi[2], sz);
               if (!(fabs(d2) < reach[2])) continue;
               if (self && sx == 0 && sy == 0 && sz == 0) continue;
               double r[3];
@@ -118,14 +112,6 @@ struct CellBondWave {
   int t[kMaxNeighbours];
 };
 
-// the bonds of atom i as a checked range of the lists: false where row_ptr is not what the fill pass wrote
-__device__ __forceinline__ bool cell_stat_row(const int* __restrict__ row_ptr, int n_bonds, int i, int* e0, int* deg) {
-  *e0 = row_ptr[i];
-  const int e1 = row_ptr[i + 1];
-  *deg = e1 - *e0;
-  return *e0 >= 0 && e1 >= *e0 && e1 <= n_bonds;
-}
-
 __global__ __launch_bounds__(256) void cell_bond_stats_kernel(const double* __restrict__ frac, const double* __restrict__ lattice,
                                                               const int* __restrict__ type, const int* __restrict__ cell_ptr, int C,
                                                               int N, int A, const int* __restrict__ row_ptr, int n_bonds,
@@ -136,13 +122,9 @@ __global__ __launch_bounds__(256) void cell_bond_stats_kernel(const double* __re
   extern __shared__ int cell_bond_hist[];
   __shared__ CellBondWave s_wave[kWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c = tiles[2 * (size_t)blockIdx.x], c0 = tiles[2 * (size_t)blockIdx.x + 1];
-  if (c < 0 || c >= C) return;
-  const int lo = cell_ptr[c], hi = cell_ptr[c + 1];
-  if (lo < 0 || hi < lo || hi > N) return;
-  const int n = hi - lo;
-  if (c0 < 0 || c0 >= n) return;
-  const int nc = min(kCellStatBondCentres, n - c0);
+  CellTile T;
+  if (!cell_tile_read<kCellStatBondCentres>(tiles + 2 * (size_t)blockIdx.x, cell_ptr, C, N, &T)) return;
+  const int c = T.c, c0 = T.c0, lo = T.lo, hi = T.lo + T.n, nc = T.nc;
   const int P = type_pairs(A), ncn = max_cn + 1;
   const int n_ang = A * P * nth, n_cn = A * A * ncn, nh = n_ang + n_cn + 1;
   int* h_ang = cell_bond_hist;
@@ -151,14 +133,16 @@ __global__ __launch_bounds__(256) void cell_bond_stats_kernel(const double* __re
   for (int k = tid; k < nh; k += 256) cell_bond_hist[k] = 0;
   __syncthreads();
   double L[9];
-  for (int k = 0; k < 9; ++k) L[k] = lattice[9 * (size_t)c + k];
+  cell_lattice_read(lattice, c, L);
   CellBondWave& W = s_wave[wave];
   for (int ci = c0 + wave; ci < c0 + nc; ci += kWaves) {   // uniform in a wavefront
     const int i = lo + ci, ti = type[i];
     if (ti < 0 || ti >= A) continue;
-    int e0, deg;
-    if (!cell_stat_row(row_ptr, n_bonds, i, &e0, &deg)) continue;
-    const double wi[3] = {cell_wrap(frac[3 * (size_t)i]), cell_wrap(frac[3 * (size_t)i + 1]), cell_wrap(frac[3 * (size_t)i + 2])};
+    int e0, e1;
+    if (!cell_row_read(row_ptr, N, n_bonds, i, &e0, &e1)) continue;   // row_ptr is not what the fill pass wrote
+    const int deg = e1 - e0;
+    double wi[3];
+    cell_wrapped_read(frac, i, wi);
     int nb0 = 0, nb1 = 0, nb2 = 0, nb3 = 0;
     for (int eb = 0; eb < deg; eb += 64) {
       const int e = eb + lane;
@@ -166,7 +150,7 @@ __global__ __launch_bounds__(256) void cell_bond_stats_kernel(const double* __re
       if (e < deg) {
         ja = bond_atom[e0 + e];
         sc = bond_shift[e0 + e];
-        if (ja >= lo && ja < hi && sc >= 0 && sc < kCellShiftCodes) {
+        if (cell_site_listed(lo, hi, ja, sc)) {
           tj = type[ja];
           if (tj < 0 || tj >= A) tj = -1;
         }
@@ -176,12 +160,9 @@ __global__ __launch_bounds__(256) void cell_bond_stats_kernel(const double* __re
       nb2 += __popcll(__ballot(tj == 2));
       nb3 += __popcll(__ballot(tj == 3));
       if (eb == 0) {   // the first 64 entries of the row, in row order
-        if (tj >= 0) {
-          const double wj[3] = {cell_wrap(frac[3 * (size_t)ja]), cell_wrap(frac[3 * (size_t)ja + 1]), cell_wrap(frac[3 * (size_t)ja + 2])};
-          int s[3];
+        if (tj >= 0) {   // cell_site_listed has passed the entry
           double r[3];
-          cell_shift_decode(sc, s);
-          cell_site_vector(wj, wi, s, L, r);
+          cell_listed_vector(frac, L, wi, ja, sc, r);
           W.v[3 * lane] = r[0];
           W.v[3 * lane + 1] = r[1];
           W.v[3 * lane + 2] = r[2];
@@ -232,22 +213,19 @@ __global__ __launch_bounds__(256) void cell_qn_kernel(const int* __restrict__ ty
                                                       unsigned long long* __restrict__ qn_hist) {
   __shared__ int h_qn[kStructMaxCn + 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c = tiles[2 * (size_t)blockIdx.x], c0 = tiles[2 * (size_t)blockIdx.x + 1];
-  if (c < 0 || c >= C) return;
-  const int lo = cell_ptr[c], hi = cell_ptr[c + 1];
-  if (lo < 0 || hi < lo || hi > N) return;
-  const int n = hi - lo;
-  if (c0 < 0 || c0 >= n || max_cn < 0 || max_cn > kStructMaxCn) return;
-  const int nc = min(kCellStatBondCentres, n - c0);
+  CellTile T;
+  if (!cell_tile_read<kCellStatBondCentres>(tiles + 2 * (size_t)blockIdx.x, cell_ptr, C, N, &T) || max_cn < 0 || max_cn > kStructMaxCn) return;
+  const int c = T.c, c0 = T.c0, lo = T.lo, hi = T.lo + T.n, nc = T.nc;
   if (tid <= kStructMaxCn) h_qn[tid] = 0;
   __syncthreads();
   for (int ci = c0 + wave; ci < c0 + nc; ci += kWaves) {   // uniform in a wavefront
     const int i = lo + ci;
-    int e0, deg;
-    if (type[i] != former || !cell_stat_row(row_ptr, n_bonds, i, &e0, &deg)) {
+    int e0, e1;
+    if (type[i] != former || !cell_row_read(row_ptr, N, n_bonds, i, &e0, &e1)) {
       if (lane == 0) qn[i] = -1;
       continue;
     }
+    const int deg = e1 - e0;
     int q = 0;
     for (int e = lane; e < deg; e += 64) {
       const int ja = bond_atom[e0 + e];

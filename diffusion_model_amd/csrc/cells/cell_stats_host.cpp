@@ -43,33 +43,6 @@ int cell_stat_bond_check(const char* who, int A, double dtheta, int max_cn, int 
   return EGNN_OK;
 }
 
-namespace {
-
-// the bonds of atom i of the cell [lo, hi), ascending by (atom, shift code): the loop of egnn_cell_env_host, with the axis cull of
-// the bond kernel.  -> the number of bonds; atom / code hold 27 (hi - lo) entries.
-int row_bonds(const double* w, const double* L, const double* reach, int lo, int hi, int i, double c2, int32_t* atom, int32_t* code) {
-  int n = 0;
-  for (int j = lo; j < hi; ++j)
-    for (int sx = -1; sx <= 1; ++sx) {
-      if (!(fabs(cell_delta(w[3 * (size_t)j], w[3 * (size_t)i], sx)) < reach[0])) continue;
-      for (int sy = -1; sy <= 1; ++sy) {
-        if (!(fabs(cell_delta(w[3 * (size_t)j + 1], w[3 * (size_t)i + 1], sy)) < reach[1])) continue;
-        for (int sz = -1; sz <= 1; ++sz) {
-          if (j == i && sx == 0 && sy == 0 && sz == 0) continue;
-          const int s[3] = {sx, sy, sz};
-          double r[3];
-          cell_site_vector(w + 3 * (size_t)j, w + 3 * (size_t)i, s, L, r);
-          if (!(cell_norm2(r) < c2)) continue;
-          atom[n] = j;
-          code[n++] = cell_shift_code(sx, sy, sz);
-        }
-      }
-    }
-  return n;
-}
-
-}  // namespace
-
 }  // namespace egnn
 
 using namespace egnn;
@@ -95,14 +68,12 @@ int egnn_cell_stats_host(int C, int A, const int32_t* cell_ptr, const double* la
   if (bonds)
     if (int rc = cell_stat_bond_check(who, A, dtheta, max_cn, former, bridge)) return rc;
   if (int rc = type_range_check(who, type, 0, N, A)) return rc;
-  for (size_t t = 0; t < 3 * (size_t)N; ++t)
-    if (!(fabs(frac[t]) < 1e15)) { set_error("%s: atom %d has a fractional coordinate that is not finite", who, (int)(t / 3)); return EGNN_EINVAL; }
+  if (int rc = cell_frac_finite_check(who, frac, 0, N)) return rc;
 
   int n_max = 0;
   for (int c = 0; c < C; ++c) n_max = cell_ptr[c + 1] - cell_ptr[c] > n_max ? cell_ptr[c + 1] - cell_ptr[c] : n_max;
   Scratch<double> w(3 * (size_t)N);
-  if (!w.p) { set_error("%s: out of memory", who); return EGNN_ENOMEM; }
-  for (size_t t = 0; t < 3 * (size_t)N; ++t) w[t] = cell_wrap(frac[t]);
+  if (int rc = cell_wrap_batch(who, N, frac, w)) return rc;
 
   // ---- ordered pairs over the image box ----
   if (pairs) {
@@ -160,7 +131,7 @@ int egnn_cell_stats_host(int C, int A, const int32_t* cell_ptr, const double* la
       cell_widths(L, width);
       for (int k = 0; k < 3; ++k) reach[k] = cutoff * (1.0 + 1e-6) / width[k];
       for (int i = lo; i < hi; ++i) {
-        const int deg = row_bonds(w.p, L, reach, lo, hi, i, c2, b_atom.p, b_code.p);
+        const int deg = cell_row_bonds(w.p, L, reach, lo, hi, i, c2, b_atom.p, b_code.p);
         const int ti = type[i];
         if (pass == 1) {   // Q^n
           if (ti != former) { qn[i] = -1; continue; }
@@ -174,11 +145,7 @@ int egnn_cell_stats_host(int C, int A, const int32_t* cell_ptr, const double* la
         for (int e = 0; e < deg; ++e) ++nb[type[b_atom[e]]];
         for (int b = 0; b < A; ++b) ++cn[c * n_cn + ((size_t)ti * A + b) * ncn + (nb[b] < max_cn ? nb[b] : max_cn)];
         if (deg > kMaxNeighbours) { ++overflow[c]; continue; }
-        for (int e = 0; e < deg; ++e) {
-          int s[3];
-          cell_shift_decode(b_code[e], s);
-          cell_site_vector(&w[3 * (size_t)b_atom[e]], &w[3 * (size_t)i], s, L, &vec[3 * (size_t)e]);
-        }
+        for (int e = 0; e < deg; ++e) cell_listed_vector(w.p, L, &w[3 * (size_t)i], b_atom[e], b_code[e], &vec[3 * (size_t)e]);
         for (int p = 0; p < deg; ++p)
           for (int q = p + 1; q < deg; ++q) {
             const int k = struct_angle_bin(&vec[3 * (size_t)p], &vec[3 * (size_t)q], dtheta, nth);

@@ -1,5 +1,6 @@
-// What the kernels of the evaluation families (eval/*.hip, cells/cell_env.hip) share: the steps of one wavefront, the reader of a
-// {graph, first centre, first neighbour} tile, and the one policy for raising a kernel's dynamic-LDS limit (lds_limit.h).
+// What the kernels of the evaluation families (eval/*.hip, and through cells/cell_device.h every cells/cell_*.hip) share: the steps
+// of one wavefront, the reader of a {graph, first centre, first neighbour} tile, and the one policy for raising a kernel's
+// dynamic-LDS limit (lds_limit.h).  What only the periodic-cell kernels share is in cells/cell_device.h.
 #pragma once
 #include "../common.h"
 #include "lds_limit.h"

@@ -5,36 +5,14 @@
 // Cases: the thin triclinic cell (image boxes 4 / 1 / 2 at 4.37 A) alone and in a batch with one-atom cells, every atom and a
 // scrambled centre list with a repeat, with and without the averages and q_lm, l_max = 0, 4 and 10; every bad-argument case.
 #include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <vector>
-
 #include "../../diffusion_model_amd/csrc/cells/cell_boo_math.h"
 #include "../../include/egnn_amd.h"
+#include "cell_fixtures.h"
 
 using namespace egnn;
+using namespace cell_fixtures;
 
 namespace {
-
-#define CHECK(cond, ...)                                         \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      fprintf(stderr, "FAILED %s:%d %s: ", __FILE__, __LINE__, #cond); \
-      fprintf(stderr, __VA_ARGS__);                              \
-      fprintf(stderr, "\n");                                     \
-      exit(1);                                                   \
-    }                                                            \
-  } while (0)
-
-uint64_t g_state = 24680;
-double uniform() {   // a small LCG: the program needs no library for its numbers
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  return (double)(g_state >> 11) / 9007199254740992.0;
-}
-
-double factorial(int n) { return n <= 1 ? 1.0 : n * factorial(n - 1); }
 
 struct Tables {
   std::vector<double> norm, val;
@@ -64,26 +42,6 @@ Tables stand_in_tables(int l_max) {
   return t;
 }
 
-struct Cells {
-  std::vector<int32_t> cell_ptr{0}, type;
-  std::vector<double> lattice, frac;
-  int C() const { return (int)cell_ptr.size() - 1; }
-  int N() const { return (int)type.size(); }
-};
-
-void add_cell(Cells& b, const double* L, int n, int A) {
-  for (int k = 0; k < 9; ++k) b.lattice.push_back(L[k]);
-  for (int i = 0; i < n; ++i) {
-    for (int k = 0; k < 3; ++k) b.frac.push_back(2.0 * uniform() - 0.5);   // some outside [0, 1)
-    b.type.push_back((int32_t)(uniform() * A) % A);
-  }
-  b.cell_ptr.push_back(b.N());
-}
-
-const double kThin[9] = {1.15, 0.0, 0.0, 0.4, 4.8, 0.0, 0.3, -0.5, 3.1};
-const double kCube[9] = {5.0, 0.0, 0.0, 0.0, 5.0, 0.0, 0.0, 0.0, 5.0};
-const double kCut = 4.37;
-
 struct Result {
   std::vector<double> out, qlm;
   std::vector<int32_t> n, n_solid;
@@ -110,6 +68,7 @@ Result boo(const Cells& b, int A, unsigned select, int l_max, const Tables& t, d
 }  // namespace
 
 int main() {
+  seed(24680);
   Cells thin, mixed;
   add_cell(thin, kThin, 12, 3);
   add_cell(mixed, kCube, 1, 3);

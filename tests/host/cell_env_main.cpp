@@ -6,61 +6,14 @@
 // simple-cubic cell of spacing 1.1 A (26 bonds per atom, 27 / 125 / 343 / 729 sites for 1-4 shells) at max_atoms = 729, which fits,
 // and 728, where the two scratch lists of max_atoms + 2 keys are at their fullest before the sentinel; and the ladder (five atoms
 // 0.41 A apart in a 2.05 A cell: 33 sites at 4 shells, shifts up to +-4, the ends of the code range).
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <vector>
-
 #include "../../diffusion_model_amd/csrc/cells/cell_math.h"
 #include "../../include/egnn_amd.h"
+#include "cell_fixtures.h"
 
 using namespace egnn;
+using namespace cell_fixtures;
 
 namespace {
-
-#define CHECK(cond, ...)                                         \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      fprintf(stderr, "FAILED %s:%d %s: ", __FILE__, __LINE__, #cond); \
-      fprintf(stderr, __VA_ARGS__);                              \
-      fprintf(stderr, "\n");                                     \
-      exit(1);                                                   \
-    }                                                            \
-  } while (0)
-
-struct Batch {
-  std::vector<int32_t> cell_ptr{0};
-  std::vector<double> lattice, frac;
-  std::vector<int32_t> type;
-  void add(double a, const std::vector<double>& f, const std::vector<int32_t>& t) {
-    const double L[9] = {a, 0, 0, 0, a, 0, 0, 0, a};
-    lattice.insert(lattice.end(), L, L + 9);
-    frac.insert(frac.end(), f.begin(), f.end());
-    type.insert(type.end(), t.begin(), t.end());
-    cell_ptr.push_back((int32_t)type.size());
-  }
-};
-
-void add_chain(Batch& b) { b.add(3.2, {0, 0, 0, 0.5, 0, 0}, {1, 0}); }
-
-void add_cristobalite(Batch& b) {
-  const double fcc[4][3] = {{0, 0, 0}, {0, .5, .5}, {.5, 0, .5}, {.5, .5, 0}};
-  const double arm[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
-  std::vector<double> f;
-  std::vector<int32_t> t;
-  for (int o = 0; o < 2; ++o)
-    for (int k = 0; k < 4; ++k) {
-      for (int x = 0; x < 3; ++x) f.push_back(fcc[k][x] + 0.25 * o);
-      t.push_back(1);
-    }
-  for (int k = 0; k < 4; ++k)
-    for (int m = 0; m < 4; ++m) {
-      for (int x = 0; x < 3; ++x) f.push_back(fcc[k][x] + arm[m][x] / 8.0 + 2.0);   // outside [0, 1): wrapped by the statement
-      t.push_back(0);
-    }
-  b.add(7.16, f, t);
-}
 
 void add_cubic_block(Batch& b) {   // 2 x 2 x 2 atoms, 1.1 A apart: neighbours at 1.1, 1.556 and 1.905 A, the next at 2.2 A
   std::vector<double> f;

@@ -4,59 +4,14 @@
 // pair totals of [0, 2.3) through the walk), a one-atom 7 A cell (no bond; 13 bins per axis at reach 3 and nothing within 1.5 A), an
 // empty cell alone and beside cristobalite, and refused arguments, which leave the lists alone.
 #include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <vector>
-
 #include "../../diffusion_model_amd/csrc/cells/cell_grid_math.h"
 #include "../../include/egnn_amd.h"
+#include "cell_fixtures.h"
 
 using namespace egnn;
+using namespace cell_fixtures;
 
 namespace {
-
-#define CHECK(cond, ...)                                         \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      fprintf(stderr, "FAILED %s:%d %s: ", __FILE__, __LINE__, #cond); \
-      fprintf(stderr, __VA_ARGS__);                              \
-      fprintf(stderr, "\n");                                     \
-      exit(1);                                                   \
-    }                                                            \
-  } while (0)
-
-struct Batch {
-  std::vector<int32_t> cell_ptr{0};
-  std::vector<double> lattice, frac;
-  std::vector<int32_t> type;
-  void add(double a, const std::vector<double>& f, const std::vector<int32_t>& t) {
-    const double L[9] = {a, 0, 0, 0, a, 0, 0, 0, a};
-    lattice.insert(lattice.end(), L, L + 9);
-    frac.insert(frac.end(), f.begin(), f.end());
-    type.insert(type.end(), t.begin(), t.end());
-    cell_ptr.push_back((int32_t)type.size());
-  }
-};
-
-void add_cristobalite(Batch& b) {
-  const double fcc[4][3] = {{0, 0, 0}, {0, .5, .5}, {.5, 0, .5}, {.5, .5, 0}};
-  const double arm[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
-  std::vector<double> f;
-  std::vector<int32_t> t;
-  for (int o = 0; o < 2; ++o)
-    for (int k = 0; k < 4; ++k) {
-      for (int x = 0; x < 3; ++x) f.push_back(fcc[k][x] + 0.25 * o);
-      t.push_back(1);
-    }
-  for (int k = 0; k < 4; ++k)
-    for (int m = 0; m < 4; ++m) {
-      for (int x = 0; x < 3; ++x) f.push_back(fcc[k][x] + arm[m][x] / 8.0 - 2.0);   // outside [0, 1): wrapped by the statement
-      t.push_back(0);
-    }
-  b.add(7.16, f, t);
-}
 
 struct Result {
   std::vector<int32_t> nb, atom_bin, bin_start, sorted_atom, bond_ptr, bond_atom, bond_shift;
@@ -102,7 +57,7 @@ Result run(const Batch& b, int A, double radius, int reach, bool bonds, double d
 int main() {
   {   // beta-cristobalite: 3 x 3 x 3 bins, every neighbour bin of every centre wraps
     Batch b;
-    add_cristobalite(b);
+    add_cristobalite(b, -2.0);
     Result r = run(b, 2, 2.0, 1, true, 0.0, 0);
     CHECK(r.nb[0] == 3 && r.nb[1] == 3 && r.nb[2] == 3, "nb %d %d %d", r.nb[0], r.nb[1], r.nb[2]);
     CHECK(r.bond_ptr[24] == 64, "%d bonds", r.bond_ptr[24]);
@@ -137,13 +92,13 @@ int main() {
     b.add(7.0, {}, {});
     Result r = run(b, 1, 2.0, 1, true, 0.1, 20);
     CHECK(r.n_bins == 27 && r.bond_ptr[0] == 0 && r.bin_start[27] == 0, "empty cell");
-    add_cristobalite(b);
+    add_cristobalite(b, -2.0);
     Result q = run(b, 2, 2.0, 1, true, 0.0, 0);
     CHECK(q.n_bins == 54 && q.bond_ptr[24] == 64 && q.bin_start[27] == 0 && q.bin_start[54] == 24, "empty cell beside cristobalite");
   }
   {   // refused arguments leave the lists alone
     Batch b;
-    add_cristobalite(b);
+    add_cristobalite(b, -2.0);
     int32_t nb[3] = {-7, -7, -7}, bond_ptr[25];
     int64_t n_bins = -7, counts[4 * 30];
     for (int64_t& v : counts) v = -7;

@@ -5,36 +5,14 @@
 // Cases: the thin triclinic cell (image boxes 4 / 1 / 2 at cut 4.37) and a batch of it with a one-atom cell, every atom and a
 // scrambled centre list with a repeat; the mean in one call and continued over two; every bad-argument case.
 #include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <vector>
-
 #include "../../diffusion_model_amd/csrc/cells/cell_soap_math.h"
 #include "../../include/egnn_amd.h"
+#include "cell_fixtures.h"
 
 using namespace egnn;
+using namespace cell_fixtures;
 
 namespace {
-
-#define CHECK(cond, ...)                                         \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      fprintf(stderr, "FAILED %s:%d %s: ", __FILE__, __LINE__, #cond); \
-      fprintf(stderr, __VA_ARGS__);                              \
-      fprintf(stderr, "\n");                                     \
-      exit(1);                                                   \
-    }                                                            \
-  } while (0)
-
-uint64_t g_state = 97531;
-double uniform() {   // a small LCG: the program needs no library for its numbers
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  return (double)(g_state >> 11) / 9007199254740992.0;
-}
-
-double factorial(int n) { return n <= 1 ? 1.0 : n * factorial(n - 1); }
 
 std::vector<double> stand_in_tables(double r_cut, int n_max, int l_max, double sigma) {
   const int L1 = l_max + 1;
@@ -58,26 +36,6 @@ std::vector<double> stand_in_tables(double r_cut, int n_max, int l_max, double s
   }
   return t;
 }
-
-struct Cells {
-  std::vector<int32_t> cell_ptr{0}, type;
-  std::vector<double> lattice, frac;
-  int C() const { return (int)cell_ptr.size() - 1; }
-  int N() const { return (int)type.size(); }
-};
-
-void add_cell(Cells& b, const double* L, int n, int A) {
-  for (int k = 0; k < 9; ++k) b.lattice.push_back(L[k]);
-  for (int i = 0; i < n; ++i) {
-    for (int k = 0; k < 3; ++k) b.frac.push_back(2.0 * uniform() - 0.5);   // some outside [0, 1)
-    b.type.push_back((int32_t)(uniform() * A) % A);
-  }
-  b.cell_ptr.push_back(b.N());
-}
-
-const double kThin[9] = {1.15, 0.0, 0.0, 0.4, 4.8, 0.0, 0.3, -0.5, 3.1};
-const double kCube[9] = {5.0, 0.0, 0.0, 0.0, 5.0, 0.0, 0.0, 0.0, 5.0};
-const double kCut = 4.37;
 
 // the two-call protocol: sizes, then lists of exactly the size learnt
 void sites(const Cells& b, const std::vector<int32_t>& centres, std::vector<int32_t>& row_ptr, std::vector<int32_t>& atom,
@@ -115,6 +73,7 @@ std::vector<double> soap(const Cells& b, int A, const std::vector<double>& table
 }  // namespace
 
 int main() {
+  seed(97531);
   const std::vector<double> tables = stand_in_tables(4.0, 3, 2, 0.1);
   Cells thin, mixed;
   add_cell(thin, kThin, 12, 3);

@@ -5,61 +5,14 @@
 // 48 tetrahedral and 16 straight angles, eight Q^4), nbins = 1, the exact 3 x 3 x 3 grid of spacing 0.7 A (92 bonds per atom: the
 // overflow beyond 64, CN still exact, max_cn = 64 at its largest) and refused arguments, which leave every output alone.
 #include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <vector>
-
 #include "../../diffusion_model_amd/csrc/cells/cell_stats_math.h"
 #include "../../include/egnn_amd.h"
+#include "cell_fixtures.h"
 
 using namespace egnn;
+using namespace cell_fixtures;
 
 namespace {
-
-#define CHECK(cond, ...)                                         \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      fprintf(stderr, "FAILED %s:%d %s: ", __FILE__, __LINE__, #cond); \
-      fprintf(stderr, __VA_ARGS__);                              \
-      fprintf(stderr, "\n");                                     \
-      exit(1);                                                   \
-    }                                                            \
-  } while (0)
-
-struct Batch {
-  std::vector<int32_t> cell_ptr{0};
-  std::vector<double> lattice, frac;
-  std::vector<int32_t> type;
-  void add(double a, const std::vector<double>& f, const std::vector<int32_t>& t) {
-    const double L[9] = {a, 0, 0, 0, a, 0, 0, 0, a};
-    lattice.insert(lattice.end(), L, L + 9);
-    frac.insert(frac.end(), f.begin(), f.end());
-    type.insert(type.end(), t.begin(), t.end());
-    cell_ptr.push_back((int32_t)type.size());
-  }
-};
-
-void add_chain(Batch& b) { b.add(3.2, {0, 0, 0, 0.5, 0, 0}, {1, 0}); }
-
-void add_cristobalite(Batch& b) {
-  const double fcc[4][3] = {{0, 0, 0}, {0, .5, .5}, {.5, 0, .5}, {.5, .5, 0}};
-  const double arm[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
-  std::vector<double> f;
-  std::vector<int32_t> t;
-  for (int o = 0; o < 2; ++o)
-    for (int k = 0; k < 4; ++k) {
-      for (int x = 0; x < 3; ++x) f.push_back(fcc[k][x] + 0.25 * o);
-      t.push_back(1);
-    }
-  for (int k = 0; k < 4; ++k)
-    for (int m = 0; m < 4; ++m) {
-      for (int x = 0; x < 3; ++x) f.push_back(fcc[k][x] + arm[m][x] / 8.0 + 2.0);   // outside [0, 1): wrapped by the statement
-      t.push_back(0);
-    }
-  b.add(7.16, f, t);
-}
 
 void add_grid(Batch& b) {   // 3 x 3 x 3 atoms, 0.7 A apart: 92 neighbours within 2.0 A (i^2 + j^2 + k^2 <= 8)
   std::vector<double> f;

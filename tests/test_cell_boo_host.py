@@ -170,5 +170,5 @@ def test_g_tables_are_symmetric_tensors_of_even_l_only():
 
 
 def test_cell_boo_host_under_sanitizers(tmp_path):
-    r = build_and_run(tmp_path, "cell_boo_main", ["cells/cell_boo_host.cpp", "cells/cell_soap_host.cpp", "host_logic.cpp"])
+    r = build_and_run(tmp_path, "cell_boo_main", ["cells/cell_boo_host.cpp", "cells/cell_soap_host.cpp", "cells/cell_host.cpp", "host_logic.cpp"])
     assert r.returncode == 0 and "CELL-BOO-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

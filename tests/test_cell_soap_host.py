@@ -174,5 +174,5 @@ def test_refusals():
 
 
 def test_cell_soap_host_under_sanitizers(tmp_path):
-    r = build_and_run(tmp_path, "cell_soap_main", ["cells/cell_soap_host.cpp", "host_logic.cpp"])
+    r = build_and_run(tmp_path, "cell_soap_main", ["cells/cell_soap_host.cpp", "cells/cell_host.cpp", "host_logic.cpp"])
     assert r.returncode == 0 and "CELL-SOAP-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

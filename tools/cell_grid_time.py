@@ -120,7 +120,7 @@ def main():
         _lib.check(lib.egnn_cell_bonds_grid_fill(*DC._grid_bond_args(cb, grid, CUTOFF), _lib.ptr(row_ptr), E, _lib.ptr(atom), _lib.ptr(code)))
 
     def pair_entry(cb, grid, counts):
-        _lib.check(lib.egnn_cell_pair_counts_grid(_lib.stream_ptr(), cb.C, cb.N, cb.A, *grid.args(cb), _lib.ptr(grid.sorted_frac),
+        _lib.check(lib.egnn_cell_pair_counts_grid(*grid.args(cb, A=True), _lib.ptr(grid.sorted_frac),
                                                   _lib.ptr(grid.sorted_type), DR, nbins, grid.reach, _lib.ptr(grid.tiles), grid.n_tiles,
                                                   _lib.ptr(counts)))
 

@@ -30,6 +30,7 @@ CELL_STAT_CENTRE_BLOCK, CELL_STAT_CHUNK, CELL_STAT_BOND_CENTRES, CELL_STAT_MAX_I
 # kCellGrid* of csrc/cells/cell_grid_math.h: bins per axis, the reach, and the keys of a bond row staged per wavefront
 CELL_GRID_MAX_BINS, CELL_GRID_MAX_REACH, CELL_GRID_ROW_KEYS = 256, 3, 128
 CELL_SOAP_MAX_BOX = 4     # kCellSoapMaxBox of csrc/cells/cell_soap_math.h: the image box the shift code holds
+EWALD_ATOM_CHUNK, EWALD_MAX_POWER = 1024, 64   # kEwaldAtomChunk, kEwaldMaxPower of csrc/cells/cell_ewald_math.h
 PREALIGN_MIN_ATOMS = 5    # kPrealignMinAtoms of csrc/eval/assign_host.h: atom 0 and its four nearest neighbours
 
 
@@ -215,6 +216,11 @@ SIGNATURES = {
     "egnn_cell_boo_invariants": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [C.c_uint, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, C.c_double, _i, _i, _vp, _i, _vp,
                                       _vp, _i] + [_vp] * 5),
     "egnn_cell_boo_host": (_i, [_i, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_uint, _i, _vp, _i, _vp, _vp, _vp, _i, C.c_double, _i, _i] + [_vp] * 5),
+    "egnn_cell_ewald_real": (_i, [_vp, _i, _i, _i] + [_vp] * 8 + [_i, _i] + [C.c_double] * 5 + [_i, _i, _vp, _i, _vp, _vp, _i] + [_vp] * 4),
+    "egnn_cell_ewald_amplitudes": (_i, [_vp, _i, _i, _i] + [_vp] * 11 + [C.c_double] * 4 + [_i, _vp, _i, _vp, _i, _vp, _vp]),
+    "egnn_cell_ewald_recip": (_i, [_vp, _i, _i, _i] + [_vp] * 9 + [C.c_double] * 4 + [_i, _i] + [_vp] * 3),
+    "egnn_cell_ewald_finish": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [C.c_double] * 4 + [_vp] * 8),
+    "egnn_cell_ewald_host": (_i, [_i, _i] + [_vp] * 6 + [_i, _i] + [C.c_double] * 5 + [_i] + [_vp] * 8),
     "egnn_sq_debye": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _vp, _i, _vp, _vp, _vp]),
     "egnn_sq_cell_plan": (_i, [_i, _vp, C.c_double, _vp, _vp]),
     "egnn_sq_cell_count": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),

@@ -22,6 +22,9 @@ bins only: O(n) instead of O(n^2), and bitwise the same outputs (``csrc/cells/ce
 ``neighbour_sites`` / ``soap_descriptors`` (``csrc/cells/cell_soap.hip``) reach every image inside a radius; ``bond_order`` and
 ``bond_order_profile`` (``csrc/cells/cell_boo.hip``) compute Steinhardt's bond-orientational order over those sites: q_l, w_l, the
 Lechner-Dellago averages and the ten Wolde-Frenkel solid-bond count (an extension: no file of the reference computes them).
+``lattice_energy`` (``csrc/cells/cell_ewald.hip``) is the energy and the forces of a cell of point charges with a short-range pair
+potential (``PairTable``; ``BKS`` for silica): an Ewald sum over those sites and over the reciprocal vectors of
+``structure_factor`` (an extension: no file of the reference computes an energy).
 
 The definitions (``csrc/cells/cell_math.h``) are those of the INFINITE lattice: a site is (atom, integer shift), a bond joins
 sites closer than the cutoff, an environment is what ``shells`` bonds reach.  Wherever the reference's search uses no bond that
@@ -520,13 +523,13 @@ def _sq_vector_tiles(counts) -> np.ndarray:
     return np.stack([ci, t * _lib.SQ_VECTOR_BLOCK], 1).astype(np.int32).reshape(-1, 2)
 
 
-class _SqCellRun:
-    """the reciprocal vectors of a batch of cells (plan, count pass, prefix sums, work list, outputs allocated); ``rho()`` and
-    ``shells()`` are the launches alone"""
+class _SqVectors:
+    """the reciprocal vectors of a batch of cells below ``q_max``: plan, count pass, prefix sums and the work list of blocks of 256
+    vectors; ``name`` is what the caller calls the bound"""
 
-    def __init__(self, cb: _CellBatch, q_max: float, dq: float, nbins: int):
+    def __init__(self, cb: _CellBatch, q_max: float, name: str = "q_max"):
         lib = _lib.lib()
-        self.cb, self.q_max, self.dq, self.nbins = cb, q_max, dq, nbins
+        self.cb, self.q_max = cb, q_max
         self.plan_h, n_rows_h = torch.zeros(cb.C, 4, dtype=torch.int32), torch.zeros(1, dtype=torch.int32)
         _lib.check(lib.egnn_sq_cell_plan(cb.C, _lib.ptr(cb.lattice_h), q_max, _lib.ptr(self.plan_h), _lib.ptr(n_rows_h)))
         self.n_rows, self.plan = int(n_rows_h), self.plan_h.to(cb.dev)
@@ -540,7 +543,7 @@ class _SqCellRun:
         self.counts = (self.vec_ptr64[1:] - self.vec_ptr64[:-1]).tolist()
         for c, n in enumerate(self.counts):
             if n > _lib.SQ_MAX_VECTORS:
-                raise ValueError(f"cell {c}: {n} reciprocal vectors below q_max = {q_max} (at most {_lib.SQ_MAX_VECTORS}; lower q_max)")
+                raise ValueError(f"cell {c}: {n} reciprocal vectors below {name} = {q_max} (at most {_lib.SQ_MAX_VECTORS}; lower {name})")
         self.K = K = int(self.vec_ptr64[-1])
         if K >= 2 ** 31:
             raise ValueError("more than 2^31 - 1 reciprocal vectors in the batch (fewer cells per call)")
@@ -548,6 +551,15 @@ class _SqCellRun:
         self.vec_ptr, self.row_ptr = self.vec_ptr_h.to(cb.dev), row_ptr64.to(torch.int32)
         tiles_h = _sq_vector_tiles(self.counts)
         self.n_tiles, self.tiles = len(tiles_h), torch.from_numpy(tiles_h).to(cb.dev)
+
+
+class _SqCellRun(_SqVectors):
+    """the vectors of a batch of cells and the outputs of the structure-factor launches, allocated; ``rho()`` and ``shells()`` are the
+    launches alone"""
+
+    def __init__(self, cb: _CellBatch, q_max: float, dq: float, nbins: int):
+        super().__init__(cb, q_max)
+        self.dq, self.nbins, K = dq, nbins, self.K
         self.hkl = _empty(K, 3, dtype=torch.int32, device=cb.dev)
         self.kabs = _empty(K, dtype=torch.float64, device=cb.dev)
         self.bins = _empty(K, dtype=torch.int32, device=cb.dev)
@@ -895,9 +907,14 @@ class SiteList:
 def _check_site_boxes(cb: _CellBatch, radius: float):
     """the refusals of csrc/cells/cell_soap_math.h, as ValueError naming the cell and its widths: the image box
     floor(radius / w_k) + 1 must stay within 4, the range of the shift code"""
+    _check_lattice_boxes(cb.lattice_h.numpy(), radius)
+
+
+def _check_lattice_boxes(lattices: np.ndarray, radius: float):
+    """``_check_site_boxes`` on the lattices [C, 9] alone: no device"""
     if not (math.isfinite(radius) and radius > 0.0):
         raise ValueError("the radius must be positive and finite")
-    widths, singular = _widths(cb.lattice_h.numpy())
+    widths, singular = _widths(lattices)
     for c, w in enumerate(widths):
         if singular[c]:
             raise ValueError(f"cell {c}: singular lattice")
@@ -1313,3 +1330,167 @@ def bond_order_profile(cells: Union[PeriodicCell, Sequence[PeriodicCell]], cutof
             b = torch.clamp((q_avg[rows] * bins).floor().long(), 0, bins - 1)          # [m, L1]
             hist[c, a] = torch.zeros(L1, bins, dtype=torch.int64).scatter_add_(1, b.T.contiguous(), torch.ones_like(b.T))
     return dict(count=count, solid_fraction=frac, q_avg_hist=hist, **means)
+
+
+# ---- lattice energy of periodic cells (csrc/cells/cell_ewald.hip) ---------------------------------------------------------------
+_EWALD_SLAB_BYTES = 256 << 20   # site lists of one slab of the real-space launch; the outputs do not depend on the slabs
+COULOMB_CONSTANT = 14.3996454784   # e^2 / (4 pi eps_0) in eV A
+
+
+class PairTable:
+    """Short-range pair potential u_ab(r) = A_ab exp(-b_ab r) - C_ab / r^6 + D_ab / r^n between atom types: ``A`` (eV), ``b`` (1/A),
+    ``C`` (eV A^6) and ``D`` (eV A^n; default none) are symmetric, finite [types, types] tables, ``n`` one integer in [1, 64] for
+    the whole table (24 is the customary repulsive fix of BKS)."""
+
+    def __init__(self, A, b, C, D=None, n: int = 24):
+        tabs = [np.array(t, dtype=np.float64) for t in (A, b, C)]
+        tabs.append(np.zeros_like(tabs[0]) if D is None else np.array(D, dtype=np.float64))
+        shape = tabs[0].shape
+        if len(shape) != 2 or shape[0] != shape[1] or not 1 <= shape[0] <= _lib.CELL_MAX_TYPES or any(t.shape != shape for t in tabs):
+            raise ValueError(f"the pair tables A, b, C, D must share one shape [types, types], 1 <= types <= {_lib.CELL_MAX_TYPES}")
+        for name, t in zip("AbCD", tabs):
+            if not np.all(np.isfinite(t)):
+                raise ValueError(f"pair table {name} is not finite")
+            if not np.array_equal(t, t.T):
+                raise ValueError(f"pair table {name} is not symmetric")
+        if int(n) != n or not 1 <= int(n) <= _lib.EWALD_MAX_POWER:
+            raise ValueError(f"the power n of D / r^n must be an integer in [1, {_lib.EWALD_MAX_POWER}]")
+        self.A, self.b, self.C, self.D, self.n = *tabs, int(n)
+
+    @property
+    def num_types(self) -> int:
+        return int(self.A.shape[0])
+
+    def tables(self) -> np.ndarray:
+        """float64 [4, types, types]: what the entries of include/egnn_amd.h take as ``pot``"""
+        return np.ascontiguousarray(np.stack([self.A, self.b, self.C, self.D]))
+
+
+class _Bks:
+    """van Beest, Kramer and van Santen's silica potential (Phys. Rev. Lett. 64, 1955 (1990)), type order (O, Si): ``charges`` and
+    the Buckingham ``potential`` (no Si-Si term, no D / r^n repulsion).  The numbers are stated from the publication, not pinned by
+    execution (INTEGRATION.md, "Lattice energy")."""
+    charges = (-1.2, 2.4)
+    potential = PairTable(A=[[1388.7730, 18003.7572], [18003.7572, 0.0]], b=[[2.76000, 4.87318], [4.87318, 0.0]],
+                          C=[[175.0000, 133.5381], [133.5381, 0.0]])
+
+
+BKS = _Bks()
+
+
+class CellEnergy:
+    """Lattice energy of C cells of N atoms in all, float64 on the device: ``energy`` [C] (eV), ``energy_per_atom`` [N],
+    ``forces`` [N, 3] (eV / A) or None, ``components`` [C, 5] and ``components_per_atom`` [N, 5] in the order real, reciprocal, self,
+    background, short; ``n_vectors`` int64 [C] on the host (half-space vectors below ``k_max``; zeros where no charge is set);
+    ``alpha`` (1 / A) and ``k_max`` (1 / A), the Ewald parameters used."""
+
+    def __init__(self, energy, energy_per_atom, forces, components, components_per_atom, n_vectors, alpha, k_max):
+        self.energy, self.energy_per_atom, self.forces, self.components = energy, energy_per_atom, forces, components
+        self.components_per_atom, self.n_vectors, self.alpha, self.k_max = components_per_atom, n_vectors, alpha, k_max
+
+
+def _ewald_setup(cell_list, charges, potential, r_cut, short_cut, accuracy, alpha, k_max, coulomb_constant):
+    """the host-side checks of ``lattice_energy`` and its parameters -> (A, charges float64 [A], pot [4, A, A] | None, n, r_cut,
+    short_cut, alpha, k_max, kappa).  No device."""
+    A = max(c.num_types for c in cell_list)
+    if A > _lib.CELL_MAX_TYPES:
+        raise ValueError(f"{A} atom types (at most {_lib.CELL_MAX_TYPES})")
+    q = np.array(charges.detach().cpu() if isinstance(charges, torch.Tensor) else charges, dtype=np.float64).reshape(-1)
+    if q.shape[0] != A:
+        raise ValueError(f"charges has {q.shape[0]} entries for {A} atom types (one charge per type)")
+    if not np.all(np.isfinite(q)):
+        raise ValueError("charges must be finite")
+    if potential is not None:
+        if not isinstance(potential, PairTable):
+            raise ValueError("potential must be a PairTable or None")
+        if potential.num_types != A:
+            raise ValueError(f"the pair tables are [{potential.num_types}, {potential.num_types}] for {A} atom types")
+    r_cut, accuracy, kappa = float(r_cut), float(accuracy), float(coulomb_constant)
+    short_cut = r_cut if short_cut is None else float(short_cut)
+    if not (math.isfinite(r_cut) and r_cut > 0.0):
+        raise ValueError("r_cut must be positive and finite")
+    if not (math.isfinite(short_cut) and 0.0 < short_cut <= r_cut):
+        raise ValueError(f"short_cut = {short_cut} must lie in (0, r_cut = {r_cut}]: short_cut > r_cut is not served")
+    if not 0.0 < accuracy < 1.0:
+        raise ValueError(f"accuracy = {accuracy} must lie in (0, 1)")
+    if not (math.isfinite(kappa) and kappa > 0.0):
+        raise ValueError("coulomb_constant must be positive and finite")
+    root = math.sqrt(-math.log(accuracy))
+    alpha = root / r_cut if alpha is None else float(alpha)
+    if not (math.isfinite(alpha) and alpha > 0.0):
+        raise ValueError("alpha must be positive and finite")
+    k_max = 2.0 * alpha * root if k_max is None else float(k_max)
+    if not (math.isfinite(k_max) and k_max > 0.0):
+        raise ValueError("k_max must be positive and finite")
+    lattices = np.stack([c.lattice.numpy().reshape(9) for c in cell_list])
+    _check_lattice_boxes(lattices, r_cut)
+    for c, L in enumerate(lattices.reshape(-1, 3, 3)):
+        need = int(math.floor(k_max * float(np.sqrt((L * L).sum(1)).max()) / (2 * math.pi)))
+        if need > 1023:
+            raise ValueError(f"cell {c}: k_max = {k_max} needs a Miller index of {need} (at most 1023; lower the accuracy demand or raise r_cut)")
+    pot = None if potential is None else potential.tables()
+    return A, np.ascontiguousarray(q), pot, (24 if potential is None else potential.n), r_cut, short_cut, alpha, k_max, kappa
+
+
+def lattice_energy(cells: Union[PeriodicCell, Sequence[PeriodicCell]], charges, potential: Optional[PairTable] = None, r_cut: float = 10.0,
+                   short_cut: Optional[float] = None, shift: bool = True, accuracy: float = 1e-8, alpha: Optional[float] = None,
+                   k_max: Optional[float] = None, coulomb_constant: float = COULOMB_CONSTANT, forces: bool = True, method: str = "auto",
+                   device=None, _slab_bytes: Optional[int] = None) -> CellEnergy:
+    """Energy (eV) and forces (eV / A) of periodic cells of point charges with a short-range pair potential
+    (csrc/cells/cell_ewald_math.h): ``charges`` one per atom type, ``potential`` a ``PairTable`` or None (Coulomb only);
+    ``lattice_energy(cells, BKS.charges, BKS.potential, short_cut=5.5)`` is BKS silica (types O, Si).  The Coulomb part is an Ewald
+    sum: real space over the ``neighbour_sites`` at ``r_cut`` (erfc(alpha r) / r), reciprocal space over the half-space vectors below
+    ``k_max`` (those of ``structure_factor`` at ``q_max = k_max``), the self term and the neutralising background of a charged cell;
+    ``alpha = sqrt(-ln accuracy) / r_cut`` and ``k_max = 2 alpha sqrt(-ln accuracy)`` unless given.  The pair potential acts on the
+    sites with r < ``short_cut`` (default ``r_cut``), shifted by u_ab(short_cut) with ``shift``.  ``method`` as in
+    ``neighbour_sites``.  ValueError: a wrong ``charges`` length, tables that do not fit, ``short_cut > r_cut``, ``accuracy`` outside
+    (0, 1), a cell too thin for the image box of 4, an index need above 1023, coincident atoms (naming the cell).  All fp64, every
+    sum in one fixed order: results are bitwise reproducible, the same for a cell alone and in a batch, and do not depend on the
+    slabs the site rows go through in; ``forces=False`` skips the force sums and leaves the energy bits unchanged.  The reciprocal
+    part is a direct sum, O(atoms x vectors) per cell."""
+    cell_list = _as_cells(cells)
+    A, q_h, pot_h, n, r_cut, short_cut, alpha, k_max, kappa = _ewald_setup(cell_list, charges, potential, r_cut, short_cut, accuracy, alpha,
+                                                                          k_max, coulomb_constant)
+    cb = _CellBatch(cell_list, device)
+    search = _SiteSearch(cb, r_cut, method)
+    lib, dev, N, C = _lib.lib(), cb.dev, cb.N, cb.C
+    forces = bool(forces)
+    q_ptr, pot_ptr = _lib.host_ptr(q_h), (None if pot_h is None else _lib.host_ptr(pot_h))
+    ewald = (kappa, alpha, r_cut, k_max)
+    real = _empty(N, 5, dtype=torch.float64, device=dev)
+    flag = torch.zeros(C, dtype=torch.int32, device=dev)
+    every, every_cell = _centres(cb, None)
+    step = max(1, int(_EWALD_SLAB_BYTES if _slab_bytes is None else _slab_bytes) // (8 * _slab_sites(cb, r_cut)))
+    head = cb.args(A=True, types=True)
+    for a0 in range(0, N, step):
+        a1 = min(N, a0 + step)
+        args, keep = _row_args(search, every[a0:a1], every_cell[a0:a1])
+        _lib.check(lib.egnn_cell_ewald_real(*head, q_ptr, pot_ptr, n, int(bool(shift)), kappa, alpha, r_cut, short_cut, k_max, int(forces), *args,
+                                            _lib.ptr(real[a0:a1]), _lib.ptr(flag)))
+    rec, n_vectors = None, torch.zeros(C, dtype=torch.int64)
+    if bool(np.any(q_h != 0.0)):
+        vecs = _SqVectors(cb, k_max, "k_max")
+        n_vectors = torch.tensor(vecs.counts, dtype=torch.int64)
+        hkl = _empty(vecs.K, 3, dtype=torch.int32, device=dev)
+        table = _empty(vecs.K, 5, dtype=torch.float64, device=dev)
+        rec = _empty(N, 4, dtype=torch.float64, device=dev)
+        amp_head = cb.args(A=True, types=True, host=(_lib.ptr(vecs.plan_h), _lib.ptr(vecs.vec_ptr_h)), dev=(_lib.ptr(vecs.plan), _lib.ptr(vecs.vec_ptr)))
+        _lib.check(lib.egnn_cell_ewald_amplitudes(*amp_head, q_ptr, *ewald, vecs.n_rows, _lib.ptr(vecs.row_ptr), vecs.K, _ptr_or_none(vecs.tiles),
+                                                  vecs.n_tiles, _ptr_or_none(hkl), _ptr_or_none(table)))
+        rec_head = cb.args(A=True, types=True, host=(_lib.ptr(vecs.vec_ptr_h),), dev=(_lib.ptr(vecs.vec_ptr),))
+        _lib.check(lib.egnn_cell_ewald_recip(*rec_head, q_ptr, *ewald, int(forces), vecs.K, _ptr_or_none(hkl), _ptr_or_none(table),
+                                             _ptr_or_none(rec)))
+    n_type = torch.empty(C, A, dtype=torch.int32, device=dev)
+    comp_atom = _empty(N, 5, dtype=torch.float64, device=dev)
+    e_atom = _empty(N, dtype=torch.float64, device=dev)
+    force = _empty(N, 3, dtype=torch.float64, device=dev) if forces else None
+    comp = torch.empty(C, 5, dtype=torch.float64, device=dev)
+    energy = torch.empty(C, dtype=torch.float64, device=dev)
+    _lib.check(lib.egnn_cell_ewald_finish(*cb.args(A=True, frac=False, types=True), q_ptr, *ewald, _ptr_or_none(real), _ptr_or_none(rec),
+                                          _lib.ptr(n_type), _ptr_or_none(comp_atom), _ptr_or_none(e_atom), _lib.ptr(force), _lib.ptr(comp),
+                                          _lib.ptr(energy)))
+    bad = torch.nonzero(flag.cpu()).reshape(-1).tolist()
+    if bad:
+        raise ValueError(f"cell {bad[0]}: coincident atoms (a site at distance 0 from its centre); the energy is not defined" +
+                         (f" (also cells {bad[1:]})" if len(bad) > 1 else ""))
+    return CellEnergy(energy, e_atom, force, comp, comp_atom, n_vectors, alpha, k_max)

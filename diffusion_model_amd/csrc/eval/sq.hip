@@ -8,9 +8,8 @@
 //
 // Work lists come from the caller (built from the sizes on the host).  A kernel trusts no entry: graph / cell, blocks and offsets
 // are checked against graph_ptr / vec_ptr / the plan, and every index a kernel forms lies inside the arrays the entry was given.
-#include "eval_device.h"
+#include "sq_device.h"
 #include "sq_host.h"
-#include "sq_math.h"
 
 namespace egnn {
 
@@ -115,26 +114,7 @@ __global__ __launch_bounds__(256) void sq_debye_finish_kernel(const int* __restr
 }
 
 // ---- cells: the vectors ----------------------------------------------------------------------------------------------------------
-// plan [C, 4] = {H, K, L, first row}: the index box of a cell and where its (h, k) rows start in the row arrays
-struct SqRow {
-  int h, k, Lb, row;
-  double Bm[9];
-};
-
-__device__ __forceinline__ bool sq_row_read(const int* __restrict__ plan, const double* __restrict__ lattice, int c, int local, int n_rows,
-                                            SqRow* R) {
-  const int H = plan[4 * c], K = plan[4 * c + 1];
-  R->Lb = plan[4 * c + 2];
-  if (H < 0 || H > kSqMaxIndex || K < 0 || K > kSqMaxIndex || R->Lb < 0 || R->Lb > kSqMaxIndex) return false;
-  if (local >= sq_box_rows(H, K)) return false;
-  R->row = plan[4 * c + 3] + local;
-  if (plan[4 * c + 3] < 0 || R->row < 0 || R->row >= n_rows) return false;
-  R->h = local / (2 * K + 1);
-  R->k = local % (2 * K + 1) - K;
-  double L[9];
-  for (int t = 0; t < 9; ++t) L[t] = lattice[9 * (size_t)c + t];
-  return sq_reciprocal(L, R->Bm);
-}
+// the (h, k) rows of a cell's index box are read by sq_row_read (sq_device.h)
 
 // one thread per (h, k) row of the index box of cell blockIdx.y: the number of its l that are vectors
 __global__ __launch_bounds__(256) void sq_cell_count_kernel(const int* __restrict__ plan, const double* __restrict__ lattice, double q_max,

@@ -892,6 +892,57 @@ int egnn_cell_boo_host(int C, int A, const int32_t* cell_ptr, const double* latt
                        int l_solid, double threshold, int averaged, int M, const int32_t* centre_atom, double* out, int32_t* n,
                        int32_t* n_solid, double* qlm);
 
+/* ---- lattice energy of periodic cells (csrc/cells/cell_ewald.hip; definitions in csrc/cells/cell_ewald_math.h) -----------------
+ * Ewald sum of point charges plus a short-range pair potential (Buckingham with an optional D / r^n term: BKS), per-atom energies
+ * (eV) and forces (eV / A).  An extension: no file of the reference computes an energy.  The model of a call, HOST arguments: A <= 4,
+ * charges double [A] (q_i = charges[type_i]); pot double [4, A, A] = the symmetric tables A, b, C, D of u_ab(r) = A exp(-b r) -
+ * C / r^6 + D / r^n or NULL (Coulomb only), 1 <= n <= 64, shift != 0 subtracts u_ab(short_cut); kappa the Coulomb constant, alpha
+ * the splitting parameter, 0 < short_cut <= r_cut, k_max: positive and finite.  Sites are those of egnn_cell_sites_* at cut = r_cut,
+ * vectors those of egnn_sq_cell_* at q_max = k_max (plan, count, prefix sums and tiles as there).  All fp64, no floating-point
+ * atomic: a sum is a lane's ascending running sum and one fixed butterfly over the wavefront, or an ascending running sum; results
+ * are bitwise reproducible and a cell gives the same bits in any batch and slab.  Host and device agree bitwise on membership and
+ * to rounding on values.  Bad arguments are EGNN_EINVAL with a message before anything is launched; a width <= r_cut / 4 and an
+ * index need above 1023 are refused as by egnn_cell_sites_count and egnn_sq_cell_plan.
+ *
+ * egnn_cell_ewald_real (an extension): the CSR and the centres as in egnn_cell_boo_qlm; d_real double [M, 5] = (e_real, e_short, F_x,
+ * F_y, F_z) of centre m (F zeros without forces); d_coincident int32 [C], zeroed by the caller, set to 1 for a cell with a site on
+ * its centre (r = 0: the site is left out).
+ * egnn_cell_ewald_amplitudes (an extension): d_hkl int32 [K, 3] and d_vec double [K, 5] = (k_x, k_y, k_z, g S^c, g S^s), g =
+ * exp(-k^2 / 4 alpha^2) / k^2, S^c + i S^s = sum_j q_j exp(i k . r_j) over the atoms in ascending order; d_tiles int32 [n_tiles, 2] =
+ * {cell, first vector (local, a multiple of 256)}.
+ * egnn_cell_ewald_recip (an extension): d_rec double [N, 4] = (e_rec, F_x, F_y, F_z) of every atom of the batch from the table.
+ * egnn_cell_ewald_finish (an extension): d_real double [N, 5] (centre m = atom m), d_rec double [N, 4] or NULL (no reciprocal part);
+ * d_n_type int32 [C, A] workspace; d_atom_components double [N, 5] = (real, reciprocal, self, background, short),
+ * d_energy_per_atom double [N], d_force double [N, 3] or NULL; d_components double [C, 5] and d_energy double [C], the sums over a
+ * cell's atoms in ascending order. */
+int egnn_cell_ewald_real(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                         const double* d_lattice, const double* d_frac, const int32_t* d_type, const double* charges, const double* pot, int n,
+                         int shift, double kappa, double alpha, double r_cut, double short_cut, double k_max, int forces, int n_rows,
+                         const int32_t* d_row_ptr, int T, const int32_t* d_site_atom, const int32_t* d_site_shift, int M,
+                         const int32_t* d_centre_atom, const int32_t* d_centre_row, double* d_real, int32_t* d_coincident);
+int egnn_cell_ewald_amplitudes(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* plan,
+                               const int32_t* vec_ptr, const int32_t* d_cell_ptr, const double* d_lattice, const int32_t* d_plan,
+                               const int32_t* d_vec_ptr, const double* d_frac, const int32_t* d_type, const double* charges, double kappa,
+                               double alpha, double r_cut, double k_max, int n_rows, const int32_t* d_row_ptr, int K, const int32_t* d_tiles,
+                               int n_tiles, int32_t* d_hkl, double* d_vec);
+int egnn_cell_ewald_recip(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* vec_ptr,
+                          const int32_t* d_cell_ptr, const double* d_lattice, const int32_t* d_vec_ptr, const double* d_frac,
+                          const int32_t* d_type, const double* charges, double kappa, double alpha, double r_cut, double k_max, int forces, int K,
+                          const int32_t* d_hkl, const double* d_vec, double* d_rec);
+int egnn_cell_ewald_finish(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                           const double* d_lattice, const int32_t* d_type, const double* charges, double kappa, double alpha, double r_cut,
+                           double k_max, const double* d_real, const double* d_rec, int32_t* d_n_type, double* d_atom_components,
+                           double* d_energy_per_atom, double* d_force, double* d_components, double* d_energy);
+/* Host statement of the four entries above (an extension): HOST pointers, no GPU, the same definitions in plain C++, walking the
+ * image box and the index box itself, every sum one ascending running sum.  energy [C], components [C, 5], energy_per_atom [N],
+ * n_vectors int64 [C] (0 where every charge is 0: no reciprocal part) and coincident int32 [C] are always written; atom_components
+ * [N, 5], n_sites int32 [N] (the sites of every atom inside r_cut) where given, force [N, 3] with forces != 0.  Also EGNN_EINVAL: a
+ * type outside [0, A), a coordinate that is not finite. */
+int egnn_cell_ewald_host(int C, int A, const int32_t* cell_ptr, const double* lattice, const double* frac, const int32_t* type,
+                         const double* charges, const double* pot, int n, int shift, double kappa, double alpha, double r_cut, double short_cut,
+                         double k_max, int forces, double* energy, double* components, double* energy_per_atom, double* atom_components,
+                         double* force, int32_t* n_sites, int64_t* n_vectors, int32_t* coincident);
+
 /* ---- structure factors (csrc/eval/sq.hip; definitions in csrc/eval/sq_math.h) -----------------------------------------------
  * Reciprocal-space statistics: Debye sums of clusters and reciprocal-lattice sums of periodic cells.  No file of the reference
  * computes them (an extension, like the rings).  All sums are fp64 in one fixed order, no floating-point atomic: results are

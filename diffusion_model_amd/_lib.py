@@ -221,6 +221,10 @@ SIGNATURES = {
     "egnn_cell_ewald_recip": (_i, [_vp, _i, _i, _i] + [_vp] * 9 + [C.c_double] * 4 + [_i, _i] + [_vp] * 3),
     "egnn_cell_ewald_finish": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [C.c_double] * 4 + [_vp] * 8),
     "egnn_cell_ewald_host": (_i, [_i, _i] + [_vp] * 6 + [_i, _i] + [C.c_double] * 5 + [_i] + [_vp] * 8),
+    "egnn_cell_ewald_virial_real": (_i, [_vp, _i, _i, _i] + [_vp] * 8 + [_i, _i] + [C.c_double] * 5 + [_i, _vp, _i, _vp, _vp, _i] + [_vp] * 4),
+    "egnn_cell_ewald_virial_recip": (_i, [_vp, _i, _i, _i] + [_vp] * 9 + [C.c_double] * 4 + [_i] + [_vp] * 3),
+    "egnn_cell_ewald_virial_finish": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [C.c_double] * 4 + [_vp] * 9),
+    "egnn_cell_ewald_virial_host": (_i, [_i, _i] + [_vp] * 6 + [_i, _i] + [C.c_double] * 5 + [_vp] * 8),
     "egnn_sq_debye": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _vp, _i, _vp, _vp, _vp]),
     "egnn_sq_cell_plan": (_i, [_i, _vp, C.c_double, _vp, _vp]),
     "egnn_sq_cell_count": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),

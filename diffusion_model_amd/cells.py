@@ -24,7 +24,8 @@ bins only: O(n) instead of O(n^2), and bitwise the same outputs (``csrc/cells/ce
 Lechner-Dellago averages and the ten Wolde-Frenkel solid-bond count (an extension: no file of the reference computes them).
 ``lattice_energy`` (``csrc/cells/cell_ewald.hip``) is the energy and the forces of a cell of point charges with a short-range pair
 potential (``PairTable``; ``BKS`` for silica): an Ewald sum over those sites and over the reciprocal vectors of
-``structure_factor`` (an extension: no file of the reference computes an energy).
+``structure_factor`` (an extension: no file of the reference computes an energy); with ``stress=True`` also the strain derivative of
+that energy, the stress tensor and the pressure (``csrc/cells/cell_stress_math.h``; ``strained`` builds the strained cells).
 
 The definitions (``csrc/cells/cell_math.h``) are those of the INFINITE lattice: a site is (atom, integer shift), a bond joins
 sites closer than the cutoff, an environment is what ``shells`` bonds reach.  Wherever the reference's search uses no bond that
@@ -1382,11 +1383,38 @@ class CellEnergy:
     """Lattice energy of C cells of N atoms in all, float64 on the device: ``energy`` [C] (eV), ``energy_per_atom`` [N],
     ``forces`` [N, 3] (eV / A) or None, ``components`` [C, 5] and ``components_per_atom`` [N, 5] in the order real, reciprocal, self,
     background, short; ``n_vectors`` int64 [C] on the host (half-space vectors below ``k_max``; zeros where no charge is set);
-    ``alpha`` (1 / A) and ``k_max`` (1 / A), the Ewald parameters used."""
+    ``alpha`` (1 / A) and ``k_max`` (1 / A), the Ewald parameters used.  With ``stress=True`` (None otherwise):
+    ``strain_derivative`` [C, 3, 3] (eV: dE / d eps_xy under L -> L (1 + eps), fractional coordinates and membership held),
+    ``strain_derivative_components`` [C, 5, 3, 3] (the same component order; the self block is zeros),
+    ``strain_derivative_per_atom`` [N, 3, 3], ``stress`` [C, 3, 3] = strain_derivative / V (eV / A^3, tension positive) and
+    ``pressure`` [C] = -tr stress / 3; every 3 x 3 form is filled from six stored numbers, so xy and yx are the same bits."""
 
-    def __init__(self, energy, energy_per_atom, forces, components, components_per_atom, n_vectors, alpha, k_max):
+    def __init__(self, energy, energy_per_atom, forces, components, components_per_atom, n_vectors, alpha, k_max, strain_derivative=None,
+                 strain_derivative_components=None, strain_derivative_per_atom=None, stress=None, pressure=None):
         self.energy, self.energy_per_atom, self.forces, self.components = energy, energy_per_atom, forces, components
         self.components_per_atom, self.n_vectors, self.alpha, self.k_max = components_per_atom, n_vectors, alpha, k_max
+        self.strain_derivative, self.strain_derivative_components = strain_derivative, strain_derivative_components
+        self.strain_derivative_per_atom, self.stress, self.pressure = strain_derivative_per_atom, stress, pressure
+
+
+EV_PER_A3_IN_GPA = 160.2176634   # 1 eV / A^3 in GPa: e = 1.602176634e-19 C exactly
+_VOIGT_3X3 = (0, 5, 4, 5, 1, 3, 4, 3, 2)   # the Voigt index (xx, yy, zz, yz, xz, xy) of every entry of a row-major 3 x 3 form
+
+
+def _voigt_to_3x3(six: torch.Tensor) -> torch.Tensor:
+    """[..., 6] -> [..., 3, 3], a gather: xy and yx are the same stored number"""
+    return six[..., list(_VOIGT_3X3)].reshape(*six.shape[:-1], 3, 3)
+
+
+def strained(cells: Union[PeriodicCell, Sequence[PeriodicCell]], strain):
+    """New ``PeriodicCell``s with lattice L (1 + eps) = L + L eps, the same fractional coordinates, types and id: the homogeneous
+    strain ``lattice_energy(..., stress=True)`` differentiates by.  ``strain`` is a finite [3, 3] form (float64).  A cell for a cell,
+    a list for a sequence.  Pure Python: no device."""
+    eps = torch.as_tensor(strain, dtype=torch.float64).detach().cpu()
+    if tuple(eps.shape) != (3, 3) or not bool(torch.isfinite(eps).all()):
+        raise ValueError("strain must be a finite [3, 3] form")
+    out = [PeriodicCell(c.lattice + c.lattice @ eps, c.frac, types=c.types, id=c.id, num_types=c.num_types) for c in _as_cells(cells)]
+    return out[0] if isinstance(cells, PeriodicCell) else out
 
 
 def _ewald_setup(cell_list, charges, potential, r_cut, short_cut, accuracy, alpha, k_max, coulomb_constant):
@@ -1435,7 +1463,7 @@ def _ewald_setup(cell_list, charges, potential, r_cut, short_cut, accuracy, alph
 def lattice_energy(cells: Union[PeriodicCell, Sequence[PeriodicCell]], charges, potential: Optional[PairTable] = None, r_cut: float = 10.0,
                    short_cut: Optional[float] = None, shift: bool = True, accuracy: float = 1e-8, alpha: Optional[float] = None,
                    k_max: Optional[float] = None, coulomb_constant: float = COULOMB_CONSTANT, forces: bool = True, method: str = "auto",
-                   device=None, _slab_bytes: Optional[int] = None) -> CellEnergy:
+                   device=None, _slab_bytes: Optional[int] = None, stress: bool = False) -> CellEnergy:
     """Energy (eV) and forces (eV / A) of periodic cells of point charges with a short-range pair potential
     (csrc/cells/cell_ewald_math.h): ``charges`` one per atom type, ``potential`` a ``PairTable`` or None (Coulomb only);
     ``lattice_energy(cells, BKS.charges, BKS.potential, short_cut=5.5)`` is BKS silica (types O, Si).  The Coulomb part is an Ewald
@@ -1447,18 +1475,21 @@ def lattice_energy(cells: Union[PeriodicCell, Sequence[PeriodicCell]], charges, 
     (0, 1), a cell too thin for the image box of 4, an index need above 1023, coincident atoms (naming the cell).  All fp64, every
     sum in one fixed order: results are bitwise reproducible, the same for a cell alone and in a batch, and do not depend on the
     slabs the site rows go through in; ``forces=False`` skips the force sums and leaves the energy bits unchanged.  The reciprocal
-    part is a direct sum, O(atoms x vectors) per cell."""
+    part is a direct sum, O(atoms x vectors) per cell.  ``stress=True`` adds the strain derivative of the energy, the stress tensor
+    and the pressure (csrc/cells/cell_stress_math.h; the attributes of ``CellEnergy``) by one more walk of the sites and one more of
+    the vectors, with or without ``forces``; every other output keeps its bits."""
     cell_list = _as_cells(cells)
     A, q_h, pot_h, n, r_cut, short_cut, alpha, k_max, kappa = _ewald_setup(cell_list, charges, potential, r_cut, short_cut, accuracy, alpha,
                                                                           k_max, coulomb_constant)
     cb = _CellBatch(cell_list, device)
     search = _SiteSearch(cb, r_cut, method)
     lib, dev, N, C = _lib.lib(), cb.dev, cb.N, cb.C
-    forces = bool(forces)
+    forces, stress = bool(forces), bool(stress)
     q_ptr, pot_ptr = _lib.host_ptr(q_h), (None if pot_h is None else _lib.host_ptr(pot_h))
     ewald = (kappa, alpha, r_cut, k_max)
     real = _empty(N, 5, dtype=torch.float64, device=dev)
     flag = torch.zeros(C, dtype=torch.int32, device=dev)
+    v_real = _empty(N, 12, dtype=torch.float64, device=dev) if stress else None
     every, every_cell = _centres(cb, None)
     step = max(1, int(_EWALD_SLAB_BYTES if _slab_bytes is None else _slab_bytes) // (8 * _slab_sites(cb, r_cut)))
     head = cb.args(A=True, types=True)
@@ -1467,6 +1498,10 @@ def lattice_energy(cells: Union[PeriodicCell, Sequence[PeriodicCell]], charges, 
         args, keep = _row_args(search, every[a0:a1], every_cell[a0:a1])
         _lib.check(lib.egnn_cell_ewald_real(*head, q_ptr, pot_ptr, n, int(bool(shift)), kappa, alpha, r_cut, short_cut, k_max, int(forces), *args,
                                             _lib.ptr(real[a0:a1]), _lib.ptr(flag)))
+        if stress:
+            _lib.check(lib.egnn_cell_ewald_virial_real(*head, q_ptr, pot_ptr, n, int(bool(shift)), kappa, alpha, r_cut, short_cut, k_max, *args,
+                                                       _lib.ptr(v_real[a0:a1]), _lib.ptr(flag)))
+    v_rec = None
     rec, n_vectors = None, torch.zeros(C, dtype=torch.int64)
     if bool(np.any(q_h != 0.0)):
         vecs = _SqVectors(cb, k_max, "k_max")
@@ -1480,6 +1515,10 @@ def lattice_energy(cells: Union[PeriodicCell, Sequence[PeriodicCell]], charges, 
         rec_head = cb.args(A=True, types=True, host=(_lib.ptr(vecs.vec_ptr_h),), dev=(_lib.ptr(vecs.vec_ptr),))
         _lib.check(lib.egnn_cell_ewald_recip(*rec_head, q_ptr, *ewald, int(forces), vecs.K, _ptr_or_none(hkl), _ptr_or_none(table),
                                              _ptr_or_none(rec)))
+        if stress:
+            v_rec = _empty(N, 6, dtype=torch.float64, device=dev)
+            _lib.check(lib.egnn_cell_ewald_virial_recip(*rec_head, q_ptr, *ewald, vecs.K, _ptr_or_none(hkl), _ptr_or_none(table),
+                                                        _ptr_or_none(v_rec)))
     n_type = torch.empty(C, A, dtype=torch.int32, device=dev)
     comp_atom = _empty(N, 5, dtype=torch.float64, device=dev)
     e_atom = _empty(N, dtype=torch.float64, device=dev)
@@ -1489,8 +1528,20 @@ def lattice_energy(cells: Union[PeriodicCell, Sequence[PeriodicCell]], charges, 
     _lib.check(lib.egnn_cell_ewald_finish(*cb.args(A=True, frac=False, types=True), q_ptr, *ewald, _ptr_or_none(real), _ptr_or_none(rec),
                                           _lib.ptr(n_type), _ptr_or_none(comp_atom), _ptr_or_none(e_atom), _lib.ptr(force), _lib.ptr(comp),
                                           _lib.ptr(energy)))
+    extra = {}
+    if stress:
+        d_comp_atom = _empty(N, 5, 6, dtype=torch.float64, device=dev)
+        d_atom = _empty(N, 6, dtype=torch.float64, device=dev)
+        d_comp = torch.empty(C, 5, 6, dtype=torch.float64, device=dev)
+        d_cell, sigma = torch.empty(C, 6, dtype=torch.float64, device=dev), torch.empty(C, 6, dtype=torch.float64, device=dev)
+        pressure = torch.empty(C, dtype=torch.float64, device=dev)
+        _lib.check(lib.egnn_cell_ewald_virial_finish(*cb.args(A=True, frac=False, types=True), q_ptr, *ewald, _ptr_or_none(v_real),
+                                                     _ptr_or_none(v_rec), _lib.ptr(n_type), _ptr_or_none(d_comp_atom), _ptr_or_none(d_atom),
+                                                     _lib.ptr(d_comp), _lib.ptr(d_cell), _lib.ptr(sigma), _lib.ptr(pressure)))
+        extra = dict(strain_derivative=_voigt_to_3x3(d_cell), strain_derivative_components=_voigt_to_3x3(d_comp),
+                     strain_derivative_per_atom=_voigt_to_3x3(d_atom), stress=_voigt_to_3x3(sigma), pressure=pressure)
     bad = torch.nonzero(flag.cpu()).reshape(-1).tolist()
     if bad:
         raise ValueError(f"cell {bad[0]}: coincident atoms (a site at distance 0 from its centre); the energy is not defined" +
                          (f" (also cells {bad[1:]})" if len(bad) > 1 else ""))
-    return CellEnergy(energy, e_atom, force, comp, comp_atom, n_vectors, alpha, k_max)
+    return CellEnergy(energy, e_atom, force, comp, comp_atom, n_vectors, alpha, k_max, **extra)

@@ -58,6 +58,50 @@ int cell_ewald_batch_check(const char* who, int C, int N, int A, const int32_t* 
   return sq_cells_check(who, C, A, cell_ptr, lattice, k_max, nullptr);
 }
 
+int cell_ewald_vector_table(const char* who, int c, const EwaldModel& P, const double* L, const double* w, const int32_t* type, int na,
+                            int64_t* n_vectors, Scratch<int32_t>* hkl_out, Scratch<double>* tab_out) {
+  const bool charged = cell_ewald_charged(P);
+  int64_t nv = 0;
+  double Bm[9];
+  int need[3];
+  sq_reciprocal(L, Bm);
+  sq_index_need(L, P.k_max, need);
+  const int H = sq_index_box(need[0]), Kb = sq_index_box(need[1]), Lb = sq_index_box(need[2]);
+  if (charged)
+    for (int h = 0; h <= H; ++h)
+      for (int k = -Kb; k <= Kb; ++k) nv += sq_row_vectors(h, k, Lb, Bm, P.k_max, [](int, int, double) {});
+  if (nv > kSqMaxVectors) {
+    set_error("%s: cell %d has %lld vectors below k_max (at most %d; lower k_max)", who, c, (long long)nv, kSqMaxVectors);
+    return EGNN_EINVAL;
+  }
+  *n_vectors = nv;
+  Scratch<int32_t>& hkl = *hkl_out;
+  Scratch<double>& tab = *tab_out;
+  if (!hkl.reset(3 * (size_t)nv) || !tab.reset(5 * (size_t)nv)) { set_error("%s: out of memory", who); return EGNN_ENOMEM; }
+  if (charged) {
+    size_t v = 0;
+    for (int h = 0; h <= H; ++h)
+      for (int k = -Kb; k <= Kb; ++k)
+        sq_row_vectors(h, k, Lb, Bm, P.k_max, [&](int, int l, double k2) {
+          double sc = 0.0, ss = 0.0;
+          for (int j = 0; j < na; ++j) {
+            double sn, cs;
+            sq_phase_sincos(sq_phase(h, k, l, w + 3 * (size_t)j), &sn, &cs);
+            const double qj = P.charge[type[j]];
+            sc += qj * cs;
+            ss += qj * sn;
+          }
+          const double g = ewald_g(k2, P.alpha);
+          hkl[3 * v] = h; hkl[3 * v + 1] = k; hkl[3 * v + 2] = l;
+          ewald_kvec(h, k, l, Bm, tab.p + 5 * v);
+          tab[5 * v + 3] = g * sc;
+          tab[5 * v + 4] = g * ss;
+          ++v;
+        });
+  }
+  return EGNN_OK;
+}
+
 }  // namespace egnn
 
 using namespace egnn;
@@ -79,7 +123,6 @@ int egnn_cell_ewald_host(int C, int A, const int32_t* cell_ptr, const double* la
   if (int rc = cell_ewald_batch_check(who, C, N, A, cell_ptr, lattice, r_cut, k_max)) return rc;
   if (N > 0 && (!frac || !type)) { set_error("bad %s arguments (frac and type given)", who); return EGNN_EINVAL; }
   if (int rc = cell_inputs_check(who, N, frac, type, A, 0, nullptr)) return rc;
-  const bool charged = cell_ewald_charged(P);
   const double cut2 = r_cut * r_cut;
   for (int c = 0; c < C; ++c) {
     const int lo = cell_ptr[c], hi = cell_ptr[c + 1], na = hi - lo;
@@ -93,43 +136,10 @@ int egnn_cell_ewald_host(int C, int A, const int32_t* cell_ptr, const double* la
     const double Q = ewald_cell_charge(P, n_type);
     // the vectors of the cell and their amplitudes
     int64_t nv = 0;
-    double Bm[9];
-    int need[3];
-    sq_reciprocal(L, Bm);
-    sq_index_need(L, k_max, need);
-    const int H = sq_index_box(need[0]), Kb = sq_index_box(need[1]), Lb = sq_index_box(need[2]);
-    if (charged)
-      for (int h = 0; h <= H; ++h)
-        for (int k = -Kb; k <= Kb; ++k) nv += sq_row_vectors(h, k, Lb, Bm, k_max, [](int, int, double) {});
-    if (nv > kSqMaxVectors) {
-      set_error("%s: cell %d has %lld vectors below k_max (at most %d; lower k_max)", who, c, (long long)nv, kSqMaxVectors);
-      return EGNN_EINVAL;
-    }
+    Scratch<int32_t> hkl(0);
+    Scratch<double> tab(0);
+    if (int rc = cell_ewald_vector_table(who, c, P, L, w.p, type + lo, na, &nv, &hkl, &tab)) return rc;
     n_vectors[c] = nv;
-    Scratch<int32_t> hkl(3 * (size_t)nv);
-    Scratch<double> tab(5 * (size_t)nv);
-    if (!hkl.p || !tab.p) { set_error("%s: out of memory", who); return EGNN_ENOMEM; }
-    if (charged) {
-      size_t v = 0;
-      for (int h = 0; h <= H; ++h)
-        for (int k = -Kb; k <= Kb; ++k)
-          sq_row_vectors(h, k, Lb, Bm, k_max, [&](int, int l, double k2) {
-            double sc = 0.0, ss = 0.0;
-            for (int j = 0; j < na; ++j) {
-              double sn, cs;
-              sq_phase_sincos(sq_phase(h, k, l, w.p + 3 * (size_t)j), &sn, &cs);
-              const double qj = P.charge[type[lo + j]];
-              sc += qj * cs;
-              ss += qj * sn;
-            }
-            const double g = ewald_g(k2, P.alpha);
-            hkl[3 * v] = h; hkl[3 * v + 1] = k; hkl[3 * v + 2] = l;
-            ewald_kvec(h, k, l, Bm, tab.p + 5 * v);
-            tab[5 * v + 3] = g * sc;
-            tab[5 * v + 4] = g * ss;
-            ++v;
-          });
-    }
     int box[3];
     double width[3];
     cell_soap_box(L, r_cut, box, width);

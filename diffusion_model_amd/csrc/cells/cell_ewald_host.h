@@ -16,6 +16,11 @@ int cell_ewald_model_check(const char* who, int A, const double* charges, const 
 // the batch of an entry: the image box of r_cut within 4 (cell_soap_batch_check) and the index need of k_max within the limit of
 // sq_index_need (sq_cells_check)
 int cell_ewald_batch_check(const char* who, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, double r_cut, double k_max);
+// the vector table of cell c for the host statements (egnn_cell_ewald_host, egnn_cell_ewald_virial_host): the half-space vectors
+// below P.k_max in ascending (h, k, l) and (k_x, k_y, k_z, g S^c, g S^s) of each, the amplitudes over the na atoms (wrapped
+// coordinates w [na, 3], types type [na]) in ascending order; none where every charge is 0.  EGNN_EINVAL above kSqMaxVectors.
+int cell_ewald_vector_table(const char* who, int c, const EwaldModel& P, const double* L, const double* w, const int32_t* type, int na,
+                            int64_t* n_vectors, Scratch<int32_t>* hkl, Scratch<double>* table);
 inline bool cell_ewald_charged(const EwaldModel& P) {
   for (int a = 0; a < P.A; ++a)
     if (P.charge[a] != 0.0) return true;

@@ -943,6 +943,45 @@ int egnn_cell_ewald_host(int C, int A, const int32_t* cell_ptr, const double* la
                          double k_max, int forces, double* energy, double* components, double* energy_per_atom, double* atom_components,
                          double* force, int32_t* n_sites, int64_t* n_vectors, int32_t* coincident);
 
+/* ---- strain derivative of the lattice energy: Ewald virial, stress, pressure (csrc/cells/cell_ewald.hip, section 5; definitions
+ * in csrc/cells/cell_stress_math.h) ------------------------------------------------------------------------------------------
+ * D_xy = dE / d eps_xy (eV) under a homogeneous strain L -> L (1 + eps) with the fractional coordinates, alpha, the cutoffs and the
+ * membership of sites and vectors held; six numbers in Voigt order xx, yy, zz, yz, xz, xy; split per atom and per component (real,
+ * reciprocal, self = 0, background, short) as the energy is.  stress = D / V (eV / A^3, tension positive), pressure = -(s_xx +
+ * s_yy + s_zz) / 3.  An extension: no file of the reference computes a stress.  The model, the sites, the vector table, the orders
+ * of the sums, the checks and the refusals are those of the lattice-energy entries above; the entries of the energy are not
+ * changed by these and produce the same bits with or without them.
+ *
+ * egnn_cell_ewald_virial_real (an extension): the arguments of egnn_cell_ewald_real without `forces`; d_virial double [M, 12] =
+ * D_real (six) and D_short (six) of centre m; d_coincident as there.
+ * egnn_cell_ewald_virial_recip (an extension): the arguments of egnn_cell_ewald_recip without `forces`, the table of
+ * egnn_cell_ewald_amplitudes; d_virial double [N, 6] = D_reciprocal of every atom of the batch.
+ * egnn_cell_ewald_virial_finish (an extension): d_virial_real double [N, 12] (centre m = atom m), d_virial_recip double [N, 6] or
+ * NULL (no reciprocal part); d_n_type int32 [C, A] workspace; d_atom_components double [N, 5, 6], d_per_atom double [N, 6];
+ * d_components double [C, 5, 6] and d_strain double [C, 6], the sums over a cell's atoms in ascending order; d_stress double [C, 6],
+ * d_pressure double [C]. */
+int egnn_cell_ewald_virial_real(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                                const double* d_lattice, const double* d_frac, const int32_t* d_type, const double* charges, const double* pot,
+                                int n, int shift, double kappa, double alpha, double r_cut, double short_cut, double k_max, int n_rows,
+                                const int32_t* d_row_ptr, int T, const int32_t* d_site_atom, const int32_t* d_site_shift, int M,
+                                const int32_t* d_centre_atom, const int32_t* d_centre_row, double* d_virial, int32_t* d_coincident);
+int egnn_cell_ewald_virial_recip(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* vec_ptr,
+                                 const int32_t* d_cell_ptr, const double* d_lattice, const int32_t* d_vec_ptr, const double* d_frac,
+                                 const int32_t* d_type, const double* charges, double kappa, double alpha, double r_cut, double k_max, int K,
+                                 const int32_t* d_hkl, const double* d_vec, double* d_virial);
+int egnn_cell_ewald_virial_finish(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                                  const double* d_lattice, const int32_t* d_type, const double* charges, double kappa, double alpha, double r_cut,
+                                  double k_max, const double* d_virial_real, const double* d_virial_recip, int32_t* d_n_type,
+                                  double* d_atom_components, double* d_per_atom, double* d_components, double* d_strain, double* d_stress,
+                                  double* d_pressure);
+/* Host statement of the three entries above (an extension): HOST pointers, no GPU, the same definitions in plain C++, every sum one
+ * ascending running sum.  strain [C, 6], components [C, 5, 6], per_atom [N, 6], stress [C, 6], pressure [C], n_vectors int64 [C]
+ * and coincident int32 [C] are always written; atom_components [N, 5, 6] where given.  The refusals of egnn_cell_ewald_host. */
+int egnn_cell_ewald_virial_host(int C, int A, const int32_t* cell_ptr, const double* lattice, const double* frac, const int32_t* type,
+                                const double* charges, const double* pot, int n, int shift, double kappa, double alpha, double r_cut,
+                                double short_cut, double k_max, double* strain, double* components, double* per_atom, double* atom_components,
+                                double* stress, double* pressure, int64_t* n_vectors, int32_t* coincident);
+
 /* ---- structure factors (csrc/eval/sq.hip; definitions in csrc/eval/sq_math.h) -----------------------------------------------
  * Reciprocal-space statistics: Debye sums of clusters and reciprocal-lattice sums of periodic cells.  No file of the reference
  * computes them (an extension, like the rings).  All sums are fp64 in one fixed order, no floating-point atomic: results are

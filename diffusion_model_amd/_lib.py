@@ -31,6 +31,9 @@ CELL_STAT_CENTRE_BLOCK, CELL_STAT_CHUNK, CELL_STAT_BOND_CENTRES, CELL_STAT_MAX_I
 CELL_GRID_MAX_BINS, CELL_GRID_MAX_REACH, CELL_GRID_ROW_KEYS = 256, 3, 128
 CELL_SOAP_MAX_BOX = 4     # kCellSoapMaxBox of csrc/cells/cell_soap_math.h: the image box the shift code holds
 EWALD_ATOM_CHUNK, EWALD_MAX_POWER = 1024, 64   # kEwaldAtomChunk, kEwaldMaxPower of csrc/cells/cell_ewald_math.h
+# kRelax* of csrc/cells/cell_relax_math.h: the status codes and the columns of the scalars and counters of a relaxation
+RELAX_CONVERGED, RELAX_COINCIDENT, RELAX_NOT_FINITE, RELAX_STUCK = 1, 3, 4, 5
+RELAX_SCALARS, RELAX_COUNTERS = 5, 4
 PREALIGN_MIN_ATOMS = 5    # kPrealignMinAtoms of csrc/eval/assign_host.h: atom 0 and its four nearest neighbours
 
 
@@ -225,6 +228,10 @@ SIGNATURES = {
     "egnn_cell_ewald_virial_recip": (_i, [_vp, _i, _i, _i] + [_vp] * 9 + [C.c_double] * 4 + [_i] + [_vp] * 3),
     "egnn_cell_ewald_virial_finish": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [C.c_double] * 4 + [_vp] * 9),
     "egnn_cell_ewald_virial_host": (_i, [_i, _i] + [_vp] * 6 + [_i, _i] + [C.c_double] * 5 + [_vp] * 8),
+    "egnn_cell_relax_real": (_i, [_vp, _i, _i, _i] + [_vp] * 8 + [_i, _i] + [C.c_double] * 6 + [_i, _vp, _i, _vp, _vp, _i] + [_vp] * 4),
+    "egnn_cell_relax_step": (_i, [_vp, _i, _i] + [_vp] * 7 + [C.c_double, _i] + [C.c_double] * 6 + [_i, C.c_double] + [_vp] * 10),
+    "egnn_cell_relax_step_host": (_i, [_i, _i] + [_vp] * 5 + [C.c_double, _i] + [C.c_double] * 6 + [_i, C.c_double] + [_vp] * 10),
+    "egnn_cell_relax_host": (_i, [_i, _i] + [_vp] * 6 + [_i, _i] + [C.c_double] * 7 + [_i] + [C.c_double] * 6 + [_i, C.c_double] + [_vp] * 12),
     "egnn_sq_debye": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _vp, _i, _vp, _vp, _vp]),
     "egnn_sq_cell_plan": (_i, [_i, _vp, C.c_double, _vp, _vp]),
     "egnn_sq_cell_count": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),

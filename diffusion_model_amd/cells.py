@@ -26,6 +26,8 @@ Lechner-Dellago averages and the ten Wolde-Frenkel solid-bond count (an extensio
 potential (``PairTable``; ``BKS`` for silica): an Ewald sum over those sites and over the reciprocal vectors of
 ``structure_factor`` (an extension: no file of the reference computes an energy); with ``stress=True`` also the strain derivative of
 that energy, the stress tensor and the pressure (``csrc/cells/cell_stress_math.h``; ``strained`` builds the strained cells).
+``relax`` (``csrc/cells/cell_relax.hip``) moves the atoms of fixed cells down that energy by FIRE, on the device, over site lists
+that are held while no atom has moved further than half a skin (an extension: no file of the reference relaxes a structure).
 
 The definitions (``csrc/cells/cell_math.h``) are those of the INFINITE lattice: a site is (atom, integer shift), a bond joins
 sites closer than the cutoff, an environment is what ``shells`` bonds reach.  Wherever the reference's search uses no bond that
@@ -1545,3 +1547,214 @@ def lattice_energy(cells: Union[PeriodicCell, Sequence[PeriodicCell]], charges, 
         raise ValueError(f"cell {bad[0]}: coincident atoms (a site at distance 0 from its centre); the energy is not defined" +
                          (f" (also cells {bad[1:]})" if len(bad) > 1 else ""))
     return CellEnergy(energy, e_atom, force, comp, comp_atom, n_vectors, alpha, k_max, **extra)
+
+
+# ---- relaxation of periodic cells (csrc/cells/cell_relax.hip) -------------------------------------------------------------------
+_RELAX_LIST_BYTES = 1 << 30   # the held site lists of one call (atom and shift code, 8 bytes a site), all cells together
+
+
+class FireParameters:
+    """The parameters of FIRE (Bitzek, Koskinen, Gaehler, Moseler and Gumbsch, Phys. Rev. Lett. 97, 170201 (2006)) as commonly used,
+    unit mass 1: first time step ``dt`` and its bound ``dt_max``, ``n_min`` downhill steps before the step grows by ``f_inc``, the
+    cut ``f_dec`` after an uphill step, the mixing ``a_start`` and its decay ``f_a``, and ``max_step`` (A), the largest move of one
+    atom in one step.  The numbers are stated from the publication, not pinned by execution ("Relaxation")."""
+
+    def __init__(self, dt: float = 0.1, dt_max: float = 1.0, n_min: int = 5, f_inc: float = 1.1, f_dec: float = 0.5, a_start: float = 0.1,
+                 f_a: float = 0.99, max_step: float = 0.2):
+        self.dt, self.dt_max, self.n_min, self.f_inc = float(dt), float(dt_max), int(n_min), float(f_inc)
+        self.f_dec, self.a_start, self.f_a, self.max_step = float(f_dec), float(a_start), float(f_a), float(max_step)
+        pos = lambda v: math.isfinite(v) and v > 0.0
+        if not (pos(self.dt) and pos(self.dt_max) and self.dt <= self.dt_max):
+            raise ValueError("FIRE needs 0 < dt <= dt_max")
+        if n_min != self.n_min or self.n_min < 0:
+            raise ValueError("FIRE needs an integer n_min >= 0")
+        if not (pos(self.f_inc) and self.f_inc >= 1.0 and 0.0 < self.f_dec < 1.0 and 0.0 < self.a_start <= 1.0 and 0.0 < self.f_a <= 1.0):
+            raise ValueError("FIRE needs f_inc >= 1, 0 < f_dec < 1, 0 < a_start <= 1 and 0 < f_a <= 1")
+        if not pos(self.max_step):
+            raise ValueError("max_step must be positive and finite")
+
+    def step_args(self):
+        """(dt_max, n_min, f_inc, f_dec, a_start, f_a, max_step): what the step entries of include/egnn_amd.h take"""
+        return (self.dt_max, self.n_min, self.f_inc, self.f_dec, self.a_start, self.f_a, self.max_step)
+
+
+class Relaxation:
+    """What ``relax`` returns for C cells of N atoms in all, float64 on the device unless noted: ``cells`` (new ``PeriodicCell``s at the
+    final coordinates, on the host), ``frac`` [N, 3] (unwrapped since a cell's last list build), ``energy`` and ``initial_energy`` [C]
+    (eV), ``forces`` [N, 3] at the final coordinates, ``max_force`` [C], ``steps`` int32 [C] (the moves made), ``converged`` bool [C],
+    ``displacement`` [N, 3] (A: the net move of every atom, never folded into the cell), ``rmsd`` [C] from it, ``n_rebuilds`` int32
+    [C]; with ``trace=True`` ``energy_trace`` and ``max_force_trace`` [max_steps + 1, C], entry k the values before move k and NaN
+    beyond a cell's last evaluation (None otherwise).  Of the final evaluation, as in ``CellEnergy`` (what the accuracy tests
+    compare): ``energy_per_atom`` [N], ``components`` [C, 5], ``components_per_atom`` [N, 5].  ``iterations`` (int): the
+    evaluate-and-step iterations launched, a multiple of ``check_every`` (what tools/cell_relax_time.py divides by)."""
+
+    def __init__(self, **kw):
+        self.energy_trace = self.max_force_trace = None
+        self.__dict__.update(kw)
+
+
+def _relax_list_need(cell_list, radius: float) -> int:
+    """the bytes of the held lists of a call, estimated from every cell's number density: no device"""
+    need = 0.0
+    for c in cell_list:
+        vol = abs(float(np.linalg.det(c.lattice.numpy())))
+        need += 8.0 * c.num_atoms * (c.num_atoms / vol) * 4.0 / 3.0 * math.pi * radius ** 3
+    return int(need)
+
+
+def _relax_check(cell_list, r_cut, f_max, max_steps, skin, fire, check_every, method):
+    """the refusals of ``relax`` beyond those of ``_ewald_setup`` -> (f_max, max_steps, skin, fire, check_every).  No device."""
+    f_max, skin = float(f_max), float(skin)
+    if not (math.isfinite(f_max) and f_max > 0.0):
+        raise ValueError(f"f_max = {f_max} must be positive and finite")
+    if int(max_steps) != max_steps or int(max_steps) < 0:
+        raise ValueError(f"max_steps = {max_steps} must be an integer >= 0")
+    if not (math.isfinite(skin) and skin > 0.0):
+        raise ValueError(f"skin = {skin} must be positive and finite")
+    fire = FireParameters() if fire is None else fire
+    if not isinstance(fire, FireParameters):
+        raise ValueError("fire must be a FireParameters or None")
+    if fire.max_step > skin / 2:
+        raise ValueError(f"max_step = {fire.max_step} exceeds skin / 2 = {skin / 2} (skin = {skin}): one move could outrun the held lists")
+    if int(check_every) != check_every or int(check_every) < 1:
+        raise ValueError("check_every must be an integer >= 1")
+    _check_method(method)
+    _check_lattice_boxes(np.stack([c.lattice.numpy().reshape(9) for c in cell_list]), r_cut + skin)   # the held lists reach r_cut + skin
+    need = _relax_list_need(cell_list, r_cut + skin)
+    if need > _RELAX_LIST_BYTES:
+        raise ValueError(f"the held site lists need about {need} bytes at radius r_cut + skin = {r_cut + skin} (at most _RELAX_LIST_BYTES = "
+                         f"{_RELAX_LIST_BYTES}; fewer cells per call, or a smaller r_cut or skin)")
+    return f_max, int(max_steps), skin, fire, int(check_every)
+
+
+def _wrap(frac: torch.Tensor) -> torch.Tensor:
+    """cell_wrap of csrc/cells/cell_math.h on a tensor: w = f - floor(f), 0 where that rounds to 1"""
+    w = frac - torch.floor(frac)
+    return torch.where(w < 1.0, w, torch.zeros_like(w))
+
+
+def relax(cells: Union[PeriodicCell, Sequence[PeriodicCell]], charges, potential: Optional[PairTable] = None, r_cut: float = 10.0,
+          short_cut: Optional[float] = None, shift: bool = True, accuracy: float = 1e-8, alpha: Optional[float] = None,
+          k_max: Optional[float] = None, coulomb_constant: float = COULOMB_CONSTANT, f_max: float = 1e-3, max_steps: int = 1000,
+          skin: float = 1.0, fire: Optional[FireParameters] = None, check_every: int = 16, trace: bool = False, method: str = "auto",
+          device=None) -> Relaxation:
+    """Relaxes the atoms of periodic cells in their fixed lattices down the energy of ``lattice_energy`` (the same model arguments,
+    the same refusals) by FIRE, on the device: every cell of the batch on its own, until its largest force is below ``f_max`` (eV / A)
+    or it has made ``max_steps`` moves (csrc/cells/cell_relax_math.h).  The real-space sites come from lists searched at ``r_cut +
+    skin`` and held: a cell whose next move would bring an atom further than ``skin / 2`` from where it stood when its list was
+    built does not move until the list has been rebuilt, so no evaluation misses a site; a cell whose list has just been built
+    always moves.  ``method`` as in ``neighbour_sites``: the same rows either way.  The loop launches ``check_every`` iterations
+    (evaluate, step) without a synchronisation, reads two flag arrays back, rebuilds where asked (no coordinate goes through the
+    host; every row is searched again, and a cell that did not ask gets its rows back bit for bit) and stops when every cell is
+    done.  All fp64, every sum in one fixed order: two runs agree bitwise, and a cell's trajectory does not depend on the batch it
+    is in or on ``check_every``.  ValueError beyond those of ``lattice_energy``: ``f_max <= 0``, ``max_steps < 0``, ``skin <= 0``,
+    ``fire.max_step > skin / 2``, a cell too thin for the image box of 4 at ``r_cut + skin``, held lists above
+    ``_RELAX_LIST_BYTES``, coincident atoms at an evaluation (naming the cell and the step), forces that are not finite.
+    RuntimeError: a cell froze twice without moving in between (a guard; the freeze rule excludes it).  The cell itself is not
+    relaxed, finished cells stay in the launches, and the reciprocal part is the direct sum of ``lattice_energy``."""
+    cell_list = _as_cells(cells)
+    A, q_h, pot_h, n, r_cut, short_cut, alpha, k_max, kappa = _ewald_setup(cell_list, charges, potential, r_cut, short_cut, accuracy, alpha,
+                                                                          k_max, coulomb_constant)
+    f_max, max_steps, skin, fire, check_every = _relax_check(cell_list, r_cut, f_max, max_steps, skin, fire, check_every, method)
+    cb = _CellBatch(cell_list, device)      # cb.frac: the REFERENCE coordinates the lists are searched on
+    lib, dev, N, C = _lib.lib(), cb.dev, cb.N, cb.C
+    cb.frac.copy_(_wrap(cb.frac))
+    u = cb.frac.clone()                      # the unwrapped coordinates the evaluations read
+    search = _SiteSearch(cb, r_cut + skin, method)
+    every, every_cell = _centres(cb, None)
+    gridded = None                           # the atoms of the cells whose rows come from the linked-cell bond list, as the sub-batch holds them
+    if search.grid_mask is not None:
+        gridded = torch.cat([torch.arange(cb.cell_ptr_h[c], cb.cell_ptr_h[c + 1]) for c in torch.nonzero(search.grid_mask).reshape(-1).tolist()]).to(dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    velocity, since, moved = (torch.zeros(max(N, 1), 3, **f64)[:N] for _ in range(3))
+    scalars = torch.zeros(C, _lib.RELAX_SCALARS, **f64)
+    scalars[:, 0], scalars[:, 1] = fire.dt, fire.a_start
+    counters = torch.zeros(C, _lib.RELAX_COUNTERS, dtype=torch.int32, device=dev)
+    flags = torch.zeros(2, C, dtype=torch.int32, device=dev)     # done, rebuild: one download
+    n_rebuilds = torch.zeros(C, dtype=torch.int32, device=dev)
+    coincident = torch.zeros(C, dtype=torch.int32, device=dev)
+    traces = torch.full((2, max_steps + 1, C), float("nan"), **f64) if trace else None
+    real, rec = _empty(N, 5, **f64), None
+    comp_atom, e_atom, force = _empty(N, 5, **f64), _empty(N, **f64), _empty(N, 3, **f64)
+    n_type = torch.empty(C, A, dtype=torch.int32, device=dev)
+    comp, energy = torch.empty(C, 5, **f64), torch.empty(C, **f64)
+    q_ptr, pot_ptr = _lib.host_ptr(q_h), (None if pot_h is None else _lib.host_ptr(pot_h))
+    ewald = (kappa, alpha, r_cut, k_max)
+    hp, dp, up = cb._host_ptrs, cb._dev_ptrs, _ptr_or_none(u, N)
+    head = (_lib.stream_ptr(), C, N, A, *hp, dp[0], dp[1], up, dp[3])     # cb.args(A=True, types=True) on u
+    calls = []                                                              # the launches of one evaluation after the real part
+    if bool(np.any(q_h != 0.0)):
+        vecs = _SqVectors(cb, k_max, "k_max")                               # the vectors of a fixed cell: counted once
+        hkl, table = _empty(vecs.K, 3, dtype=torch.int32, device=dev), _empty(vecs.K, 5, **f64)
+        rec = _empty(N, 4, **f64)
+        calls.append((lib.egnn_cell_ewald_amplitudes,
+                      (*head[:6], _lib.ptr(vecs.plan_h), _lib.ptr(vecs.vec_ptr_h), dp[0], dp[1], _lib.ptr(vecs.plan), _lib.ptr(vecs.vec_ptr), up,
+                       dp[3], q_ptr, *ewald, vecs.n_rows, _lib.ptr(vecs.row_ptr), vecs.K, _ptr_or_none(vecs.tiles), vecs.n_tiles,
+                       _ptr_or_none(hkl), _ptr_or_none(table))))
+        calls.append((lib.egnn_cell_ewald_recip,
+                      (*head[:6], _lib.ptr(vecs.vec_ptr_h), dp[0], dp[1], _lib.ptr(vecs.vec_ptr), up, dp[3], q_ptr, *ewald, 1, vecs.K,
+                       _ptr_or_none(hkl), _ptr_or_none(table), _ptr_or_none(rec))))
+    calls.append((lib.egnn_cell_ewald_finish,
+                  (*head[:6], dp[0], dp[1], dp[3], q_ptr, *ewald, _ptr_or_none(real), _ptr_or_none(rec), _lib.ptr(n_type),
+                   _ptr_or_none(comp_atom), _ptr_or_none(e_atom), _ptr_or_none(force), _lib.ptr(comp), _lib.ptr(energy))))
+    calls.append((lib.egnn_cell_relax_step,
+                  (_lib.stream_ptr(), C, N, *hp, dp[0], dp[1], _ptr_or_none(force), _lib.ptr(energy), _lib.ptr(coincident), *fire.step_args(),
+                   f_max, max_steps, skin, up, _ptr_or_none(velocity), _ptr_or_none(since), _ptr_or_none(moved), _lib.ptr(scalars),
+                   _lib.ptr(counters), _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(traces[0]) if trace else None,
+                   _lib.ptr(traces[1]) if trace else None)))
+    cell_ptr_l = cb.cell_ptr_h.tolist()
+
+    def held_rows(again=True):
+        if again and gridded is not None:     # the grid's own copy of the references, then its bond list again: all on the device
+            search.sub.frac.copy_(cb.frac[gridded])
+            search.bonds = _bond_list(search.sub, search.radius, "grid")
+        args, keep = _row_args(search, every, every_cell)
+        if 8 * int(keep[1].shape[0]) > _RELAX_LIST_BYTES:
+            raise ValueError(f"the held site lists need {8 * int(keep[1].shape[0])} bytes at radius r_cut + skin = {r_cut + skin} (at most "
+                             f"_RELAX_LIST_BYTES = {_RELAX_LIST_BYTES}; fewer cells per call, or a smaller r_cut or skin)")
+        return (lib.egnn_cell_relax_real, (*head, q_ptr, pot_ptr, n, int(bool(shift)), kappa, alpha, r_cut, short_cut, k_max, skin, *args,
+                                           _ptr_or_none(real), _lib.ptr(coincident))), keep
+
+    real_call, keep = held_rows(again=False)     # the search was built on these coordinates (the grid wraps on read)
+    iterations = 0
+    while N:
+        iterations += check_every
+        for _ in range(check_every):
+            _lib.check(real_call[0](*real_call[1]))
+            for fn, a in calls:
+                _lib.check(fn(*a))
+        done_h, ask_h = flags.cpu().bool()
+        if bool(done_h.all()):
+            break
+        ask = torch.nonzero(ask_h & ~done_h).reshape(-1)
+        if ask.numel():
+            atoms = torch.cat([torch.arange(cell_ptr_l[c], cell_ptr_l[c + 1]) for c in ask.tolist()]).to(dev)   # indices, not coordinates
+            ask = ask.to(dev)
+            w = _wrap(u[atoms])
+            u[atoms] = w
+            cb.frac[atoms] = w
+            since[atoms] = 0.0
+            flags[1, ask] = 0
+            n_rebuilds[ask] += 1
+            real_call, keep = held_rows()        # every row again, on the references: a cell that did not ask gets its rows back
+    status_h, steps_h = counters[:, 2].cpu(), counters[:, 1].cpu()
+    for code, what in ((_lib.RELAX_COINCIDENT, "coincident atoms (a site at distance 0 from its centre); the energy is not defined"),
+                       (_lib.RELAX_NOT_FINITE, "the forces are not finite")):
+        bad = torch.nonzero(status_h == code).reshape(-1).tolist()
+        if bad:
+            raise ValueError(f"cell {bad[0]}, step {int(steps_h[bad[0]])}: {what}" + (f" (also cells {bad[1:]})" if len(bad) > 1 else ""))
+    stuck = torch.nonzero(status_h == _lib.RELAX_STUCK).reshape(-1).tolist()
+    if stuck:
+        raise RuntimeError(f"cell {stuck[0]}, step {int(steps_h[stuck[0]])}: froze twice without moving in between (skin = {skin}, max_step = "
+                           f"{fire.max_step})")
+    frac_h, moved_h = u.cpu(), moved.cpu()
+    out = [PeriodicCell(c.lattice, frac_h[cell_ptr_l[k]:cell_ptr_l[k + 1]], types=c.types, id=c.id, num_types=c.num_types)
+           for k, c in enumerate(cell_list)]
+    d2 = (moved_h * moved_h).sum(1).numpy()
+    rmsd = np.array([math.sqrt(float(np.mean(d2[cell_ptr_l[k]:cell_ptr_l[k + 1]]))) if cell_ptr_l[k + 1] > cell_ptr_l[k] else 0.0
+                     for k in range(C)])
+    return Relaxation(cells=out, frac=u, energy=scalars[:, 2].clone(), initial_energy=scalars[:, 3].clone(), forces=force,
+                      max_force=scalars[:, 4].clone(), steps=counters[:, 1].clone(), converged=(counters[:, 2] == _lib.RELAX_CONVERGED),
+                      displacement=moved, rmsd=torch.from_numpy(rmsd).to(dev), n_rebuilds=n_rebuilds, energy_per_atom=e_atom,
+                      components=comp, components_per_atom=comp_atom, iterations=iterations,
+                      energy_trace=traces[0] if trace else None, max_force_trace=traces[1] if trace else None)

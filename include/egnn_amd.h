@@ -982,6 +982,59 @@ int egnn_cell_ewald_virial_host(int C, int A, const int32_t* cell_ptr, const dou
                                 double short_cut, double k_max, double* strain, double* components, double* per_atom, double* atom_components,
                                 double* stress, double* pressure, int64_t* n_vectors, int32_t* coincident);
 
+/* ---- relaxation of periodic cells: FIRE over held site lists (csrc/cells/cell_relax.hip; definitions in
+ * csrc/cells/cell_relax_math.h) ---------------------------------------------------------------------------------------------
+ * The atoms of a fixed cell move down the lattice energy above by FIRE (Bitzek et al., PRL 97, 170201; unit mass 1).  An extension:
+ * no file of the reference relaxes a structure.  The sites of an evaluation come from rows of egnn_cell_sites_* at cut = r_cut +
+ * skin that are held while no atom has moved more than skin / 2 since they were built.  State of a call, caller-owned device
+ * arrays: d_frac double [N, 3] UNWRAPPED fractional coordinates, d_velocity, d_since (the Cartesian move since the cell's list was
+ * built) and d_moved (the net move) double [N, 3]; d_scalars double [C, 5] = (dt, a, energy, initial energy, max force); d_counters
+ * int32 [C, 4] = (n_pos, steps, status: 0 running, 1 converged, 2 step limit, 3 coincident atoms, 4 forces not finite, 5 stuck: froze
+ * twice without a move in between; frozen: steps + 1 of the last freeze, 0 at the start); d_done and
+ * d_rebuild int32 [C].  All fp64, no floating-point atomic, every sum in one fixed order that depends on the cell alone: results are
+ * bitwise reproducible and a cell gives the same bits in any batch.  Bad arguments are EGNN_EINVAL with a message before anything
+ * is launched.
+ *
+ * egnn_cell_relax_real (an extension): egnn_cell_ewald_real over HELD rows -- the arguments of that entry with `skin` in place of
+ * `forces` (always computed); d_frac is read unwrapped, the vector of site (j, s) is ((u_j - u_i) + s) L in the operation order of
+ * the search, and an entry counts iff cell_norm2(d) < r_cut^2 now.  The image box of r_cut + skin must stay within 4.
+ * egnn_cell_relax_step (an extension): one step of every cell from d_force double [N, 3], d_energy double [C] and d_coincident int32
+ * [C] of an evaluation: convergence (max |F| < f_max), the step limit, the FIRE update, the cap max_step on the largest move of an
+ * atom, the freeze rule (a move that would bring an atom beyond skin / 2 since the build is not made: d_rebuild is set and nothing
+ * else of the cell changes; a cell whose d_since is all zero, just built, always moves), the move, the counters.  A cell with d_done or d_rebuild set is left alone; the caller rebuilds
+ * (d_frac <- wrapped, d_since <- 0, the rows searched again) and clears d_rebuild.  d_energy_trace, d_force_trace double
+ * [max_steps + 1, C] or NULL: row k holds the energy and max |F| before move k.  max_step <= skin / 2. */
+int egnn_cell_relax_real(void* stream, int C, int N, int A, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                         const double* d_lattice, const double* d_frac, const int32_t* d_type, const double* charges, const double* pot, int n,
+                         int shift, double kappa, double alpha, double r_cut, double short_cut, double k_max, double skin, int n_rows,
+                         const int32_t* d_row_ptr, int T, const int32_t* d_site_atom, const int32_t* d_site_shift, int M,
+                         const int32_t* d_centre_atom, const int32_t* d_centre_row, double* d_real, int32_t* d_coincident);
+int egnn_cell_relax_step(void* stream, int C, int N, const int32_t* cell_ptr, const double* lattice, const int32_t* d_cell_ptr,
+                         const double* d_lattice, const double* d_force, const double* d_energy, const int32_t* d_coincident, double dt_max,
+                         int n_min, double f_inc, double f_dec, double a_start, double f_a, double max_step, double f_max, int max_steps,
+                         double skin, double* d_frac, double* d_velocity, double* d_since, double* d_moved, double* d_scalars,
+                         int32_t* d_counters, int32_t* d_done, int32_t* d_rebuild, double* d_energy_trace, double* d_force_trace);
+/* Host statement of egnn_cell_relax_step (an extension): HOST pointers, no GPU, the same text in plain C++; bitwise what the kernel
+ * gives. */
+int egnn_cell_relax_step_host(int C, int N, const int32_t* cell_ptr, const double* lattice, const double* force, const double* energy,
+                              const int32_t* coincident, double dt_max, int n_min, double f_inc, double f_dec, double a_start, double f_a,
+                              double max_step, double f_max, int max_steps, double skin, double* frac, double* velocity, double* since,
+                              double* moved, double* scalars, int32_t* counters, int32_t* done, int32_t* rebuild, double* energy_trace,
+                              double* force_trace);
+/* Host statement of the whole relaxation (an extension): HOST pointers, no GPU.  Per cell: the held list at r_cut + skin by the box
+ * walk of egnn_cell_ewald_host, the evaluation by the code behind that statement with the real part added over the held row in
+ * ascending order, the step above, a rebuild as soon as the cell asks.  dt is the first time step.  Always written: frac_out [N, 3]
+ * (unwrapped since the last build), energy, initial_energy, max_force double [C], force [N, 3] at the final coordinates, steps,
+ * status and n_rebuilds int32 [C], moved [N, 3].  Where given: energy_trace, force_trace [max_steps + 1, C] and frac_trace
+ * [max_steps + 1, N, 3] (the coordinates evaluated before move k), NaN beyond a cell's last evaluation.  The refusals of
+ * egnn_cell_ewald_host and of the step; the image box of r_cut + skin within 4. */
+int egnn_cell_relax_host(int C, int A, const int32_t* cell_ptr, const double* lattice, const double* frac, const int32_t* type,
+                         const double* charges, const double* pot, int n, int shift, double kappa, double alpha, double r_cut, double short_cut,
+                         double k_max, double dt, double dt_max, int n_min, double f_inc, double f_dec, double a_start, double f_a, double max_step,
+                         double f_max, int max_steps, double skin, double* frac_out, double* energy, double* initial_energy, double* force,
+                         double* max_force, int32_t* steps, int32_t* status, double* moved, int32_t* n_rebuilds, double* energy_trace,
+                         double* force_trace, double* frac_trace);
+
 /* ---- structure factors (csrc/eval/sq.hip; definitions in csrc/eval/sq_math.h) -----------------------------------------------
  * Reciprocal-space statistics: Debye sums of clusters and reciprocal-lattice sums of periodic cells.  No file of the reference
  * computes them (an extension, like the rings).  All sums are fp64 in one fixed order, no floating-point atomic: results are

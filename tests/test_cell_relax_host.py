@@ -8,6 +8,8 @@ the definitions the kernels compile, csrc/cells/cell_relax_math.h) against
     a face of the cell (there egnn_cell_ewald_host wraps, names the same sites by other shifts and so adds them in another order:
     DESIGN.md 5.13);
   * what a relaxation must reach: the ideal rocksalt sites (by symmetry stationary), with and without rebuilds, from translated copies.
+The constructions of tests/test_gpu_cell_relax_held.py (held rows at moved coordinates): the entries that pass the re-test in numpy are
+the rows of the truth, entries have entered and left r_cut where a case claims it, the gap and E_host conditions hold.
 Refusals of cells.relax (raised before a device is touched) and of the host statements, and a stand-alone program under the address
 and undefined-behaviour sanitizers.  No GPU.
 """
@@ -17,6 +19,8 @@ import pytest
 from diffusion_model_amd import _lib, cells
 from tests import _cell_ewald_util as EU
 from tests import _cell_relax_util as RU
+from tests import _cell_soap_util as CSU
+from tests import _cells_util as CU
 
 EINVAL = -22
 # the untranslated fixture against the restatement driven by egnn_cell_ewald_host, measured here: 2.3e-16 in a fractional coordinate
@@ -239,6 +243,80 @@ def test_refusals_of_relax_come_before_the_device():
         cells.FireParameters(f_dec=1.5)
     f = cells.FireParameters()
     assert (f.dt, f.dt_max, f.n_min, f.f_inc, f.f_dec, f.a_start, f.f_a, f.max_step) == (0.1, 1.0, 5, 1.1, 0.5, 0.1, 0.99, 0.2)
+
+
+# ---- the constructions of tests/test_gpu_cell_relax_held.py ---------------------------------------------------------------------------------
+def _names(j, s, keep):
+    return {(int(a), *map(int, b)) for a, b in zip(j[keep], s[keep])}
+
+
+@pytest.mark.parametrize("name", list(RU.HELD_CASES))
+def test_held_cases_are_what_they_claim(name):
+    """every held case of the device tests, without a device: the entries of the held rows that pass the re-test in numpy are the rows
+    of the truth, "entered" and "left" are met where claimed, and the conditions on the gap and on E_host hold"""
+    h = RU.held(name)
+    case, ref, skin = h["case"], h["ref"], h["skin"]
+    ex, e_host = RU.held_truth(name)
+    rows, truth = RU.held_retest(h), RU.truth_rows_as_held(h, ex)
+    n_held, n_kept = [len(r[0]) for r in rows], [int(r[2].sum()) for r in rows]
+    entered, left = [int((r[2] & ~r[3]).sum()) for r in rows], [int((r[3] & ~r[2]).sum()) for r in rows]
+    print(f"{name}: r_cut = {case['r_cut']:.6f} skin = {skin} held {n_held} kept {n_kept} entered {entered} left {left} gap = {float(ex['gap']):.2e} "
+          f"E_host = {e_host:.2e}")
+    assert e_host <= EU.CAP and float(ex["gap"]) > EU.GAP                       # conditions, not measurements
+    assert case["alpha"] * case["r_cut"] <= 3.0 and not case["shift"]
+    length = np.sqrt((h["delta"] ** 2).sum(1))
+    assert length.max() <= skin / 2 and (name in ("limit", "outside", "pair", "single") or (length.min() == 0.0 and length.max() > 0.99 * skin / 2))
+    L = np.asarray(ref["lattice"], np.float64)
+    assert CSU.box(L, case["r_cut"] + skin).max() <= 4                         # the range of the shift code
+    for i, (j, s, now, then, d) in enumerate(rows):
+        assert _names(j, s, now) == truth[i] and n_kept[i] == len(truth[i]) == int(ex["row_ptr"][i + 1] - ex["row_ptr"][i]), i
+        own = j == i                                                           # an own image moves with its centre: s L whatever delta_i
+        assert np.array_equal(d[own], CU.site_vectors(np.zeros(3), np.zeros(3), s[own], L))
+    if name in RU.HELD_MOVED:                                                  # in EVERY row an entry has entered r_cut and one has left it
+        assert min(entered) > 0 and min(left) > 0
+    u = case["cell"]["frac"]
+    if name.startswith("row"):
+        assert int(name[3:]) in n_kept
+    if ref["name"] == "thin8":
+        assert ((u < 0.0) | (u >= 1.0)).any()                                  # a coordinate outside [0, 1)
+        assert CSU.box(L, case["r_cut"] + skin).tolist() == ([2, 1, 1] if name == "row1" else [4, 1, 2])
+    if name == "three":                                                        # three passes of a wavefront, less than one kept
+        assert all(128 < a <= 192 for a in n_held) and all(0 < b < 64 for b in n_kept)
+    if name == "outside":
+        assert n_held == [6] and n_kept == [0]
+    if name == "limit":                                                        # the outermost entry of its row counts; the inner one does not
+        assert n_held == [1, 1, 1, 1] and n_kept == [1, 1, 0, 0] and entered == [1, 1, 0, 0] and left == [0, 0, 1, 1]
+        built = [float(np.sqrt(EU._norm2(CSU.sites(ref, case["r_cut"] + skin, i)[2]))[0]) for i in range(4)]
+        assert all(case["r_cut"] + skin - 2e-3 < b < case["r_cut"] + skin for b in built[:2])
+        assert all(case["r_cut"] - skin < b < case["r_cut"] - skin + 2e-3 for b in built[2:])
+    if name == "face":
+        assert u[0, 0] > 1.0 and not h["delta"][1].any()
+        j, s, now, _, _ = rows[0]
+        assert (1, 1, 0, 0) in _names(j, s, now)                               # the unmoved neighbour across the face, named from w0
+        assert any(a == 0 for a, *_ in _names(j, s, now))                      # an image of the centre itself
+
+
+def test_held_coincidence_appears_only_after_the_move():
+    L = _lib.lib()
+    h = RU.held("coincide")
+    u = h["case"]["cell"]["frac"]
+    assert np.array_equal(u[0], u[1]) and np.abs(h["delta"]).max() <= h["skin"] / 2
+    assert np.array_equal(h["ref"]["frac"] + h["delta"] / 4.0, u)              # exact in a cube of 4 A
+    rc, now = EU.host(L, [h["case"]])
+    rc0, then = EU.host(L, [dict(h["case"], cell=h["ref"])])
+    assert rc == 0 and rc0 == 0 and now["coincident"].tolist() == [1] and then["coincident"].tolist() == [0]
+    j, s, inside, _, d = RU.held_retest(h)[0]
+    at = np.nonzero((j == 1) & (s == 0).all(1))[0]
+    assert len(at) == 1 and inside[at[0]] and not d[at[0]].any()
+
+
+@pytest.mark.parametrize("name", list(EU.fixtures()))
+def test_fp64_scales_are_those_of_the_truth(name):
+    """tests/_cell_relax_util.scales (the yardstick of a cell too large for 50 digits) against the scales of the five fixtures' truth: a
+    sum of n positive fp64 terms is within n ulp of the sum at 50 digits, n below 1e4 here"""
+    se, sf = RU.scales(EU.fixtures()[name])
+    want = EU.truth(name)
+    assert np.allclose(se, want["scale_e"], rtol=1e-12, atol=0.0) and np.allclose(sf, want["scale_f"], rtol=1e-12, atol=0.0)
 
 
 def test_cell_relax_host_under_sanitizers(tmp_path):
